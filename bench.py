@@ -19,7 +19,12 @@ rank filters its range with the carry of the lower ranges; one RCCL all-reduce
 sums the match counters.  `--mode selfmum` runs the other sharded path of
 SURVEY 8e instead: the self-index MUM scan split into suffix-array ranges.
 
-Prints ONE JSON line on rank 0.  Everything in it is measured in this run:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps and prints the headline (metric, value, unit, ms_per_step, the counters
+of the job); `--dump-outputs DIR` also writes what the last timed step handed
+its caller (dump_outputs below).  `--full` adds the figures that take runs of
+their own, every one measured in this run:
+  reads_as_bytes     the same batch resident as one byte per symbol
   roofline           the dominant kernel (k_query_search_planned), HIP-event time
   roofline_families  the same for the other kernel families of the path --
                      first pass, -complete (K1), MEM, -complete -e 2 (piece
@@ -29,8 +34,9 @@ Prints ONE JSON line on rank 0.  Everything in it is measured in this run:
                      vsa_mkvtree) on P = all host cores given to the box
                      (P processes over 1/P of the sample each, wall = slowest)
                      and on one core; the CPU restatement (oracle) on one core
-`--quick` leaves the extra families and the reference program out (A/B runs,
-profiling passes).
+  mum_150bp, end_to_end  the other read length and the host-memory pipelines
+`--full --quick` leaves the extra families and the reference program out (A/B
+runs, profiling passes).
 """
 import argparse
 import ctypes as C
@@ -100,8 +106,16 @@ def parse():
                     help="how the query batch lies in HBM: the reference's "
                          "Multiseq bytes, or two bits per symbol "
                          "(vsa_pack_reads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: "
+                         "roofline, other kernel families and read lengths, "
+                         "the byte form of the reads, end-to-end pipelines, "
+                         "CPU and reference baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "returned to its caller as DIR/<name>.npy (float64)")
     ap.add_argument("--quick", action="store_true",
-                    help="headline step and its roofline only")
+                    help="with --full: headline step and its roofline only")
     ap.add_argument("--no-reference", action="store_true",
                     help="do not run oracle/_ref/vmatch_ref")
     ap.add_argument("--workdir", default="/dev/shm")
@@ -138,7 +152,10 @@ def parse():
     # to the torch form can be rehearsed on a box with one GPU)
     ap.add_argument("--test-fail-c-path", action="store_true",
                     help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # what the kernels of a default run are compiled from
@@ -155,6 +172,30 @@ def kernel_source_hash():
         with open(os.path.join(ROOT, "vstree_amd", "csrc", f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+DUMP_ROWS = 1 << 20     # rows of a match list written at most (32 MB)
+DUMP_SEED = 7
+
+
+def dump_outputs(dirname, matches, counters):
+    """--dump-outputs: the match list the last timed step returned, one
+    float64 file per field (positions below 2^53 are exact), and the counters
+    of that call.  A list longer than DUMP_ROWS is written as a fixed, seeded
+    sample of its rows, in list order; rows.npy says which."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.arange(len(matches))
+    if len(matches) > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(
+            len(matches), DUMP_ROWS, replace=False))
+    sample = matches[rows]
+    for field in matches.dtype.names:
+        np.save(os.path.join(dirname, field + ".npy"),
+                sample[field].astype(np.float64))
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    for name, v in counters.items():
+        np.save(os.path.join(dirname, name + ".npy"),
+                np.array([v], np.float64))
 
 
 def count_bytes(H, run, nq, w, symbols):
@@ -358,7 +399,8 @@ def reference_baseline(a, V, H, genome, qsym, m, L, ncores):
         # on the same files: whole process, incl. mapping the index, its
         # upload to HBM, the derived tables, FASTA parsing and printing
         dropin = None
-        gpubin = os.path.join(ROOT, "integration", "_build", "vmatch_gpu")
+        gpubin = os.path.join(ROOT, "oracle", "_ref", "integration",
+                              "vmatch_gpu")
         if os.access(gpubin, os.X_OK):
             with open(wd + "/qall.fna", "wb") as f:
                 for p in range(ncores):
@@ -382,9 +424,9 @@ def reference_baseline(a, V, H, genome, qsym, m, L, ncores):
             if pr.returncode == 0 and nm > 0:
                 dropin = {"value": nsp / td, "unit": "queries/s",
                           "wall_s": td, "queries": nsp, "mums": nm,
-                          "what": "integration/_build/vmatch_gpu -mum -l %d "
-                                  "-q (the reference program with the GPU "
-                                  "engine linked in): whole process, index "
+                          "what": "oracle/_ref/integration/vmatch_gpu -mum "
+                                  "-l %d -q (the reference program with the "
+                                  "GPU engine linked in): whole process, index "
                                   "files -> HBM included" % L,
                           "trace": trace,
                           "reference_same_queries_16_processes_s": tp}
@@ -657,7 +699,7 @@ def c_path_mode(a, jsonfd, rank, world):
         out["bytes_over_pcie_per_step"] = int(nq * N * m + 16 * nq * N +
                                               32 * int(st.count))
     borrowed = None
-    if not a.quick:
+    if a.full and not a.quick:
         try:
             # the kernel's algorithmic bytes, counted like the N = 1 line does: on
             # the searches the plans of block 0 hold (test infrastructure: the
@@ -757,6 +799,11 @@ def main():
         a.path = "c" if (a.gpus > 1 and a.mode == "mum" and
                          not a.rehearse_on_one_gpu and
                          not a.force_distributed) else "torch"
+    if a.dump_outputs and (a.gpus > 1 or a.path == "c" or
+                           a.force_distributed):
+        log("bench.py: --dump-outputs is written by the one-process path "
+            "(--gpus 1, --path torch) only")
+        sys.exit(2)
     if a.path == "c" and world not in (1, a.gpus):
         log("bench.py: --gpus %d but WORLD_SIZE=%d: refusing to print a line "
             "for another number of GPUs than asked for" % (a.gpus, world))
@@ -839,13 +886,16 @@ def main():
     if a.reads == "packed":
         hq = np.empty(nq * m, np.uint8)
         V.device_download(hq, dq, dev)
-        bytequeries = queries      # (timed for comparison behind the steps)
-        bytequeries.set_offset(rank * nq)
+        if a.full:
+            bytequeries = queries  # (timed for comparison behind the steps)
+            bytequeries.set_offset(rank * nq)
+        else:
+            queries.close()
         queries = V.Queries.from_host_packed(hq, m, dev)
         del hq
     queries.set_offset(rank * nq)
     V.device_free(dq, dev)
-    extras = rank == 0 and world == 1 and not a.quick
+    extras = rank == 0 and world == 1 and a.full and not a.quick
     q150 = hq150 = None
     if extras:
         # BASELINE configs[4]: 150 bp reads of the same genome
@@ -888,10 +938,12 @@ def main():
     if distributed and not a.rehearse_on_one_gpu:
         rowbuf[0] = torch.empty(2 * 1024, dtype=torch.int64, device="cuda")
 
-    def one_step():
+    kept = None     # --dump-outputs: the match list of the last timed step
+
+    def one_step(keep=False):
         """the hot path over the whole batch; returns (count, sumlength,
         searches, candidates) of the job"""
-        nonlocal totals
+        nonlocal totals, kept
         if not distributed:
             r = V.findquerymatches(index, queries, L, mum=True)
             s = r.stats()
@@ -899,7 +951,10 @@ def main():
             first_ms.append(s.first_kernel_ms)
             totals = (s.count, s.sumlength, s.searches, s.candidates,
                       s.kernel_searches)
-            r.close()
+            if keep:
+                kept = r
+            else:
+                r.close()
             return
         # phase 1: candidates of this rank's queries (no communication), in
         # the order the kernel left them, grouped by the rank that filters
@@ -969,8 +1024,8 @@ def main():
     first_ms.clear()
     sync()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        one_step()
+    for i in range(a.steps):
+        one_step(keep=bool(a.dump_outputs) and i == a.steps - 1)
     if distributed:
         # the final match-count reduction of the job (every step produces the
         # same counters here; a real job would have summed them over its
@@ -986,6 +1041,12 @@ def main():
         elapsed = float(e.item())
 
     count, sumlength, searches, candidates, kernel_searches = totals
+    if kept is not None:
+        dump_outputs(a.dump_outputs, kept.fetch(),
+                     {"matches": count, "sumlength": sumlength,
+                      "candidates": candidates,
+                      "query_suffix_searches": searches})
+        kept.close()
     bytes_form = None
     if bytequeries is not None and not distributed:
         # the same batch as the reference's Multiseq bytes, a few steps
@@ -1050,7 +1111,7 @@ def main():
     if bytes_form is not None:
         out["reads_as_bytes"] = bytes_form
 
-    if rank == 0:
+    if rank == 0 and a.full:
         import helpers as H  # test infrastructure: the CPU oracle
         w = info.device_integersize // 8
         t = index.download()
@@ -1219,6 +1280,7 @@ def main():
                         "+ WRITE_SIZE of every dispatch between the first "
                         "pass of one step and the first pass of the next, "
                         "%s) / ms_per_step of this run" % tj.get("source")}
+    if rank == 0:
         sys.stdout.flush()
         os.write(jsonfd, (json.dumps(out) + "\n").encode())
     if distributed:
@@ -1601,14 +1663,18 @@ def selfmum_mode(a, V, S, torch, dist, rank, world, dev, jsonfd):
             torch.cuda.synchronize()
 
     kms = []
+    kept = None     # --dump-outputs: the match list of the last timed step
 
-    def one_step():
-        nonlocal totals
+    def one_step(keep=False):
+        nonlocal totals, kept
         r = V.findmaximaluniquematches(idx, L, first, last)
         s = r.stats()
         kms.append(s.search_kernel_ms)
         totals = [s.count, s.sumlength]
-        r.close()
+        if keep:
+            kept = r
+        else:
+            r.close()
         if distributed:
             totals = Sh.all_reduce_counters(
                 dist, torch, totals,
@@ -1619,8 +1685,8 @@ def selfmum_mode(a, V, S, torch, dist, rank, world, dev, jsonfd):
     kms.clear()
     sync()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        one_step()
+    for i in range(a.steps):
+        one_step(keep=bool(a.dump_outputs) and i == a.steps - 1)
     sync()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -1628,6 +1694,10 @@ def selfmum_mode(a, V, S, torch, dist, rank, world, dev, jsonfd):
                          device="cpu" if a.rehearse_on_one_gpu else "cuda")
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if kept is not None:
+        dump_outputs(a.dump_outputs, kept.fetch(),
+                     {"matches": totals[0], "sumlength": totals[1]})
+        kept.close()
     if rank == 0:
         ms = float(np.mean(kms))
         nbytes = 2.0 * (last - first)

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Wall clock of the drop-in binary (integration/_build/vmatch_gpu: the
+"""Wall clock of the drop-in binary (oracle/_ref/integration/vmatch_gpu: the
 reference's vmatch with the GPU engine linked in) on a 3 Gbp index for 0.2 M,
 2 M and 10 M reads of 100 bp, `-mum -l 20`, next to the unmodified reference
 on 16 processes (1/16 of the reads each, wall = slowest): where the GPU
 program's start-up (index files -> HBM + derived tables) is paid back.
 VSA_TRACE=1 prints the phases of the upload.  Needs oracle/_ref and
-integration/_build (built where /root/reference exists).
+oracle/_ref/integration (built where the reference's sources are).
 usage: dropin_startup_probe.py [genome bp] [workdir]"""
 import json
 import os
@@ -47,7 +47,7 @@ try:
     hit = np.flatnonzero(sub != V.NO_SUBST)
     rows[hit, sub[hit]] = (rows[hit, sub[hit]] + step[hit]) & 3
     del g
-    gpubin = os.path.join(ROOT, "integration", "_build", "vmatch_gpu")
+    gpubin = os.path.join(ROOT, "oracle", "_ref", "integration", "vmatch_gpu")
     args = ["-mum", "-l", str(L), "-q"]
     # page the index files in once (both programs map them)
     B.write_queries(wd + "/warm.fna", qsym, m, 0, 20000)

@@ -17,8 +17,8 @@ while read -r line; do
   case "$line" in "2 "*) steps=2; line=${line#2 };; esac
   # a line that starts with "F " runs the WHOLE bench (every kernel family,
   # the self-index scan; no reference program) whatever the arguments say
-  args=("$@")
-  case "$line" in "F "*) line=${line#F }; args=(--no-reference);; esac
+  args=(--full "$@")
+  case "$line" in "F "*) line=${line#F }; args=(--full --no-reference);; esac
   echo $steps > $R/gpurun_out/$OUT/p$i.steps
   timeout -k 10 300 rocprofv3 --pmc $line --output-format csv -d $R/gpurun_out/$OUT/p$i -- python3 $R/bench.py --steps $steps --warmup 0 --cpu-sample 0 "${args[@]}" > $R/gpurun_out/$OUT/p$i.json 2> $R/gpurun_out/$OUT/p$i.err
   rc=$?

@@ -12,7 +12,7 @@ i=0
 for line in "$@"; do
   i=$((i+1))
   export $ENVS
-  timeout -k 10 200 rocprofv3 --pmc $line --output-format csv -d $OUT/p$i -- python3 $R/bench.py --steps 1 --warmup 0 --cpu-sample 0 --quick > $OUT/p$i.json 2> $OUT/p$i.err
+  timeout -k 10 200 rocprofv3 --pmc $line --output-format csv -d $OUT/p$i -- python3 $R/bench.py --steps 1 --warmup 0 --cpu-sample 0 --full --quick > $OUT/p$i.json 2> $OUT/p$i.err
   rc=$?
   echo "pass $i rc=$rc : $line" >> $OUT/progress.log
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi

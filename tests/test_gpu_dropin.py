@@ -4,8 +4,8 @@ wrapped onto the GPU library (integration/vmengine_shim.c) must print what the
 unmodified reference printed (md5 of the output lines in the golden manifest).
 
 Needs the prebuilt binaries oracle/_ref/mkvtree_ref (writes the index files)
-and integration/_build/vmatch_gpu; both are built in the build container and
-travel to the GPU box."""
+and oracle/_ref/integration/vmatch_gpu; both are built in the build container
+and travel to the GPU box."""
 import gzip
 import hashlib
 import os
@@ -19,11 +19,12 @@ import helpers as H
 
 pytestmark = pytest.mark.gpu
 M = H.manifest()
-VMATCH_GPU = os.path.join(H.ROOT, "integration", "_build", "vmatch_gpu")
+VMATCH_GPU = os.path.join(H.REF_DIR, "integration", "vmatch_gpu")
 
 needs_binaries = pytest.mark.skipif(
     not (os.access(VMATCH_GPU, os.X_OK) and os.access(H.MKVTREE_REF, os.X_OK)),
-    reason="integration/_build/vmatch_gpu or oracle/_ref/mkvtree_ref not built")
+    reason="oracle/_ref/integration/vmatch_gpu or oracle/_ref/mkvtree_ref not "
+    "built")
 
 
 def stage(case, wd):
@@ -163,14 +164,14 @@ def test_selection_function_plugin_still_sees_every_match(tmp_path):
 
 # ---- boundary B2: the reference's dlopen hook for complete matches ---------
 
-PLUGIN_DIR = os.path.join(H.ROOT, "integration", "_build")
+PLUGIN_DIR = os.path.join(H.REF_DIR, "integration")
 PLUGIN = "cpridxps_amd.so"
 
 needs_plugin = pytest.mark.skipif(
     not (os.path.exists(os.path.join(PLUGIN_DIR, PLUGIN)) and
          os.access(H.VMATCH_REF, os.X_OK) and
          os.access(H.MKVTREE_REF, os.X_OK)),
-    reason="integration/_build/cpridxps_amd.so or oracle/_ref not built")
+    reason="oracle/_ref/integration/cpridxps_amd.so or oracle/_ref not built")
 
 
 def run_ref_vmatch_with_plugin(args, wd):

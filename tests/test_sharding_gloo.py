@@ -14,6 +14,32 @@ import helpers as H
 WORLD = 2
 
 
+def _spawn(fn, args, timeout=600):
+    """fn(rank, *args) for every rank, each in a fresh process; fails when one
+    of them fails (the others are stopped).  The stdlib's spawn and not
+    torch.multiprocessing: importing torch here would map its HIP runtime
+    into the pytest process beside the one libvstree_amd.so links, and a
+    process that has used the GPU through both does not survive its exit."""
+    import multiprocessing
+    import time
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(rank,) + tuple(args))
+             for rank in range(WORLD)]
+    for p in procs:
+        p.start()
+    deadline = time.monotonic() + timeout
+    while any(p.is_alive() for p in procs) and time.monotonic() < deadline:
+        if any(p.exitcode not in (None, 0) for p in procs):
+            break
+        time.sleep(0.1)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+        p.join()
+    codes = [p.exitcode for p in procs]
+    assert codes == [0] * WORLD, "ranks ended with %r" % (codes,)
+
+
 def _worker(rank, world, port, outdir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -124,14 +150,12 @@ def _worker(rank, world, port, outdir):
 
 def test_two_ranks_reproduce_the_single_process_reference(tmp_path):
     import socket
-    import torch.multiprocessing as mp
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     H.load_case("c1")          # warm the oracle build before forking
-    mp.spawn(_worker, args=(WORLD, port, str(tmp_path)), nprocs=WORLD,
-             join=True)
+    _spawn(_worker, (WORLD, port, str(tmp_path)))
     out = np.load(os.path.join(str(tmp_path), "out.npz"))
     idx, q = H.load_case("c1")
     want_mum = H.expected("c1", "mum20")
@@ -179,14 +203,12 @@ def test_self_index_scan_split_over_two_ranks(tmp_path):
     ranges, one per rank; rank order = suffix-array order = reference order;
     only the counters are reduced."""
     import socket
-    import torch.multiprocessing as mp
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     idx, _ = H.load_case("grumbach_all")
-    mp.spawn(_selfmum_worker, args=(WORLD, port, str(tmp_path)),
-             nprocs=WORLD, join=True)
+    _spawn(_selfmum_worker, (WORLD, port, str(tmp_path)))
     out = np.load(os.path.join(str(tmp_path), "selfmum.npz"))
     want = H.expected("grumbach_all", "selfmum14")
     assert np.array_equal(H.selfmatches_as_ref(idx, out["mums"]), want)
