@@ -161,6 +161,195 @@ def test_planted_answers_and_global_mum_filter(V, world):
 
 
 # ---------------------------------------------------------------------------
+# The headline configuration off the generator's happy path: a batch of NQ
+# reads in four interleaved families, packed (what bench.py times) and as
+# bytes, on the same 3 Gbp index
+# ---------------------------------------------------------------------------
+
+FAMILIES = 4
+
+
+def mixed_batch(w, nq, m, seed):
+    """nq reads of m symbols, family i % 4: (a) the generator's reads, (b)
+    4 % substitutions and 0.5 % indels per symbol, (c) reads of an unrelated
+    random genome, (d) 1..3 wildcards at offset 0, D - 1 = 15, inside the key
+    window 16..25 and elsewhere.  numpy, vectorized; -> (nq * m,) symbols"""
+    g = w["host"].tis
+    rng = np.random.default_rng(seed)
+    out = np.zeros((nq, m), np.uint8)
+    col = np.arange(m, dtype=np.int64)
+    fam = np.arange(nq) % FAMILIES
+    # (a): the generator's plan of the first nq reads (cut + one substitution
+    # for a quarter), as host_queries builds them
+    a = np.flatnonzero(fam == 0)
+    pos, sub, step = generator_plan(w, nq, m)
+    out[a] = g[pos[a, None].astype(np.int64) + col]
+    s = a[sub[a] != 0xFFFFFFFF]
+    out[s, sub[s]] = (out[s, sub[s]] + step[s]) & 3
+    # (b): per symbol keep / substitute / delete (skip one source symbol) /
+    # insert (a random symbol, the source stays)
+    b = np.flatnonzero(fam == 1)
+    p = rng.integers(0, N - 2 * m, len(b))
+    ev = rng.random((len(b), m))
+    dele, ins = ev < 0.0025, (ev >= 0.0025) & (ev < 0.005)
+    subs = (ev >= 0.005) & (ev < 0.045)
+    src = col + np.cumsum(dele, axis=1) - np.cumsum(ins, axis=1) + m // 2
+    x = g[p[:, None] + src]
+    x = np.where(subs, (x + rng.integers(1, 4, x.shape)) & 3, x)
+    out[b] = np.where(ins, rng.integers(0, 4, x.shape), x).astype(np.uint8)
+    # (c): another genome
+    c = np.flatnonzero(fam == 2)
+    other = rng.integers(0, 4, 10 ** 7).astype(np.uint8)
+    out[c] = other[rng.integers(0, len(other) - m, len(c))[:, None] + col]
+    # (d): cut from the text, then wildcards
+    d = np.flatnonzero(fam == 3)
+    out[d] = g[rng.integers(0, N - m, len(d))[:, None] + col]
+    places = np.stack([np.zeros(len(d), np.int64), np.full(len(d), 15),
+                       rng.integers(16, 26, len(d)),
+                       rng.integers(0, m, len(d))], 1)
+    k = rng.integers(1, 4, len(d))
+    first = np.arange(len(d)) % 4
+    out[d, places[np.arange(len(d)), first]] = H.WILDCARD
+    for extra in (1, 2):
+        e = np.flatnonzero(k > extra)
+        out[d[e], places[e, rng.integers(0, 4, len(e))]] = H.WILDCARD
+    return out.ravel()
+
+
+def generator_plan(w, nq, m):
+    if nq == NQ and m == M:
+        return w["pos"], w["sub"], w["step"]
+    import vstree_amd as V
+    return V.synth_query_plan(N, nq, m)
+
+
+@pytest.fixture(scope="module", params=[(NQ, M), (max(1, NQ // 10), 150)],
+                ids=["100bp", "150bp"])
+def mixed(V, world, request):
+    nq, m = request.param
+    sym = mixed_batch(world, nq, m, 5150 + m)
+    packed = V.Queries.from_host_packed(sym, m)
+    byte = V.Queries.from_host(sym, np.arange(nq, dtype=np.uint64) * m,
+                               np.full(nq, m, np.uint64))
+    assert packed.nq == byte.nq == nq
+    # >= 2000 sampled reads per family, spread over the batch
+    per = np.arange(0, nq // FAMILIES, max(1, nq // FAMILIES // 2000))[:2000]
+    sel = np.sort(np.concatenate([per * FAMILIES + f
+                                  for f in range(FAMILIES)]))
+    hq = H.Queries.uniform(sym.reshape(nq, m)[sel].ravel(), m)
+    host = world["host"]
+    if host.sti1 is None:
+        host.sti1 = H.sti1_from_tables(host.suf, host.lcp, host.prefixlength)
+    yield dict(sym=sym, packed=packed, byte=byte, nq=nq, m=m, sel=sel, hq=hq)
+    packed.close()
+    byte.close()
+
+
+def rows_of(lst, sel):
+    """the rows of the reads sel (sorted) of a per-read list, renumbered"""
+    keep = np.isin(lst["queryseq"], sel.astype(np.uint64))
+    out = lst[keep].copy()
+    out["queryseq"] = np.searchsorted(sel, out["queryseq"].astype(np.int64))
+    return out
+
+
+MIXED_MODES = [("complete", None, None), ("mem", {}, 0), ("mem", {}, 2),
+               ("cand", dict(mum=True, cand=True), 2)]
+
+
+def test_mixed_batch_sample_equals_oracle_and_packed_equals_bytes(V, world,
+                                                                  mixed):
+    """-complete, -l 20 (both algorithms) and -mum cand on the whole batch;
+    the rows of the sampled reads == the oracle's lists for them (these lists
+    are per read), and the packed batch == the byte batch, whole lists"""
+    ix, host = world["index"], world["host"]
+    for name, kw, sp in MIXED_MODES:
+        if name == "complete":
+            got = V.findcompletematches(ix, mixed["packed"]).fetch()
+            other = V.findcompletematches(ix, mixed["byte"]).fetch()
+            want = H.oracle_complete(host, mixed["hq"])
+        else:
+            got = V.findquerymatches(ix, mixed["packed"], L, speedup=sp,
+                                     **kw).fetch()
+            other = V.findquerymatches(ix, mixed["byte"], L, speedup=sp,
+                                       **kw).fetch()
+            want = H.oracle_querymatches(host, mixed["hq"], L, speedup=sp,
+                                         **kw)
+        assert np.array_equal(got, other), (name, sp)
+        sample = rows_of(got, mixed["sel"])
+        assert len(sample) > 0
+        assert np.array_equal(sample, want), (name, sp)
+        # every family left something in the sample (wildcards and unrelated
+        # reads included)
+        fams = set((mixed["sel"][sample["queryseq"].astype(np.int64)]
+                    % FAMILIES).tolist())
+        # (no complete match can hold a wildcard or come from elsewhere)
+        assert fams >= ({0, 1} if name == "complete" else {0, 1, 2, 3}), \
+            (name, fams)
+
+
+def test_mixed_batch_global_mum_filter_and_the_bench_chain(V, world, mixed):
+    """-mum over the whole batch == the reference's filter (CPU oracle) over
+    all GPU candidates; packed == bytes; and the chain bench.py times
+    (findmumcandidates_packed -> one range -> mumuniqueinquery_range_packed2)
+    == findquerymatches(mum=True)"""
+    import ctypes as C
+    ix = world["index"]
+    cand = V.findquerymatches(ix, mixed["packed"], L, mum=True,
+                              cand=True).fetch()
+    mums = V.findquerymatches(ix, mixed["packed"], L, mum=True).fetch()
+    assert np.array_equal(
+        mums, V.findquerymatches(ix, mixed["byte"], L, mum=True).fetch())
+    out = H.OrcMatches()
+    lib = H.oracle_lib()
+    lib.orc_matches_init(C.byref(out))
+    c2 = np.ascontiguousarray(cand.copy())
+    lib.orc_mumuniqueinquery(c2.ctypes.data, len(c2), C.byref(out))
+    assert np.array_equal(mums, H._take(out))
+    del c2
+    r = V.findmumcandidates_packed(ix, mixed["packed"], L)
+    used = r.packbits
+    assert used > 0 and r.count == len(cand)
+    dp = V.device_malloc(r.count * 16 + 64)
+    try:
+        counts, top = r.partition(1, N, dp, own=0)
+        assert int(counts[0]) == r.count
+        res = V.mumuniqueinquery_range_packed2(
+            dp, r.count, C.c_void_p(dp.value + 16 * r.count), 0, used, N, 0)
+        st = res.stats()
+        assert st.count == len(mums)
+        assert st.sumlength == int(mums["length"].sum())
+        assert np.array_equal(H.sorted_matches(res.fetch()),
+                              H.sorted_matches(mums))
+    finally:
+        V.device_free(dp)
+
+
+def test_mixed_batch_plan_skips_aligned_reads(V, world, mixed):
+    """family (a) alone: the work plan leaves out more than nine offsets in
+    ten; (b) and (c) alone, whose reads exhaust the plan's rounds and ranges,
+    still give the oracle's candidates"""
+    ix, host, m = world["index"], world["host"], mixed["m"]
+    nq = mixed["nq"]
+    blocks = mixed["sym"].reshape(nq, m)
+    a = np.ascontiguousarray(blocks[0::FAMILIES]).ravel()
+    qa = V.Queries.from_host_packed(a, m)
+    r = V.findquerymatches(ix, qa, L, mum=True, cand=True)
+    assert r.stats().kernel_searches < qa.nq * (m - L + 1) // 10
+    qa.close()
+    for f in (1, 2):
+        part = np.ascontiguousarray(blocks[f::FAMILIES][:3000]).ravel()
+        hq = H.Queries.uniform(part, m)
+        for form in (V.Queries.from_host_packed(part, m),
+                     V.Queries.from_host(part, hq.start, hq.length)):
+            for kw, sp in ((dict(mum=True, cand=True), 2), ({}, 0)):
+                got = V.findquerymatches(ix, form, L, speedup=sp,
+                                         **kw).fetch()
+                assert np.array_equal(got, H.oracle_querymatches(
+                    host, hq, L, speedup=sp, **kw)), (f, kw)
+
+
+# ---------------------------------------------------------------------------
 # BASELINE.json configs[1]: 200 Mbp index, 1 M x 100 bp, -complete -- small
 # enough for the CPU oracle to answer EVERY query: the whole list, in order.
 # ---------------------------------------------------------------------------

@@ -155,3 +155,185 @@ def test_packed_reads_of_a_multiseq_with_separators(V):
                                             V._ptr(special), ns, 0,
                                             H.C.byref(h))
     assert rc == -2 and "side list" in V.messagespace()
+
+
+# ---------------------------------------------------------------------------
+# The MEM work plan (mem_workplan.inc) on batches built to exhaust it: the
+# -l L counterpart of test_gpu_parity.py::test_mum_work_plan_on_hard_batches
+# ---------------------------------------------------------------------------
+
+def mem_hard_text(rng):
+    """three sequences of random DNA with a family of 500-symbol units planted
+    eight times each with 0..3 substitutions (stretches whose rep bits are
+    set), one 700-symbol stretch planted twice exactly (matches of 255 symbols
+    and more, which the plan cannot locate), wildcards -> (tis, unit starts,
+    long-repeat start)"""
+    unit = rng.integers(0, 4, 500).astype(np.uint8)
+    long = rng.integers(0, 4, 700).astype(np.uint8)
+    seqs, units = [], []
+    off = 0
+    for s in range(3):
+        t = rng.integers(0, 4, 30000).astype(np.uint8)
+        for r in range(8):
+            p = 3600 * r + int(rng.integers(0, 3000))
+            u = unit.copy()
+            for e in range(int(rng.integers(0, 4))):
+                u[int(rng.integers(0, len(u)))] = rng.integers(0, 4)
+            t[p:p + len(u)] = u
+            units.append(off + p)
+        if s != 1:
+            t[29000 - len(long):29000] = long
+        t[rng.random(30000) < 0.0005] = H.WILDCARD
+        seqs.append(t)
+        off += 30001
+    tis = np.concatenate([np.concatenate([s, [H.SEPARATOR]])
+                          for s in seqs])[:-1].astype(np.uint8)
+    return tis, np.array(units), 29000 - len(long)
+
+
+def mem_hard_reads(rng, tis, units, longstart, lengths, D):
+    """one read per entry of lengths, ten families: 7..12 substitutions (four
+    of ten), exact copies, cut from a planted unit, cut from the long repeat,
+    random, a deletion and an insertion, wildcards at offset 0, D - 1, inside
+    the key window D .. D + 9 and at random"""
+    reads = []
+    for i, m in enumerate(lengths):
+        m = int(m)
+        kind = i % 10
+        if kind == 5:
+            p = int(units[i // 10 % len(units)]) + int(rng.integers(0, 100))
+        elif kind == 6:
+            p = longstart + int(rng.integers(0, 60))
+        else:
+            p = int(rng.integers(0, len(tis) - m - 2))
+        q = tis[p:p + m + 1].copy()
+        q[q == H.SEPARATOR] = rng.integers(0, 4)   # read across a boundary
+        if kind < 4:
+            for x in rng.choice(m, min(m, int(rng.integers(7, 13))),
+                                replace=False):
+                q[x] = (q[x] + 1 + rng.integers(0, 3)) % 4 if q[x] < 4 else 1
+        elif kind == 7:
+            q = rng.integers(0, 4, m + 1).astype(np.uint8)
+        elif kind == 8 and m > 4:
+            x, y = sorted(rng.choice(m - 1, 2, replace=False))
+            q = np.concatenate([q[:x], q[x + 1:y], [rng.integers(0, 4)],
+                                q[y:]]).astype(np.uint8)
+        elif kind == 9 and m > 0:
+            pos = [0, D - 1, D + int(rng.integers(0, 10)),
+                   int(rng.integers(0, m))][i // 10 % 4]
+            q[min(pos, m - 1)] = H.WILDCARD
+            if i % 3 == 0:
+                q[int(rng.integers(0, m))] = H.WILDCARD
+        reads.append(q[:m])
+    return reads
+
+
+# (name, read length or None for ragged lengths, packed): every first-pass
+# variant esa_search.hip picks for the MEM plan -- dense bytes staged in LDS
+# (m <= 128, m % 4 == 0), unstaged bytes (m % 4 != 0, m > 128), ragged bytes,
+# rows of up to four words, rows of five to eight words
+MEM_VARIANTS = [("staged100", 100, False), ("odd102", 102, False),
+                ("long300", 300, False), ("ragged", None, False),
+                ("rows100", 100, True), ("rows150", 150, True),
+                ("rows252", 252, True)]
+
+
+@pytest.mark.parametrize("name,m,packed", MEM_VARIANTS,
+                         ids=[v[0] for v in MEM_VARIANTS])
+def test_mem_work_plan_on_hard_batches(V, name, m, packed, monkeypatch):
+    """-l L on reads with 7..12 mismatches (the plan's rounds and ranges run
+    out), repeats whose rep bits are set, matches of 255 symbols and more,
+    wildcards where the deep locate must step aside; both -qspeedup
+    algorithms against the oracle in order, and against the unplanned run
+    (VSA_TUNE=2) of the same index.  L = 255 is the last search length with
+    a plan, 256 the first without."""
+    seed = [v[0] for v in MEM_VARIANTS].index(name)
+    rng = np.random.default_rng(9100 + seed)
+    tis, units, longstart = mem_hard_text(rng)
+    idx = H.oracle_build_index(tis, 4)
+    idx.sti1 = H.sti1_from_tables(idx.suf, idx.lcp, idx.prefixlength)
+    gi = gpu_index(V, idx, 32)
+    D = gi.info().deepprefix
+    assert D >= idx.prefixlength and D > 0
+    monkeypatch.setenv("VSA_TUNE", "2")
+    plain = gpu_index(V, idx, 32)
+    monkeypatch.delenv("VSA_TUNE")
+    nq = 2000
+    lengths = (rng.integers(0, 400, nq) if m is None else np.full(nq, m))
+    if m is None:
+        lengths[17] = 0
+    reads = mem_hard_reads(rng, tis, units, longstart, lengths, D)
+    # (uniform reads lie back to back: the dense batch the staged first pass
+    # wants)
+    hq = (H.Queries.from_list(reads) if m is None else
+          H.Queries.uniform(np.concatenate(reads), m))
+    if packed:
+        gq = V.Queries.from_host_packed(hq.symbols, m)
+        assert gq.nq == nq
+    else:
+        gq = V.Queries.from_host(hq.symbols, hq.start, hq.length)
+    Ls = [D, 20, 31]
+    if int(lengths.max()) >= 256:
+        Ls += [255, 256]
+    for L in Ls:
+        full = int(np.maximum(hq.length.astype(np.int64) - L + 1, 0).sum())
+        for sp in (0, 2):
+            r = V.findquerymatches(gi, gq, L, speedup=sp)
+            got = r.fetch()
+            want = H.oracle_querymatches(idx, hq, L, speedup=sp)
+            assert np.array_equal(got, want), (name, L, sp)
+            u = V.findquerymatches(plain, gq, L, speedup=sp)
+            assert np.array_equal(u.fetch(), want), (name, L, sp)
+            assert u.stats().kernel_searches == full
+            assert r.stats().kernel_searches <= full
+        if L == 20:
+            assert len(want) > nq // 2
+            assert (want["length"] >= 255).any() == (m is None or m >= 255)
+
+
+def test_mem_rep_bits_follow_the_search_length(V):
+    """the rep-bit table is kept per (index, L) (index->repleast): changing L
+    on one index, back and forth and through -mum, must rebuild it"""
+    rng = np.random.default_rng(9200)
+    tis, units, longstart = mem_hard_text(rng)
+    idx = H.oracle_build_index(tis, 4)
+    gi = gpu_index(V, idx, 32)
+    m, nq = 100, 2000
+    reads = mem_hard_reads(rng, tis, units, longstart, np.full(nq, m),
+                           gi.info().deepprefix)
+    hq = H.Queries.uniform(np.concatenate(reads), m)
+    gq = V.Queries.from_host(hq.symbols, hq.start, hq.length)
+    for L, kw in ((20, {}), (25, {}), (20, {}), (20, dict(mum=True)),
+                  (20, {}), (21, {})):
+        got = V.findquerymatches(gi, gq, L, speedup=0, **kw).fetch()
+        assert np.array_equal(got, H.oracle_querymatches(idx, hq, L,
+                                                         speedup=0, **kw)), \
+            (L, kw)
+
+
+def test_empty_packed_batch(V):
+    """Queries.from_host_packed of no reads: every entry point answers with
+    an empty list (the bytes of an empty packed batch were sized by a
+    division by its read length, 0)"""
+    idx, q = H.load_case("c1")
+    gi = gpu_index(V, idx, 32)
+    for m in (100, 150):
+        empty = V.Queries.from_host_packed(np.zeros(0, np.uint8), m)
+        assert empty.nq == 0 and empty.info().numofqueries == 0
+        assert V.findcompletematches(gi, empty).count == 0
+        for kw in (dict(speedup=0), dict(speedup=2), dict(mum=True),
+                   dict(mum=True, cand=True)):
+            assert V.findquerymatches(gi, empty, 20, **kw).count == 0, kw
+        assert V.findapproxcompletematches(gi, empty, True, 2).count == 0
+        assert V.findapproxcompletematches(gi, empty, False, 1).count == 0
+        rc = empty.reverse_complement()
+        assert rc.info().numofqueries == 0
+        assert V.findcompletematches(gi, rc).count == 0
+        assert V.findquerymatches(gi, rc, 20).count == 0
+        assert V.findmumcandidates_packed(gi, empty, 20).count == 0
+        assert V.findmumcandidates_packed(gi, empty, 20, 8).count == 0
+        # and the index still answers a real batch afterwards
+        got = V.findcompletematches(gi, V.Queries.from_host_packed(
+            q.symbols, int(q.length[0]))).fetch()
+        assert np.array_equal(H.matches_as_ref(idx, got),
+                              H.expected("c1", "complete"))

@@ -562,15 +562,10 @@ def test_empty_results_leave_no_error_behind(V):
     assert V.findsupermaximalrepeats(tiny, 1).count == 0
 
 
-@pytest.mark.parametrize("seed", range(7))
-def test_mum_work_plan_on_hard_batches(V, seed):
-    """the first pass + work plan (offsets that cannot be candidates are not
-    searched) on batches built to stress it: repetitive text (non-unique
-    longest matches), reads with 0..6 substitutions at random and at chosen
-    positions (first and last symbols, just inside and outside the last l
-    symbols), wildcards in reads and text, reads that run into a sequence
-    boundary, random reads; -mum cand and -mum against the oracle, in
-    order"""
+def mum_hard_batch(seed):
+    """text and reads of test_mum_work_plan_on_hard_batches -> (tis, reads
+    as one block, m, L, nq); also the texts of the forced deep prefixes
+    (tests/test_gpu_deep_prefix.py)"""
     rng = np.random.default_rng(4000 + seed)
     m = [100, 60, 150, 100, 254, 33, 300][seed]
     L = [20, 12, 31, 14, 40, 16, 25][seed]
@@ -607,6 +602,19 @@ def test_mum_work_plan_on_hard_batches(V, seed):
         if i % 97 == 0:
             q[int(rng.integers(0, m))] = H.WILDCARD
         qb[i * m:(i + 1) * m] = q
+    return tis, qb, m, L, nq
+
+
+@pytest.mark.parametrize("seed", range(7))
+def test_mum_work_plan_on_hard_batches(V, seed):
+    """the first pass + work plan (offsets that cannot be candidates are not
+    searched) on batches built to stress it: repetitive text (non-unique
+    longest matches), reads with 0..6 substitutions at random and at chosen
+    positions (first and last symbols, just inside and outside the last l
+    symbols), wildcards in reads and text, reads that run into a sequence
+    boundary, random reads; -mum cand and -mum against the oracle, in
+    order"""
+    tis, qb, m, L, nq = mum_hard_batch(seed)
     gi = V.Index.build(tis, 4, 0)
     t = gi.download()
     host = H.Index(len(tis), gi.info().prefixlength, 4, t["tis"], t["suf"],

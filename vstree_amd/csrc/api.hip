@@ -1152,7 +1152,9 @@ int vsa_queries_bytes(const vsa_queries *cq, hipStream_t stream)
                          stream));
   if (q->start == nullptr)
   {
-    const uint64_t most = std::max<uint64_t>(q->nq, q->bytescapacity / m);
+    // (an empty batch has m = 0: room for the one start entry only)
+    const uint64_t most =
+        std::max<uint64_t>(q->nq, m > 0 ? q->bytescapacity / m : 0);
     VSA_HIP(vsa_hip_malloc((void **) &q->start, (most + 1) * 8));
     VSA_HIP(vsa_hip_malloc((void **) &q->length, (most + 1) * 8));
   }
