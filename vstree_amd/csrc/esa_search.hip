@@ -31,19 +31,24 @@
 //
 // rocPRIM supplies radix sort / scan / reduce only.
 //
+// Host side: run_complete (K1), and run_query (K2 with its plans, K4) as
+// stages over one QueryRun -- work-items, decisions, the MEM or the MUM plan,
+// the search, compaction, the result.  pickform() picks the form of every
+// search launch (Form: reference walk, deep, staged, rows, windows) and
+// withform() turns it into template arguments; RecordForm is how matches
+// travel; query_entry() is what the four C entries share.
+//
 // Switches (environment, read when an index is created):
-//   VSA_TUNE=2        no MUM work reduction: every offset of every read is
+//   VSA_TUNE=2        no work reduction: every offset of every read is
 //                     searched by the list form of the search kernel (the
 //                     cross-check of first pass + work plan)
 //   VSA_NO_ESA8=1     no deep tables: the reference walk, probe for probe
 //   VSA_DEEP_PREFIX=D their depth (default ceil(log4 n), at most 16)
 //   VSA_FORCE_WIDE=1  64-bit device tables whatever the size of the text
-// What was measured and dropped (32-byte slots, the two-phase and the deferring
-// search kernel, the anchor pass, the list form of planned batches, the filter
-// on rocPRIM scans, ...) is described in DESIGN.md section 4 with its numbers
-// under profiles/; the code left with round 4.
+// What was measured and dropped is described in DESIGN.md section 4.
 #include "search_host.hpp"
 #include <rocprim/rocprim.hpp>
+#include <type_traits>
 
 #include "search_complete.inc"
 #include "search_query.inc"
@@ -58,6 +63,106 @@
 namespace
 {
 
+// ---- launch forms ----
+
+// How a search launch reads its queries and the index: the template
+// arguments <DEEP, PQ, ROWS, WINDOWS> of k_complete_search and k_mum_first
+enum class Form
+{
+  Ref,    // the reference walk: no deep tables
+  Deep,   // deep tables, queries as bytes
+  Staged, // deep tables, reads of one length m (a multiple of 4, <= 128)
+          // back to back, staged through LDS and packed
+  Rows,   // deep tables, packed rows of up to four words whole in registers
+  Windows // deep tables, rows of up to eight words through windows of the row
+};
+
+// the launches a form is picked for
+enum class Stage
+{
+  Complete, // k_complete_search
+  MemFirst, // k_mum_first in front of the MEM plan
+  MumFirst, // k_mum_first in front of the MUM plan (and the plan and the
+            // planned search behind it)
+  Bytes     // the MEM plan's search and every search without a plan
+};
+
+Form pickform(const vsa_index *index, const vsa_queries *queries,
+              const DevQueries &qs, Stage stage, uint32_t searchlength)
+{
+  // (-complete: a query shorter than D takes the walk of the deep kernel;
+  // everywhere else the deep prefix has to fit into every search)
+  const bool deep = index->esa8 != nullptr &&
+                    (stage == Stage::Complete || searchlength >= index->D);
+  bool rows = queries->rows != nullptr && queries->roww <= 8;
+  bool staged = qs.dense != 0 && qs.uniformlen <= 128 &&
+                (qs.uniformlen & 3u) == 0;
+  switch (stage)
+  {
+  case Stage::Complete:
+    // the row and the staged kernel locate D symbols of every read (staging
+    // copies the bytes into LDS)
+    rows = rows && queries->maxlength >= index->D;
+    staged = staged && qs.symbols != nullptr && qs.uniformlen >= index->D;
+    break;
+  case Stage::MemFirst: // rows, though the MEM search behind it reads bytes
+  case Stage::MumFirst: // (asked for only under the MUM work reduction)
+    break;
+  case Stage::Bytes: // bytes, made from the rows by vsa_queries_bytes
+    rows = staged = false;
+    break;
+  }
+  if (!deep)
+  {
+    return Form::Ref;
+  }
+  if (rows)
+  {
+    return queries->roww > 4 ? Form::Windows : Form::Rows;
+  }
+  return staged ? Form::Staged : Form::Deep;
+}
+
+// fn(DEEP, PQ, ROWS, WINDOWS) with std::integral_constant<bool> arguments
+template <typename Fn>
+void withform(Form form, Fn &&fn)
+{
+  using T = std::true_type;
+  using F = std::false_type;
+  switch (form)
+  {
+  case Form::Ref:
+    return fn(F(), F(), F(), F());
+  case Form::Deep:
+    return fn(T(), F(), F(), F());
+  case Form::Staged:
+    return fn(T(), T(), F(), F());
+  case Form::Rows:
+    return fn(T(), T(), T(), F());
+  case Form::Windows:
+    return fn(T(), T(), T(), T());
+  }
+}
+
+// dynamic LDS of a launch: the staged reads of a workgroup
+size_t ldsbytes(Form form, const DevQueries &qs)
+{
+  return form == Form::Staged ? (size_t) VSA_BLOCK * qs.uniformlen : 0;
+}
+
+// A rocPRIM algorithm, called the rocPRIM way: once for the size of its
+// scratch space, which temp then holds, once to do the work.
+template <typename Algo>
+hipError_t rocprim_run(DevBuf &temp, Algo algo)
+{
+  size_t bytes = 0;
+  hipError_t e = algo(nullptr, bytes);
+  if (e == hipSuccess && temp.alloc(bytes) != 0)
+  {
+    e = hipErrorOutOfMemory;
+  }
+  return e == hipSuccess ? algo(temp.p, bytes) : e;
+}
 
 // ---- K1 pipeline ----
 
@@ -72,14 +177,15 @@ int run_complete(const vsa_index *index, const vsa_queries *queries,
   // packed batches: read from their rows by the deep kernel (whole in
   // registers up to four words, through windows up to eight); an index
   // without deep tables, or longer reads, takes their bytes
-  const bool rows = queries->rows != nullptr && ix.esa8 != nullptr &&
-                    queries->roww <= 8 && queries->maxlength >= ix.D;
-  if (queries->rows != nullptr && !rows &&
+  if (queries->rows != nullptr &&
+      pickform(index, queries, devqueries(queries), Stage::Complete, 0) <
+          Form::Rows &&
       vsa_queries_bytes(queries, stream) != 0)
   {
     return -100;
   }
   const DevQueries qs = devqueries(queries);
+  const Form form = pickform(index, queries, qs, Stage::Complete, 0);
   DevBuf left, count, offsets, temp, matches;
   uint64_t total = 0;
 
@@ -96,52 +202,19 @@ int run_complete(const vsa_index *index, const vsa_queries *queries,
   tall.start();
   VSA_HIP(hipMemsetAsync(count.as<uint64_t>() + qlimit, 0, 8, stream));
   tsearch.start();
-  {
-    const bool staged = ix.esa8 != nullptr && qs.dense != 0 &&
-                        qs.symbols != nullptr && qs.uniformlen <= 128 &&
-                        (qs.uniformlen & 3u) == 0 && qs.uniformlen >= ix.D;
-    if (rows && queries->roww > 4)
-    {
-      k_complete_search<IDX, true, true, true, true>
-          <<<gridfor(qlimit), VSA_BLOCK, 0, stream>>>(
-              ix, qs, qlimit, left.as<uint64_t>(), count.as<uint64_t>());
-    } else if (rows)
-    {
-      k_complete_search<IDX, true, true, true>
-          <<<gridfor(qlimit), VSA_BLOCK, 0, stream>>>(
-              ix, qs, qlimit, left.as<uint64_t>(), count.as<uint64_t>());
-    } else if (staged)
-    {
-      k_complete_search<IDX, true, true>
-          <<<gridfor(qlimit), VSA_BLOCK, (size_t) VSA_BLOCK * qs.uniformlen,
-             stream>>>(ix, qs, qlimit, left.as<uint64_t>(),
-                       count.as<uint64_t>());
-    } else if (ix.esa8 != nullptr)
-    {
-      k_complete_search<IDX, true><<<gridfor(qlimit), VSA_BLOCK, 0, stream>>>(
-          ix, qs, qlimit, left.as<uint64_t>(), count.as<uint64_t>());
-    } else
-    {
-      k_complete_search<IDX, false>
-          <<<gridfor(qlimit), VSA_BLOCK, 0, stream>>>(
-              ix, qs, qlimit, left.as<uint64_t>(), count.as<uint64_t>());
-    }
-  }
+  withform(form, [&](auto deep, auto pq, auto rows, auto windows) {
+    k_complete_search<IDX, deep, pq, rows, windows>
+        <<<gridfor(qlimit), VSA_BLOCK, ldsbytes(form, qs), stream>>>(
+            ix, qs, qlimit, left.as<uint64_t>(), count.as<uint64_t>());
+  });
   tsearch.stop();
   VSA_HIP(hipGetLastError());
-  size_t tb = 0;
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, count.as<uint64_t>(),
-                                  offsets.as<uint64_t>(), (uint64_t) 0,
-                                  (size_t) (qlimit + 1),
-                                  rocprim::plus<uint64_t>(), stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, count.as<uint64_t>(),
-                                  offsets.as<uint64_t>(), (uint64_t) 0,
-                                  (size_t) (qlimit + 1),
-                                  rocprim::plus<uint64_t>(), stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, count.as<uint64_t>(),
+                                   offsets.as<uint64_t>(), (uint64_t) 0,
+                                   (size_t) (qlimit + 1),
+                                   rocprim::plus<uint64_t>(), stream);
+  }));
   VSA_HIP(hipMemcpyAsync(&total, offsets.as<uint64_t>() + qlimit, 8,
                          hipMemcpyDeviceToHost, stream));
   VSA_HIP(hipStreamSynchronize(stream));
@@ -253,19 +326,14 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
   mx.len = lenbound;
   if (dbbound == 0 || lenbound == 0)
   {
-    size_t tb = 0;
     auto in = rocprim::make_transform_iterator(cand.as<vsa_match>(),
                                                MaxPairOf());
     MaxPair init;
     init.db = init.len = 0;
-    VSA_HIP(rocprim::reduce(nullptr, tb, in, dcount.as<MaxPair>(), init,
-                            (size_t) ncand, MaxPairOp(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::reduce(temp.p, tb, in, dcount.as<MaxPair>(), init,
-                            (size_t) ncand, MaxPairOp(), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::reduce(p, tb, in, dcount.as<MaxPair>(), init,
+                             (size_t) ncand, MaxPairOp(), stream);
+    }));
     VSA_HIP(hipMemcpyAsync(&mx, dcount.p, sizeof mx, hipMemcpyDeviceToHost,
                            stream));
     VSA_HIP(hipStreamSynchronize(stream));
@@ -285,17 +353,12 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
         cand.as<vsa_match>(), ncand, lenbits, k1.as<uint64_t>(),
         i1.as<uint32_t>());
     VSA_HIP(hipGetLastError());
-    size_t tb = 0;
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, k1.as<uint64_t>(), k2.as<uint64_t>(), i1.as<uint32_t>(),
-        i2.as<uint32_t>(), (size_t) ncand, 0u, lenbits + dbbits, stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, k1.as<uint64_t>(), k2.as<uint64_t>(), i1.as<uint32_t>(),
-        i2.as<uint32_t>(), (size_t) ncand, 0u, lenbits + dbbits, stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(p, tb, k1.as<uint64_t>(),
+                                       k2.as<uint64_t>(), i1.as<uint32_t>(),
+                                       i2.as<uint32_t>(), (size_t) ncand, 0u,
+                                       lenbits + dbbits, stream);
+    }));
     k_mum_keyends<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
         k2.as<uint64_t>(), ncand, lenbits, ends.as<uint64_t>());
     VSA_HIP(hipGetLastError());
@@ -333,19 +396,12 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
         sorted.as<vsa_match>(), ncand, ends.as<uint64_t>());
     VSA_HIP(hipGetLastError());
   }
-  size_t tb = 0;
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, ends.as<uint64_t>(),
-                                  dbright.as<uint64_t>(), carry,
-                                  (size_t) ncand, rocprim::maximum<uint64_t>(),
-                                  stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, ends.as<uint64_t>(),
-                                  dbright.as<uint64_t>(), carry,
-                                  (size_t) ncand, rocprim::maximum<uint64_t>(),
-                                  stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, ends.as<uint64_t>(),
+                                   dbright.as<uint64_t>(), carry,
+                                   (size_t) ncand, rocprim::maximum<uint64_t>(),
+                                   stream);
+  }));
   if (maxright != nullptr)
   {
     // sorted by dbstart, so the running maximum behind the last element
@@ -375,17 +431,11 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
     VSA_HIP(hipGetLastError());
     auto keepit =
         rocprim::make_transform_iterator(keep.as<uint8_t>(), KeepToU32());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, keepit, slots.as<uint32_t>(),
-                                    (uint32_t) 0, (size_t) ncand,
-                                    rocprim::plus<uint32_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, keepit, slots.as<uint32_t>(),
-                                    (uint32_t) 0, (size_t) ncand,
-                                    rocprim::plus<uint32_t>(), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::exclusive_scan(p, tb, keepit, slots.as<uint32_t>(),
+                                     (uint32_t) 0, (size_t) ncand,
+                                     rocprim::plus<uint32_t>(), stream);
+    }));
     DevBuf blocksum;
     const size_t nblocks = blocksfor(ncand);
     if (blocksum.alloc(vsa_grid_blocks(nblocks) * 8))
@@ -397,19 +447,11 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
         slots.as<uint32_t>(), ncand, mums.as<vsa_match>(),
         dcount.as<uint64_t>(), blocksum.as<unsigned long long>());
     VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::reduce(nullptr, tb, blocksum.as<unsigned long long>(),
-                            dcount.as<unsigned long long>() + 1, 0ull,
-                            nblocks, rocprim::plus<unsigned long long>(),
-                            stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::reduce(temp.p, tb, blocksum.as<unsigned long long>(),
-                            dcount.as<unsigned long long>() + 1, 0ull,
-                            nblocks, rocprim::plus<unsigned long long>(),
-                            stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::reduce(p, tb, blocksum.as<unsigned long long>(),
+                             dcount.as<unsigned long long>() + 1, 0ull, nblocks,
+                             rocprim::plus<unsigned long long>(), stream);
+    }));
     {
       const Fetch f[2] = {{dcount.p, 8}, {dcount.as<uint64_t>() + 1, 8}};
       uint64_t got[2];
@@ -485,24 +527,17 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
   // Sorted by dbstart alone where the runs of equal dbstarts are short (see
   // k_mumf_flags; decided afterwards from a flag that comes back with the
   // counts), by (dbstart, length down) otherwise.
-  size_t tb = 0;
   uint64_t got[3] = {0, 0, 0};
   for (int pass = 0; pass < 2; pass++)
   {
     const bool byruns = pass == 0;
     const unsigned int firstbit = byruns ? lenbits : 0u;
     VSA_HIP(hipMemsetAsync(dcount.p, 0, 24, stream));
-    tb = 0;
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, keys_in, k2.as<uint64_t>(), vals_in,
-        v2.as<VAL>(), (size_t) ncand, firstbit, lenbits + dbbits, stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, keys_in, k2.as<uint64_t>(), vals_in,
-        v2.as<VAL>(), (size_t) ncand, firstbit, lenbits + dbbits, stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(p, tb, keys_in, k2.as<uint64_t>(),
+                                       vals_in, v2.as<VAL>(), (size_t) ncand,
+                                       firstbit, lenbits + dbbits, stream);
+    }));
     if (byruns)
     {
       const dim3 tg = vsa_grid(ntiles);
@@ -546,51 +581,33 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
     // running maximum of the right ends, which are a function of the keys
     auto ends = rocprim::make_transform_iterator(k2.as<uint64_t>(),
                                                  KeyToRightEnd{lenbits});
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, ends, dbright.as<uint64_t>(),
-                                    carry, (size_t) ncand,
-                                    rocprim::maximum<uint64_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, ends, dbright.as<uint64_t>(),
-                                    carry, (size_t) ncand,
-                                    rocprim::maximum<uint64_t>(), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::exclusive_scan(p, tb, ends, dbright.as<uint64_t>(), carry,
+                                     (size_t) ncand,
+                                     rocprim::maximum<uint64_t>(), stream);
+    }));
     k_mum_keyflags<<<vsa_grid(nblocks), VSA_BLOCK, 0, stream>>>(
         k2.as<uint64_t>(), dbright.as<uint64_t>(), ncand, lenbits,
         keep.as<uint8_t>());
     VSA_HIP(hipGetLastError());
     auto keepit =
         rocprim::make_transform_iterator(keep.as<uint8_t>(), KeepToU32());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, keepit, slots.as<uint32_t>(),
-                                    (uint32_t) 0, (size_t) ncand,
-                                    rocprim::plus<uint32_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, keepit, slots.as<uint32_t>(),
-                                    (uint32_t) 0, (size_t) ncand,
-                                    rocprim::plus<uint32_t>(), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::exclusive_scan(p, tb, keepit, slots.as<uint32_t>(),
+                                     (uint32_t) 0, (size_t) ncand,
+                                     rocprim::plus<uint32_t>(), stream);
+    }));
     k_mum_writepacked<VAL><<<vsa_grid(nblocks), VSA_BLOCK, 0, stream>>>(
         k2.as<uint64_t>(), v2.as<VAL>(), keep.as<uint8_t>(),
         slots.as<uint32_t>(), ncand, lenbits, valbits, seqoffset,
         mums.as<vsa_match>(), dcount.as<uint64_t>(),
         blocksum.as<unsigned long long>());
     VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::reduce(nullptr, tb, blocksum.as<unsigned long long>(),
-                            dcount.as<unsigned long long>() + 1, 0ull, nblocks,
-                            rocprim::plus<unsigned long long>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::reduce(temp.p, tb, blocksum.as<unsigned long long>(),
-                            dcount.as<unsigned long long>() + 1, 0ull, nblocks,
-                            rocprim::plus<unsigned long long>(), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::reduce(p, tb, blocksum.as<unsigned long long>(),
+                             dcount.as<unsigned long long>() + 1, 0ull, nblocks,
+                             rocprim::plus<unsigned long long>(), stream);
+    }));
     const Fetch f[3] = {{dcount.p, 8}, {dcount.as<uint64_t>() + 1, 8},
                         {dcount.as<uint64_t>() + 2, 8}};
     if (fetchwords(stream, f, 3, got))
@@ -604,936 +621,735 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
   return 0;
 }
 
-template <typename IDX>
-int run_query(const vsa_index *index, const vsa_queries *queries, bool domum,
-              bool domumcand, uint32_t searchlength, vsa_result *res,
-              bool ordered = true, uint32_t forcebits = 0)
+// How the matches of a call travel from the search kernels to the result:
+// vsa_match records, or (MUM) 8-byte values queryseq << 16 | querystart
+// next to keys dbstart << lenbits | (2^lenbits - 1 - length), see
+// mumfilter_packed -- 4-byte values where query number and offset fit.
+struct RecordForm
 {
-  // forcebits != 0 (with domumcand, !ordered): the candidates stay pairs with
-  // this many length bits (vsa_findmumcandidates_packed)
-  hipStream_t stream = index->stream;
-  vsa_dev_set_stream(stream);
-  Timer tall(stream), tsearch(stream);
-  const DevIndex<IDX> ix = index->view<IDX>();
-  DevQueries qs = devqueries(queries);
-  DevBuf base, cursor, out, keys;
-  uint64_t nitems = 0;
-  uint32_t perquery = 0;
-  const uint64_t *dbase = nullptr;
+  bool keeppairs; // the result is the pairs (vsa_findmumcandidates_packed)
+  bool packed;
+  unsigned int lenbits, dbbits;
+  uint32_t packbits, valbits; // as the kernels take them (0: not this form)
+  size_t recsize;
+};
 
-  // work-items: one per query suffix with remaining >= searchlength
-  // (kurtz/matchsub.c:187-196: shorter queries are skipped silently)
-  if (qs.uniformlen != 0)
-  {
-    perquery = (qs.uniformlen >= searchlength)
-                   ? qs.uniformlen - searchlength + 1
-                   : 0;
-    nitems = (uint64_t) perquery * queries->nq;
-  } else
-  {
-    // base[q] = number of work-items in front of query q, from the lengths
-    // on the device (a host loop and an upload of 8 bytes per query cost
-    // more than the search for a batch of millions of reads)
-    const uint64_t nqr = queries->nq;
-    DevBuf btemp;
-    size_t tb = 0;
-    const uint64_t least = searchlength;
-    auto items = rocprim::make_transform_iterator(
-        rocprim::counting_iterator<uint64_t>(0),
-        [len = qs.length, nqr, least] __device__(uint64_t q) -> uint64_t {
-          if (q >= nqr)
-          {
-            return 0; // the entry behind the last query: the total
-          }
-          const uint64_t l = len[q];
-          return l >= least ? l - least + 1 : 0;
-        });
-    if (base.alloc((nqr + 1) * 8))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, items, base.as<uint64_t>(),
-                                    (uint64_t) 0, (size_t) (nqr + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    if (btemp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(btemp.p, tb, items, base.as<uint64_t>(),
-                                    (uint64_t) 0, (size_t) (nqr + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    {
-      const Fetch f = {base.as<uint64_t>() + nqr, 8};
-      if (fetchwords(stream, &f, 1, &nitems))
-      {
-        return -100;
-      }
-    }
-    dbase = base.as<uint64_t>();
-  }
-  res->stats.searches = nitems;
-  if (nitems == 0)
-  {
-    return 0;
-  }
-  const uint32_t nshards = VSA_CURSOR_SHARDS;
-  const bool deepok = ix.esa8 != nullptr && searchlength >= ix.D;
-  tall.start();
-  // MUM modes: first pass + work plan (mum_workplan.inc)
-  DevBuf wcount, wtemp, wplan, wlist, wfirste, wfmlen, wfmdb, wboffset;
-  uint64_t nfirstpass = 0; // candidates of the first pass (k_append_first)
-  // reads the first pass left to the plan (low half) | first-pass candidates
-  // (high half), on the device
-  const uint64_t *nlistword = nullptr;
-  uint64_t plansearches = 0, nfirst = 0, mumsum = ~0ull;
-  // -mum with the filter: candidates as (sort key, value) pairs, see
-  // mumfilter_packed
-  const bool keeppairs = domum && domumcand && !ordered && forcebits != 0;
-  const unsigned int lenbits =
-                         keeppairs ? forcebits : bitsfor(queries->maxlength),
-                     dbbits = bitsfor(index->n);
-  const bool packed = domum && (!domumcand || keeppairs) &&
-                      lenbits + dbbits <= 64 &&
-                      lenbits >= bitsfor(queries->maxlength) &&
-                      queries->maxlength < 0xFFFFu &&
-                      ((queries->nq + qs.seqoffset) >> 48) == 0;
-  if (keeppairs && !packed)
+// forcebits != 0 (with domumcand, !ordered): the candidates stay pairs with
+// this many length bits
+int recordform(const vsa_index *index, const vsa_queries *queries, bool domum,
+               bool domumcand, bool ordered, uint32_t forcebits,
+               RecordForm *rf)
+{
+  const unsigned int need = bitsfor(queries->maxlength);
+  rf->keeppairs = domum && domumcand && !ordered && forcebits != 0;
+  rf->lenbits = rf->keeppairs ? forcebits : need;
+  rf->dbbits = bitsfor(index->n);
+  rf->packed = domum && (!domumcand || rf->keeppairs) &&
+               rf->lenbits + rf->dbbits <= 64 && rf->lenbits >= need &&
+               queries->maxlength < 0xFFFFu &&
+               ((queries->nq + queries->seqoffset) >> 48) == 0;
+  if (rf->keeppairs && !rf->packed)
   {
     VSA_ERROR("packed candidates: %u length bits do not fit this batch "
               "(longest query %lu, index %lu)", forcebits,
               (unsigned long) queries->maxlength, (unsigned long) index->n);
     return -2;
   }
-  const uint32_t packbits = packed ? lenbits : 0;
-  // 4-byte values where query number and offset fit (not for pairs that
-  // travel to other ranks: those carry the global query number)
-  const uint32_t valbits =
-      (packed && !keeppairs && ((queries->nq << lenbits) >> 32) == 0)
-          ? lenbits
-          : 0;
-  const size_t recsize = valbits != 0 ? 4 : (packed ? 8 : sizeof(vsa_match));
+  rf->packbits = rf->packed ? rf->lenbits : 0;
+  // (not for pairs that travel to other ranks: those carry the global query
+  // number)
+  const bool small = ((queries->nq << rf->lenbits) >> 32) == 0;
+  rf->valbits = (rf->packed && !rf->keeppairs && small) ? rf->lenbits : 0;
+  rf->recsize = rf->valbits != 0 ? 4 : (rf->packed ? 8 : sizeof(vsa_match));
+  return 0;
+}
+
+// the filled part of every cursor region of raw / rawkeys (cap records
+// each) into out / keys from record `at` on
+int compact_into(const RecordForm &form, DevBuf &raw, DevBuf &rawkeys,
+                 uint64_t cap, DevBuf &cursors, DevBuf &doff, DevBuf &out,
+                 DevBuf &keys, uint64_t at, hipStream_t stream)
+{
+  auto launch = [&](auto rec) {
+    using REC = decltype(rec);
+    k_compact_shards<REC><<<VSA_CURSOR_SHARDS, VSA_BLOCK, 0, stream>>>(
+        raw.as<REC>(), rawkeys.as<uint64_t>(), cap,
+        cursors.as<unsigned long long>(), doff.as<uint64_t>(),
+        out.as<REC>() + at, keys.as<uint64_t>() + at);
+  };
+  if (form.valbits != 0)
+  {
+    launch(uint32_t());
+  } else if (form.packed)
+  {
+    launch(uint64_t());
+  } else
+  {
+    launch(vsa_match());
+  }
+  VSA_HIP(hipGetLastError());
+  return 0;
+}
+
+// what the stages of one run_query call share
+struct QueryRun
+{
+  const vsa_index *index;
+  const vsa_queries *queries;
+  hipStream_t stream;
+  DevQueries qs;
+  bool domum, domumcand, ordered;
+  uint32_t searchlength;
+  RecordForm rec;
+  Timer tall, tsearch, tfirst; // tfirst: the first pass kernel alone
+  // work-items: perquery per query, or (ragged batches) base[q] in front of
+  // query q (dbase)
+  DevBuf base;
+  const uint64_t *dbase = nullptr;
+  uint32_t perquery = 0;
+  uint64_t nitems = 0;
+  bool reduce = false, memplan = false;
+  // of the search kernel, and of the MUM first pass and plan
+  Form form = Form::Ref;
+  // first pass + work plan (mum_workplan.inc, mem_workplan.inc)
+  DevBuf wcount, wtemp, wplan, wlist, wfirste, wfmlen, wfmdb, wboffset;
+  // reads the first pass left to the plan (low half) | first-pass candidates
+  // (high half), on the device
+  const uint64_t *nlistword = nullptr;
+  // the cursor regions the plan answers into (PlanEmit), if it does
+  DevBuf pcursor, pdoff, psummary, prawout, prawkeys;
+  uint64_t pcap = 0;
   bool fromplan = false, planemit = false;
-  DevBuf pcursor, pdoff, psummary, prawout, prawkeys; // see PlanEmit
-  uint64_t pcap = 0, nplan = 0;
-  uint64_t nwork = nitems;
-  Timer tfirst(stream); // the first pass kernel (k_mum_first) alone
+  uint64_t plansearches = 0;
+  // the search kernel's cursor regions, and the dense list behind them
+  DevBuf cursor, doff, summary, blocksum, rtemp, rawout, rawkeys, out, keys;
+  uint64_t shardcap = 0, needed = 0, nplan = 0, nfirst = 0, plannedwork = 0;
+  double searchms = 0;
+
+  QueryRun(const vsa_index *ix, const vsa_queries *q, bool mum, bool cand,
+           bool ord, uint32_t least)
+      : index(ix), queries(q), stream(ix->stream), qs(devqueries(q)),
+        domum(mum), domumcand(cand), ordered(ord), searchlength(least),
+        tall(stream), tsearch(stream), tfirst(stream)
+  {
+  }
+};
+
+// work-items: one per query suffix with remaining >= searchlength
+// (kurtz/matchsub.c:187-196: shorter queries are skipped silently)
+// (IDX: one instance of the device lambda per offset width)
+template <typename IDX>
+int workitems(QueryRun &st)
+{
+  const uint64_t nqr = st.queries->nq, least = st.searchlength;
+  if (st.qs.uniformlen != 0)
+  {
+    st.perquery = (st.qs.uniformlen >= least) ? st.qs.uniformlen - least + 1
+                                              : 0;
+    st.nitems = (uint64_t) st.perquery * nqr;
+    return 0;
+  }
+  // base[q] = number of work-items in front of query q, from the lengths
+  // on the device (a host loop and an upload of 8 bytes per query cost
+  // more than the search for a batch of millions of reads)
+  DevBuf btemp;
+  auto items = rocprim::make_transform_iterator(
+      rocprim::counting_iterator<uint64_t>(0),
+      [len = st.qs.length, nqr, least] __device__(uint64_t q) -> uint64_t {
+        if (q >= nqr)
+        {
+          return 0; // the entry behind the last query: the total
+        }
+        const uint64_t l = len[q];
+        return l >= least ? l - least + 1 : 0;
+      });
+  if (st.base.alloc((nqr + 1) * 8))
+  {
+    return -100;
+  }
+  VSA_HIP(rocprim_run(btemp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, items, st.base.as<uint64_t>(),
+                                   (uint64_t) 0, (size_t) (nqr + 1),
+                                   rocprim::plus<uint64_t>(), st.stream);
+  }));
+  st.dbase = st.base.as<uint64_t>();
+  const Fetch f = {st.dbase + nqr, 8};
+  return fetchwords(st.stream, &f, 1, &st.nitems) ? -100 : 0;
+}
+
+// lcptab's quirk, the work reductions, the form of the search (and the
+// bytes of a packed batch that is not read from its rows)
+int decide(QueryRun &st)
+{
+  const vsa_index *index = st.index;
+  const vsa_queries *queries = st.queries;
   // ragged batches take the same route with per-query geometry
   const uint64_t maxoffsets =
-      (queries->maxlength >= searchlength)
-          ? queries->maxlength - searchlength + 1
+      (queries->maxlength >= st.searchlength)
+          ? queries->maxlength - st.searchlength + 1
           : 0;
-  if (domum && queries->maxlength >= 255 && index->lcpquirk < 0)
+  if (st.domum && queries->maxlength >= 255 && index->lcpquirk < 0)
   {
     uint8_t b = 0;
     if (index->n >= 2)
     {
       VSA_HIP(hipMemcpyAsync(&b, index->lcp + index->n - 1, 1,
-                             hipMemcpyDeviceToHost, stream));
-      VSA_HIP(hipStreamSynchronize(stream));
+                             hipMemcpyDeviceToHost, st.stream));
+      VSA_HIP(hipStreamSynchronize(st.stream));
     }
     index->lcpquirk = (b == 255) ? 1 : 0;
   }
-  // The work reduction (see k_mum_first, k_mum_plan) rests on "a match that
-  // is not unique is no candidate"; the reference's test for lcp >= 255
+  // VSA_TUNE=2: no work reduction (every offset is searched by the list form
+  // of the search kernel -- the cross-check of first pass and work plan)
+  const bool exhaustive = (index->tune & 2u) != 0;
+  const bool planable = maxoffsets > 1 && maxoffsets < 0xFFFFu &&
+                        queries->nq < 0xFFFFFFFFull && !exhaustive;
+  // The MUM work reduction (see k_mum_first, k_mum_plan) rests on "a match
+  // that is not unique is no candidate"; the reference's test for lcp >= 255
   // (fquery.c:352) breaks that rule in one situation, which one byte of
   // lcptab rules out (see vsa_index::lcpquirk).  A plan holds 16-bit offsets.
-  // VSA_TUNE=2: no work reduction (every offset is searched by the list form
-  // of the search kernel -- the cross-check of everything below).
-  const bool reduce = domum && maxoffsets > 1 && maxoffsets < 0xFFFFu &&
-                      queries->nq < 0xFFFFFFFFull && (index->tune & 2u) == 0 &&
-                      !(queries->maxlength >= 255 && index->lcpquirk != 0);
-  // packed batches (reads at two bits per symbol): first pass, plan and
-  // search kernel read the rows; everything else takes the bytes, which are
-  // made on the device once per batch
-  // (rows of up to four words -- reads of up to 124 symbols -- come into
-  // registers whole in the first pass; longer ones, 150 bp, are looked at
-  // through windows of their rows there as well)
-  const bool rows = queries->rows != nullptr && reduce && deepok &&
-                    queries->roww <= 8;
-  if (queries->rows != nullptr && !rows)
-  {
-    if (vsa_queries_bytes(queries, stream) != 0)
-    {
-      return -100;
-    }
-    qs = devqueries(queries);
-  }
+  st.reduce = st.domum && planable &&
+              !(queries->maxlength >= 255 && index->lcpquirk != 0);
   // MEM (-l L): first pass, then the plan of mem_workplan.inc -- aligned
   // stretches answered from one bit per text position, the rest searched
-  // (a packed batch has its bytes by now: MEM reads bytes)
-  const bool memplan = !domum && deepok && searchlength <= 255 &&
-                       maxoffsets > 1 &&
-                       maxoffsets < 0xFFFFu && queries->nq < 0xFFFFFFFFull &&
-                       (index->tune & 2u) == 0;
-  if (memplan)
+  st.memplan = !st.domum && planable && index->esa8 != nullptr &&
+               st.searchlength >= index->D && st.searchlength <= 255;
+  // packed batches (reads at two bits per symbol): MUM under the work
+  // reduction reads the rows in every kernel; everything else takes the
+  // bytes, which are made on the device once per batch
+  st.form = pickform(index, queries, st.qs,
+                     st.reduce ? Stage::MumFirst : Stage::Bytes,
+                     st.searchlength);
+  if (queries->rows != nullptr && st.form < Form::Rows)
   {
-    const uint64_t nq = queries->nq;
-    // one bit per text position: does its suffix have a neighbour in the
-    // suffix array with lcp >= L?  Made once per (index, L), kept.
-    if (index->repbits == nullptr || index->repleast != searchlength)
-    {
-      if (index->repbits == nullptr)
-      {
-        VSA_HIP(vsa_hip_malloc((void **) &index->repbits,
-                               ((index->n + 1) / 32 + 4) * 4));
-      }
-      VSA_HIP(hipMemsetAsync(index->repbits, 0, ((index->n + 1) / 32 + 4) * 4,
-                             stream));
-      k_repeat_bits<IDX><<<vsa_grid(blocksfor((index->n + 16) / 16)),
-                           VSA_BLOCK, 0, stream>>>(
-          ix.lcp, ix.suf, index->n, searchlength, index->repbits);
-      VSA_HIP(hipGetLastError());
-      index->repleast = searchlength;
-    }
-    if (wcount.alloc((nq + 1) * 4) || wfirste.alloc(nq * 4) ||
-        wfmlen.alloc(nq * 4) || wfmdb.alloc(nq * 8) ||
-        wplan.alloc(nq * sizeof(PlanRanges)))
+    if (vsa_queries_bytes(queries, st.stream) != 0)
     {
       return -100;
     }
-    tfirst.start();
-    {
-      const bool staged = qs.dense != 0 && qs.uniformlen <= 128 &&
-                          (qs.uniformlen & 3u) == 0;
-      if (queries->rows != nullptr && queries->roww <= 4)
-      {
-        // (a packed batch: offset 0 of every read from its row, as -mum does)
-        k_mum_first<IDX, true, true, true>
-            <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-                ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-                wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-                wfmdb.as<uint64_t>());
-      } else if (queries->rows != nullptr && queries->roww <= 8)
-      {
-        k_mum_first<IDX, true, true, true, true>
-            <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-                ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-                wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-                wfmdb.as<uint64_t>());
-      } else if (staged)
-      {
-        k_mum_first<IDX, true, true>
-            <<<gridfor(nq), VSA_BLOCK, (size_t) VSA_BLOCK * qs.uniformlen,
-               stream>>>(ix, qs, perquery, searchlength,
-                         wcount.as<uint32_t>(), wfirste.as<uint32_t>(),
-                         wfmlen.as<uint32_t>(), wfmdb.as<uint64_t>());
-      } else
-      {
-        k_mum_first<IDX, true><<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-            ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-            wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-            wfmdb.as<uint64_t>());
-      }
-    }
-    tfirst.stop();
-    VSA_HIP(hipGetLastError());
-    {
-      // room for every answer of the workgroups that share a region (a read
-      // answers at most one offset per round)
-      const uint64_t nb = blocksfor(nq),
-                     pershard = (nb + nshards - 1) / nshards;
-      pcap = pershard * VSA_BLOCK * VSA_PLAN_ROUNDS;
-      if (pcursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
-          pdoff.alloc(nshards * 8) || psummary.alloc(4 * 8) ||
-          prawout.alloc(nshards * pcap * recsize) ||
-          prawkeys.alloc(nshards * pcap * 8))
-      {
-        return -100;
-      }
-      VSA_HIP(hipMemsetAsync(pcursor.p, 0,
-                             (size_t) nshards * VSA_CURSOR_STRIDE * 8,
-                             stream));
-      PlanEmit em;
-      em.base = dbase;
-      em.perquery = perquery;
-      em.out = prawout.as<vsa_match>();
-      em.outkey = prawkeys.as<uint64_t>();
-      em.shardcap = pcap;
-      em.shardmask = nshards - 1;
-      em.cursors = pcursor.as<unsigned long long>();
-      em.packbits = 0;
-      em.valbits = 0;
-      k_mem_plan<IDX><<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-          ix, qs, perquery, searchlength, wfirste.as<uint32_t>(),
-          wfmdb.as<uint64_t>(), index->repbits, wcount.as<uint32_t>(),
-          wplan.as<PlanRanges>(), em);
-      VSA_HIP(hipGetLastError());
-      VSA_HIP(shard_summary(pcursor.as<unsigned long long>(), nshards,
-                            pdoff.as<uint64_t>(), psummary.as<uint64_t>(),
-                            stream));
-    }
-    planemit = true;
-    fromplan = true;
-    plansearches = nq; // (an upper bound of the plan's own locates per round)
+    st.qs = devqueries(queries);
   }
-  if (reduce)
+  return 0;
+}
+
+// k_mum_first over all reads, timed, behind the allocation of the buffers of
+// first pass and plan; blockcount: see k_mum_first
+template <typename IDX>
+int first_pass(QueryRun &st, const DevIndex<IDX> &ix, Form form,
+               uint64_t *blockcount)
+{
+  st.tfirst.start();
+  withform(form, [&](auto deep, auto pq, auto rows, auto windows) {
+    k_mum_first<IDX, deep, pq, rows, windows>
+        <<<gridfor(st.queries->nq), VSA_BLOCK, ldsbytes(form, st.qs),
+           st.stream>>>(ix, st.qs, st.perquery, st.searchlength,
+                        st.wcount.as<uint32_t>(), st.wfirste.as<uint32_t>(),
+                        st.wfmlen.as<uint32_t>(), st.wfmdb.as<uint64_t>(),
+                        blockcount);
+  });
+  st.tfirst.stop();
+  VSA_HIP(hipGetLastError());
+  return 0;
+}
+
+// the buffers of first pass and plan
+int alloc_first(QueryRun &st)
+{
+  const uint64_t nq = st.queries->nq;
+  return st.wcount.alloc((nq + 1) * 4) || st.wfirste.alloc(nq * 4) ||
+         st.wfmlen.alloc(nq * 4) || st.wfmdb.alloc(nq * 8) ||
+         st.wplan.alloc(nq * sizeof(PlanRanges));
+}
+
+// The cursor regions a plan kernel answers into, with room for `rounds`
+// answers per read of all the workgroups that share a region (no
+// overflow); cursors zeroed.
+int plan_emit(QueryRun &st, uint32_t rounds, PlanEmit *em)
+{
+  const uint32_t nshards = VSA_CURSOR_SHARDS;
+  const uint64_t nb = blocksfor(st.queries->nq),
+                 pershard = (nb + nshards - 1) / nshards;
+  st.pcap = pershard * VSA_BLOCK * rounds;
+  if (st.pcursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
+      st.pdoff.alloc(nshards * 8) || st.psummary.alloc(4 * 8) ||
+      st.prawout.alloc(nshards * st.pcap * st.rec.recsize) ||
+      st.prawkeys.alloc(nshards * st.pcap * 8))
   {
-    const uint64_t nq = queries->nq;
-    if (wcount.alloc((nq + 1) * 4) || wfirste.alloc(nq * 4) ||
-        wfmlen.alloc(nq * 4) || wfmdb.alloc(nq * 8) ||
-        wplan.alloc(nq * sizeof(PlanRanges)) || wlist.alloc(nq * 4))
-    {
-      return -100;
-    }
-    VSA_HIP(hipMemsetAsync(wcount.as<uint32_t>() + nq, 0, 4, stream));
-    // per workgroup of the first pass: reads it leaves to the plan | reads
-    // whose offset 0 is a candidate (counted by the first pass itself)
-    // (queries < 2^32: the condition of this branch)
-    const uint64_t nb = blocksfor(nq), nbr = vsa_grid_blocks(nb);
-    DevBuf bcount;
-    if (bcount.alloc((nbr + 1) * 8) || wboffset.alloc((nbr + 1) * 8))
-    {
-      return -100;
-    }
-    // (both halves of a count stay below 2^32: nq does)
-    VSA_HIP(hipMemsetAsync(bcount.as<uint64_t>() + nb, 0, 8, stream));
-    tfirst.start();
-    if (rows && queries->roww > 4)
-    {
-      k_mum_first<IDX, true, true, true, true>
-          <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-              ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-              wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-              wfmdb.as<uint64_t>(), bcount.as<uint64_t>());
-    } else if (rows)
-    {
-      k_mum_first<IDX, true, true, true>
-          <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-              ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-              wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-              wfmdb.as<uint64_t>(), bcount.as<uint64_t>());
-    } else if (deepok)
-    {
-      // reads of one length m (a multiple of 4, <= 128), back to back:
-      // staged through LDS and packed
-      const bool staged = qs.dense != 0 && qs.uniformlen <= 128 &&
-                          (qs.uniformlen & 3u) == 0;
-      if (staged)
-      {
-        k_mum_first<IDX, true, true>
-            <<<gridfor(nq), VSA_BLOCK, (size_t) VSA_BLOCK * qs.uniformlen,
-               stream>>>(ix, qs, perquery, searchlength,
-                         wcount.as<uint32_t>(), wfirste.as<uint32_t>(),
-                         wfmlen.as<uint32_t>(), wfmdb.as<uint64_t>(),
-                         bcount.as<uint64_t>());
-      } else
-      {
-        k_mum_first<IDX, true><<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-            ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-            wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-            wfmdb.as<uint64_t>(), bcount.as<uint64_t>());
-      }
-    } else
-    {
-      k_mum_first<IDX, false><<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-          ix, qs, perquery, searchlength, wcount.as<uint32_t>(),
-          wfirste.as<uint32_t>(), wfmlen.as<uint32_t>(),
-          wfmdb.as<uint64_t>(), bcount.as<uint64_t>());
-    }
-    tfirst.stop();
-    VSA_HIP(hipGetLastError());
-    // the reads the first pass has not finished, as a list (its counts per
-    // workgroup, a scan over the workgroups, an ordered fill); with it come
-    // the places of the first pass's candidates
-    size_t tb = 0;
-    {
-      VSA_HIP(rocprim::exclusive_scan(nullptr, tb, bcount.as<uint64_t>(),
-                                      wboffset.as<uint64_t>(), (uint64_t) 0,
-                                      (size_t) (nb + 1),
-                                      rocprim::plus<uint64_t>(), stream));
-      if (wtemp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::exclusive_scan(wtemp.p, tb, bcount.as<uint64_t>(),
-                                      wboffset.as<uint64_t>(), (uint64_t) 0,
-                                      (size_t) (nb + 1),
-                                      rocprim::plus<uint64_t>(), stream));
-      k_wanted_fill<<<vsa_grid(nb), VSA_BLOCK, 0, stream>>>(
-          wcount.as<uint32_t>(), nq, 0u, wboffset.as<uint64_t>(),
-          wlist.as<uint32_t>());
-      VSA_HIP(hipGetLastError());
-      // (the length of the list and the number of first-pass candidates,
-      // wboffset[nb], come to the host with the counts behind the search
-      // kernel: no wait here -- the plan kernel is launched over all reads
-      // and reads the length on the device)
-      nlistword = wboffset.as<uint64_t>() + nb;
-    }
-    {
-      // on the deep tables the plan answers the offsets it locates itself
-      // (PlanEmit)
-      planemit = deepok;
-      if (planemit)
-      {
-        // room for every search A of the workgroups that share a region
-        // (sized for a list of all reads: its length is not known here)
-        const uint64_t nb = blocksfor(nq),
-                       pershard = (nb + nshards - 1) / nshards;
-        pcap = pershard * VSA_BLOCK * (VSA_PLAN_ROUNDS - 1);
-        if (pcursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
-            pdoff.alloc(nshards * 8) || psummary.alloc(4 * 8) ||
-            prawout.alloc(nshards * pcap * recsize) ||
-            prawkeys.alloc(nshards * pcap * 8))
-        {
-          return -100;
-        }
-        VSA_HIP(hipMemsetAsync(pcursor.p, 0,
-                               (size_t) nshards * VSA_CURSOR_STRIDE * 8,
-                               stream));
-        PlanEmit em;
-        em.base = dbase;
-        em.perquery = perquery;
-        em.out = prawout.as<vsa_match>();
-        em.outkey = prawkeys.as<uint64_t>();
-        em.shardcap = pcap;
-        em.shardmask = nshards - 1;
-        em.cursors = pcursor.as<unsigned long long>();
-        em.packbits = packbits;
-        em.valbits = valbits;
-        if (rows)
-        {
-          k_mum_plan<IDX, true, true, true>
-              <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-                  ix, qs, wlist.as<uint32_t>(), nlistword, searchlength,
-                  wfirste.as<uint32_t>(), wcount.as<uint32_t>(),
-                  wplan.as<PlanRanges>(), em);
-        } else
-        {
-          k_mum_plan<IDX, true, true>
-              <<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-                  ix, qs, wlist.as<uint32_t>(), nlistword, searchlength,
-                  wfirste.as<uint32_t>(), wcount.as<uint32_t>(),
-                  wplan.as<PlanRanges>(), em);
-        }
-        VSA_HIP(shard_summary(pcursor.as<unsigned long long>(), nshards,
-                              pdoff.as<uint64_t>(), psummary.as<uint64_t>(),
-                              stream));
-      } else
-      {
-        k_mum_plan<IDX, false><<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-            ix, qs, wlist.as<uint32_t>(), nlistword, searchlength,
-            wfirste.as<uint32_t>(), wcount.as<uint32_t>(),
-            wplan.as<PlanRanges>());
-      }
-      VSA_HIP(hipGetLastError());
-    }
-    if (const char *pf = getenv("VSA_DEBUG_PLANFILE"))
-    {
-      // the plans of the first 65 536 queries as they stand when the search
-      // kernel starts -- per query its count and VSA_PLAN_RANGES ranges
-      // (first | length << 16), 32-bit words -- for bench.py, which prices
-      // the kernel on exactly the searches it runs
-      const uint64_t k = std::min<uint64_t>(nq, 65536);
-      std::vector<uint32_t> hc(k), hp(k * VSA_PLAN_RANGES);
-      VSA_HIP(hipMemcpyAsync(hc.data(), wcount.p, k * 4,
-                             hipMemcpyDeviceToHost, stream));
-      VSA_HIP(hipMemcpyAsync(hp.data(), wplan.p, k * sizeof(PlanRanges),
-                             hipMemcpyDeviceToHost, stream));
-      VSA_HIP(hipStreamSynchronize(stream));
-      if (FILE *f = fopen(pf, "wb"))
-      {
-        for (uint64_t q = 0; q < k; q++)
-        {
-          (void) fwrite(&hc[q], 4, 1, f);
-          (void) fwrite(&hp[q * VSA_PLAN_RANGES], 4, VSA_PLAN_RANGES, f);
-        }
-        fclose(f);
-      }
-    }
-    fromplan = true;
+    return -100;
   }
-  DevBuf doff, rawout, rawkeys, summary, blocksum, rtemp;
-  const uint64_t nplanblocks = (queries->nq + 255) / 256;
-  uint64_t plannedwork = 0;
+  VSA_HIP(hipMemsetAsync(st.pcursor.p, 0,
+                         (size_t) nshards * VSA_CURSOR_STRIDE * 8, st.stream));
+  em->base = st.dbase;
+  em->perquery = st.perquery;
+  em->out = st.prawout.as<vsa_match>();
+  em->outkey = st.prawkeys.as<uint64_t>();
+  em->shardcap = st.pcap;
+  em->shardmask = nshards - 1;
+  em->cursors = st.pcursor.as<unsigned long long>();
+  em->packbits = st.rec.packbits;
+  em->valbits = st.rec.valbits;
+  st.planemit = true;
+  return 0;
+}
+
+// the counts of the plan's cursor regions, where each goes in the list
+hipError_t plan_summary(QueryRun &st)
+{
+  return shard_summary(st.pcursor.as<unsigned long long>(), VSA_CURSOR_SHARDS,
+                       st.pdoff.as<uint64_t>(), st.psummary.as<uint64_t>(),
+                       st.stream);
+}
+
+// MEM: the first pass (offset 0 of every read), then the plan
+template <typename IDX>
+int mem_plan(QueryRun &st, const DevIndex<IDX> &ix)
+{
+  const vsa_index *index = st.index;
+  const uint64_t nq = st.queries->nq;
+  // one bit per text position: does its suffix have a neighbour in the
+  // suffix array with lcp >= L?  Made once per (index, L), kept.
+  if (index->repbits == nullptr || index->repleast != st.searchlength)
+  {
+    if (index->repbits == nullptr)
+    {
+      VSA_HIP(vsa_hip_malloc((void **) &index->repbits,
+                             ((index->n + 1) / 32 + 4) * 4));
+    }
+    VSA_HIP(hipMemsetAsync(index->repbits, 0, ((index->n + 1) / 32 + 4) * 4,
+                           st.stream));
+    k_repeat_bits<IDX><<<vsa_grid(blocksfor((index->n + 16) / 16)),
+                         VSA_BLOCK, 0, st.stream>>>(
+        ix.lcp, ix.suf, index->n, st.searchlength, index->repbits);
+    VSA_HIP(hipGetLastError());
+    index->repleast = st.searchlength;
+  }
+  const Form first = pickform(index, st.queries, st.qs, Stage::MemFirst,
+                              st.searchlength);
+  PlanEmit em;
+  // (a read answers at most one offset per round)
+  if (alloc_first(st) || first_pass(st, ix, first, nullptr) ||
+      plan_emit(st, VSA_PLAN_ROUNDS, &em))
+  {
+    return -100;
+  }
+  k_mem_plan<IDX><<<gridfor(nq), VSA_BLOCK, 0, st.stream>>>(
+      ix, st.qs, st.perquery, st.searchlength, st.wfirste.as<uint32_t>(),
+      st.wfmdb.as<uint64_t>(), index->repbits, st.wcount.as<uint32_t>(),
+      st.wplan.as<PlanRanges>(), em);
+  VSA_HIP(hipGetLastError());
+  VSA_HIP(plan_summary(st));
+  st.fromplan = true;
+  st.plansearches = nq; // (an upper bound of the plan's own locates per round)
+  return 0;
+}
+
+// VSA_DEBUG_PLANFILE: the plans of the first 65 536 queries as they stand
+// when the search kernel starts -- per query its count and VSA_PLAN_RANGES
+// ranges (first | length << 16), 32-bit words -- for bench.py, which prices
+// the kernel on exactly the searches it runs
+int dump_planfile(QueryRun &st, const char *pf)
+{
+  const uint64_t k = std::min<uint64_t>(st.queries->nq, 65536);
+  std::vector<uint32_t> hc(k), hp(k * VSA_PLAN_RANGES);
+  VSA_HIP(hipMemcpyAsync(hc.data(), st.wcount.p, k * 4,
+                         hipMemcpyDeviceToHost, st.stream));
+  VSA_HIP(hipMemcpyAsync(hp.data(), st.wplan.p, k * sizeof(PlanRanges),
+                         hipMemcpyDeviceToHost, st.stream));
+  VSA_HIP(hipStreamSynchronize(st.stream));
+  if (FILE *f = fopen(pf, "wb"))
+  {
+    for (uint64_t q = 0; q < k; q++)
+    {
+      (void) fwrite(&hc[q], 4, 1, f);
+      (void) fwrite(&hp[q * VSA_PLAN_RANGES], 4, VSA_PLAN_RANGES, f);
+    }
+    fclose(f);
+  }
+  return 0;
+}
+
+// MUM: the first pass, the reads it has not finished as a list, their plans
+template <typename IDX>
+int mum_plan(QueryRun &st, const DevIndex<IDX> &ix)
+{
+  const uint64_t nq = st.queries->nq;
+  if (alloc_first(st) || st.wlist.alloc(nq * 4))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemsetAsync(st.wcount.as<uint32_t>() + nq, 0, 4, st.stream));
+  // per workgroup of the first pass: reads it leaves to the plan | reads
+  // whose offset 0 is a candidate (counted by the first pass itself)
+  const uint64_t nb = blocksfor(nq), nbr = vsa_grid_blocks(nb);
+  DevBuf bcount;
+  if (bcount.alloc((nbr + 1) * 8) || st.wboffset.alloc((nbr + 1) * 8))
+  {
+    return -100;
+  }
+  // (both halves of a count stay below 2^32: nq does)
+  VSA_HIP(hipMemsetAsync(bcount.as<uint64_t>() + nb, 0, 8, st.stream));
+  if (first_pass(st, ix, st.form, bcount.as<uint64_t>()))
+  {
+    return -100;
+  }
+  // the reads the first pass has not finished, as a list (its counts per
+  // workgroup, a scan over the workgroups, an ordered fill); with it come
+  // the places of the first pass's candidates
+  VSA_HIP(rocprim_run(st.wtemp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, bcount.as<uint64_t>(),
+                                   st.wboffset.as<uint64_t>(), (uint64_t) 0,
+                                   (size_t) (nb + 1), rocprim::plus<uint64_t>(),
+                                   st.stream);
+  }));
+  k_wanted_fill<<<vsa_grid(nb), VSA_BLOCK, 0, st.stream>>>(
+      st.wcount.as<uint32_t>(), nq, 0u, st.wboffset.as<uint64_t>(),
+      st.wlist.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  // (the length of the list and the number of first-pass candidates,
+  // wboffset[nb], come to the host with the counts behind the search
+  // kernel: no wait here -- the plan kernel is launched over all reads
+  // and reads the length on the device)
+  st.nlistword = st.wboffset.as<uint64_t>() + nb;
+  // on the deep tables the plan answers the offsets it locates itself (room
+  // for every search A of a list of all reads: its length is not known here)
+  PlanEmit em = PlanEmit();
+  if (st.form != Form::Ref && plan_emit(st, VSA_PLAN_ROUNDS - 1, &em))
+  {
+    return -100;
+  }
+  withform(st.form, [&](auto deep, auto, auto rows, auto) {
+    k_mum_plan<IDX, deep, deep, rows><<<gridfor(nq), VSA_BLOCK, 0, st.stream>>>(
+        ix, st.qs, st.wlist.as<uint32_t>(), st.nlistword, st.searchlength,
+        st.wfirste.as<uint32_t>(), st.wcount.as<uint32_t>(),
+        st.wplan.as<PlanRanges>(), em);
+  });
+  if (st.planemit)
+  {
+    VSA_HIP(plan_summary(st));
+  }
+  VSA_HIP(hipGetLastError());
+  const char *pf = getenv("VSA_DEBUG_PLANFILE");
+  if (pf != nullptr && dump_planfile(st, pf))
+  {
+    return -100;
+  }
+  st.fromplan = true;
+  return 0;
+}
+
+// the search kernel: the planned form behind a plan, else every (query,
+// offset) pair (MEM, and MUM batches without a plan)
+template <typename IDX>
+void launch_search(QueryRun &st, const DevIndex<IDX> &ix,
+                   uint64_t nplanblocks)
+{
+  withform(st.form, [&](auto deep, auto, auto rows, auto) {
+    auto planned = [&](auto mum) {
+      k_query_search_planned<IDX, 256, deep, rows, mum>
+          <<<vsa_grid(nplanblocks), 256, 0, st.stream>>>(
+              ix, st.qs, st.dbase, st.perquery, st.wplan.as<PlanRanges>(),
+              st.wcount.as<uint32_t>(), st.searchlength,
+              st.rawout.as<vsa_match>(), st.rawkeys.as<uint64_t>(),
+              st.shardcap, VSA_CURSOR_SHARDS - 1,
+              st.cursor.as<unsigned long long>(), st.rec.packbits,
+              st.rec.valbits, st.blocksum.as<unsigned long long>());
+    };
+    auto unplanned = [&](auto mum) {
+      k_query_search<IDX, mum, deep, 256>
+          <<<vsa_grid((st.nitems + 255) / 256), 256, 0, st.stream>>>(
+              ix, st.qs, st.dbase, st.perquery, st.nitems, st.searchlength,
+              st.rawout.as<vsa_match>(), st.rawkeys.as<uint64_t>(),
+              st.shardcap, VSA_CURSOR_SHARDS - 1,
+              st.cursor.as<unsigned long long>(), st.rec.packbits,
+              st.rec.valbits);
+    };
+    if (st.fromplan && st.domum)
+    {
+      planned(std::true_type());
+    } else if (st.fromplan)
+    {
+      if constexpr (deep && !rows) // (the MEM plan: deep tables, bytes)
+      {
+        planned(std::false_type());
+      }
+    } else if (st.nitems > 0 && st.domum)
+    {
+      unplanned(std::true_type());
+    } else if (st.nitems > 0)
+    {
+      unplanned(std::false_type());
+    }
+  });
+}
+
+// The search into cursor regions.  First guess of their size: MUM modes
+// report at most one match per work-item but typically about one per query;
+// MEM is unbounded.  The kernel counts what it needs and never writes past a
+// region's capacity; on overflow of any region run again with regions of the
+// size that was asked for.
+template <typename IDX>
+int search(QueryRun &st, const DevIndex<IDX> &ix)
+{
+  const uint32_t nshards = VSA_CURSOR_SHARDS;
+  const uint64_t nplanblocks = (st.queries->nq + 255) / 256;
   size_t rbytes = 0;
-  if (fromplan)
+  if (st.fromplan)
   {
     // the work-items of the planned search: summed per workgroup by the
     // kernel, reduced behind it into the fifth word of the shard summary
-    if (blocksum.alloc((vsa_grid_blocks(nplanblocks) + 1) * 8))
+    if (st.blocksum.alloc((vsa_grid_blocks(nplanblocks) + 1) * 8))
     {
       return -100;
     }
     VSA_HIP(rocprim::reduce(nullptr, rbytes,
-                            blocksum.as<unsigned long long>(),
+                            st.blocksum.as<unsigned long long>(),
                             (unsigned long long *) nullptr, 0ull,
                             (size_t) nplanblocks,
-                            rocprim::plus<unsigned long long>(), stream));
-    if (rtemp.alloc(rbytes))
+                            rocprim::plus<unsigned long long>(), st.stream));
+    if (st.rtemp.alloc(rbytes))
     {
       return -100;
     }
   }
-  if (cursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
-      doff.alloc(nshards * 8) || summary.alloc(5 * 8))
+  if (st.cursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
+      st.doff.alloc(nshards * 8) || st.summary.alloc(5 * 8))
   {
     return -100;
   }
-  // first guess: MUM modes report at most one match per work-item but
-  // typically about one per query; MEM is unbounded.  The kernel counts what
-  // it needs and never writes past a region's capacity; on overflow of any
-  // region run again with regions of the size that was asked for.
-  uint64_t shardcap =
-      std::max<uint64_t>((queries->nq * 2 / nshards) * 5 / 4 + 64, 256);
-  uint64_t needed = 0, maxshard = 0;
-  double searchms = 0;
+  st.shardcap =
+      std::max<uint64_t>((st.queries->nq * 2 / nshards) * 5 / 4 + 64, 256);
+  uint64_t maxshard = 0;
   for (int attempt = 0; attempt < 2; attempt++)
   {
-    if (rawout.alloc(nshards * shardcap * recsize) ||
-        rawkeys.alloc(nshards * shardcap * 8))
+    if (st.rawout.alloc(nshards * st.shardcap * st.rec.recsize) ||
+        st.rawkeys.alloc(nshards * st.shardcap * 8))
     {
       return -100;
     }
-    VSA_HIP(hipMemsetAsync(cursor.p, 0,
-                           (size_t) nshards * VSA_CURSOR_STRIDE * 8, stream));
-    tsearch.start();
-#define VSA_LAUNCH_QUERY(MUMFLAG, KEYFLAG)                                     \
-  k_query_search<IDX, MUMFLAG, KEYFLAG, 256>                                  \
-      <<<vsa_grid((nwork + 255) / 256), 256, 0, stream>>>(                    \
-          ix, qs, dbase, perquery, nwork, searchlength,                       \
-          rawout.as<vsa_match>(), rawkeys.as<uint64_t>(), shardcap,           \
-          nshards - 1, cursor.as<unsigned long long>(), packbits, valbits)
-    if (fromplan && memplan)
-    {
-      k_query_search_planned<IDX, 256, true, false, false>
-          <<<vsa_grid(nplanblocks), 256, 0, stream>>>(
-              ix, qs, dbase, perquery, wplan.as<PlanRanges>(),
-              wcount.as<uint32_t>(), searchlength, rawout.as<vsa_match>(),
-              rawkeys.as<uint64_t>(), shardcap, nshards - 1,
-              cursor.as<unsigned long long>(), packbits, valbits,
-              blocksum.as<unsigned long long>());
-    } else if (fromplan && rows)
-    {
-      k_query_search_planned<IDX, 256, true, true>
-          <<<vsa_grid(nplanblocks), 256, 0, stream>>>(
-              ix, qs, dbase, perquery, wplan.as<PlanRanges>(),
-              wcount.as<uint32_t>(), searchlength, rawout.as<vsa_match>(),
-              rawkeys.as<uint64_t>(), shardcap, nshards - 1,
-              cursor.as<unsigned long long>(), packbits, valbits,
-              blocksum.as<unsigned long long>());
-    } else if (fromplan && deepok)
-    {
-      k_query_search_planned<IDX, 256, true>
-          <<<vsa_grid(nplanblocks), 256, 0, stream>>>(
-              ix, qs, dbase, perquery, wplan.as<PlanRanges>(),
-              wcount.as<uint32_t>(), searchlength, rawout.as<vsa_match>(),
-              rawkeys.as<uint64_t>(), shardcap, nshards - 1,
-              cursor.as<unsigned long long>(), packbits, valbits,
-              blocksum.as<unsigned long long>());
-    } else if (fromplan)
-    {
-      k_query_search_planned<IDX, 256, false>
-          <<<vsa_grid(nplanblocks), 256, 0, stream>>>(
-              ix, qs, dbase, perquery, wplan.as<PlanRanges>(),
-              wcount.as<uint32_t>(), searchlength, rawout.as<vsa_match>(),
-              rawkeys.as<uint64_t>(), shardcap, nshards - 1,
-              cursor.as<unsigned long long>(), packbits, valbits,
-              blocksum.as<unsigned long long>());
-    } else if (nwork > 0)
-    {
-      // every (query, offset) pair: MEM, and MUM batches without a plan
-      // (deep locate needs the deep prefix to fit into every search)
-      if (domum && deepok)
-      {
-        VSA_LAUNCH_QUERY(true, true);
-      } else if (domum)
-      {
-        VSA_LAUNCH_QUERY(true, false);
-      } else if (deepok)
-      {
-        VSA_LAUNCH_QUERY(false, true);
-      } else
-      {
-        VSA_LAUNCH_QUERY(false, false);
-      }
-    }
-#undef VSA_LAUNCH_QUERY
-    tsearch.stop();
+    VSA_HIP(hipMemsetAsync(st.cursor.p, 0,
+                           (size_t) nshards * VSA_CURSOR_STRIDE * 8,
+                           st.stream));
+    st.tsearch.start();
+    launch_search(st, ix, nplanblocks);
+    st.tsearch.stop();
     VSA_HIP(hipGetLastError());
-    if (fromplan)
+    if (st.fromplan)
     {
-      VSA_HIP(rocprim::reduce(rtemp.p, rbytes,
-                              blocksum.as<unsigned long long>(),
-                              summary.as<unsigned long long>() + 4, 0ull,
+      VSA_HIP(rocprim::reduce(st.rtemp.p, rbytes,
+                              st.blocksum.as<unsigned long long>(),
+                              st.summary.as<unsigned long long>() + 4, 0ull,
                               (size_t) nplanblocks,
-                              rocprim::plus<unsigned long long>(), stream));
+                              rocprim::plus<unsigned long long>(), st.stream));
     }
     // where each region goes in the dense list, how much there is
-    VSA_HIP(shard_summary(cursor.as<unsigned long long>(), nshards,
-                          doff.as<uint64_t>(), summary.as<uint64_t>(),
-                          stream));
-    {
-      const Fetch f[7] = {{summary.as<uint64_t>(), 8},
-                          {summary.as<uint64_t>() + 1, 8},
-                          {summary.as<uint64_t>() + 2, 8},
-                          {summary.as<uint64_t>() + 3, 8},
-                          {summary.as<uint64_t>() + 4, 8},
-                          {planemit ? psummary.p : summary.p, 8},
-                          {nlistword != nullptr ? (const void *) nlistword
-                                                : summary.p, 8}};
-      uint64_t got[7];
-      if (fetchwords(stream, f, 7, got))
-      {
-        return -100;
-      }
-      if (nlistword != nullptr)
-      {
-        nfirstpass = got[6] >> 32;
-        plansearches = 2 * (got[6] & 0xFFFFFFFFull);
-      }
-      nplan = planemit ? got[5] : 0;
-      needed = got[0];
-      maxshard = got[1];
-      nfirst = fromplan ? nfirstpass : 0;
-      plannedwork = fromplan ? got[4] : 0;
-    }
-    searchms += tsearch.ms();
-    if (maxshard <= shardcap)
-    {
-      break;
-    }
-    shardcap = maxshard;
-  }
-  if (maxshard > shardcap)
-  {
-    VSA_ERROR("match buffer overflow: %llu > %llu",
-              (unsigned long long) maxshard, (unsigned long long) shardcap);
-    return -5;
-  }
-  if (needed + nplan + nfirst > 0)
-  {
-    if (out.alloc((needed + nplan + nfirst) * recsize) ||
-        keys.alloc((needed + nplan + nfirst) * 8))
+    const uint64_t *sm = st.summary.as<uint64_t>();
+    VSA_HIP(shard_summary(st.cursor.as<unsigned long long>(), nshards,
+                          st.doff.as<uint64_t>(), st.summary.as<uint64_t>(),
+                          st.stream));
+    const Fetch f[7] = {{sm, 8}, {sm + 1, 8}, {sm + 2, 8}, {sm + 3, 8},
+                        {sm + 4, 8}, {st.planemit ? st.psummary.p : sm, 8},
+                        {st.nlistword != nullptr ? st.nlistword : sm, 8}};
+    uint64_t got[7];
+    if (fetchwords(st.stream, f, 7, got))
     {
       return -100;
     }
-    if (nplan > 0 && valbits != 0)
+    if (st.nlistword != nullptr)
     {
-      k_compact_shards<uint32_t><<<nshards, VSA_BLOCK, 0, stream>>>(
-          prawout.as<uint32_t>(), prawkeys.as<uint64_t>(), pcap,
-          pcursor.as<unsigned long long>(), pdoff.as<uint64_t>(),
-          out.as<uint32_t>() + needed, keys.as<uint64_t>() + needed);
-      VSA_HIP(hipGetLastError());
-    } else if (nplan > 0 && packed)
-    {
-      k_compact_shards<uint64_t><<<nshards, VSA_BLOCK, 0, stream>>>(
-          prawout.as<uint64_t>(), prawkeys.as<uint64_t>(), pcap,
-          pcursor.as<unsigned long long>(), pdoff.as<uint64_t>(),
-          out.as<uint64_t>() + needed, keys.as<uint64_t>() + needed);
-      VSA_HIP(hipGetLastError());
-    } else if (nplan > 0)
-    {
-      k_compact_shards<vsa_match><<<nshards, VSA_BLOCK, 0, stream>>>(
-          prawout.as<vsa_match>(), prawkeys.as<uint64_t>(), pcap,
-          pcursor.as<unsigned long long>(), pdoff.as<uint64_t>(),
-          out.as<vsa_match>() + needed, keys.as<uint64_t>() + needed);
-      VSA_HIP(hipGetLastError());
+      st.nfirst = got[6] >> 32;
+      st.plansearches = 2 * (got[6] & 0xFFFFFFFFull);
     }
-    if (needed > 0 && valbits != 0)
+    st.nplan = st.planemit ? got[5] : 0;
+    st.needed = got[0];
+    maxshard = got[1];
+    st.plannedwork = st.fromplan ? got[4] : 0;
+    st.searchms += st.tsearch.ms();
+    if (maxshard <= st.shardcap)
     {
-      k_compact_shards<uint32_t><<<nshards, VSA_BLOCK, 0, stream>>>(
-          rawout.as<uint32_t>(), rawkeys.as<uint64_t>(), shardcap,
-          cursor.as<unsigned long long>(), doff.as<uint64_t>(),
-          out.as<uint32_t>(), keys.as<uint64_t>());
-      VSA_HIP(hipGetLastError());
-    } else if (needed > 0 && packed)
-    {
-      k_compact_shards<uint64_t><<<nshards, VSA_BLOCK, 0, stream>>>(
-          rawout.as<uint64_t>(), rawkeys.as<uint64_t>(), shardcap,
-          cursor.as<unsigned long long>(), doff.as<uint64_t>(),
-          out.as<uint64_t>(), keys.as<uint64_t>());
-      VSA_HIP(hipGetLastError());
-    } else if (needed > 0)
-    {
-      k_compact_shards<vsa_match><<<nshards, VSA_BLOCK, 0, stream>>>(
-          rawout.as<vsa_match>(), rawkeys.as<uint64_t>(), shardcap,
-          cursor.as<unsigned long long>(), doff.as<uint64_t>(),
-          out.as<vsa_match>(), keys.as<uint64_t>());
-      VSA_HIP(hipGetLastError());
+      return 0;
     }
-    if (nfirst > 0)
-    {
-      k_append_first<<<gridfor(queries->nq), VSA_BLOCK, 0, stream>>>(
-          wfmlen.as<uint32_t>(), wfmdb.as<uint64_t>(),
-          wboffset.as<uint64_t>(), queries->nq, perquery, dbase, qs.seqoffset,
-          needed + nplan,
-          out.as<vsa_match>(), keys.as<uint64_t>(), packbits, valbits);
-      VSA_HIP(hipGetLastError());
-    }
-    needed += nplan + nfirst;
+    st.shardcap = maxshard;
   }
-  res->stats.candidates = domum ? needed : 0;
-  if (keeppairs)
+  VSA_ERROR("match buffer overflow: %llu > %llu",
+            (unsigned long long) maxshard, (unsigned long long) st.shardcap);
+  return -5;
+}
+
+// the search's answers, the plan's and the first pass's into one dense list
+int compact(QueryRun &st)
+{
+  const uint64_t total = st.needed + st.nplan + st.nfirst;
+  if (total == 0)
+  {
+    return 0;
+  }
+  if (st.out.alloc(total * st.rec.recsize) || st.keys.alloc(total * 8) ||
+      (st.nplan > 0 &&
+       compact_into(st.rec, st.prawout, st.prawkeys, st.pcap, st.pcursor,
+                    st.pdoff, st.out, st.keys, st.needed, st.stream)) ||
+      (st.needed > 0 &&
+       compact_into(st.rec, st.rawout, st.rawkeys, st.shardcap, st.cursor,
+                    st.doff, st.out, st.keys, 0, st.stream)))
+  {
+    return -100;
+  }
+  if (st.nfirst > 0)
+  {
+    k_append_first<<<gridfor(st.queries->nq), VSA_BLOCK, 0, st.stream>>>(
+        st.wfmlen.as<uint32_t>(), st.wfmdb.as<uint64_t>(),
+        st.wboffset.as<uint64_t>(), st.queries->nq, st.perquery, st.dbase,
+        st.qs.seqoffset, st.needed + st.nplan, st.out.as<vsa_match>(),
+        st.keys.as<uint64_t>(), st.rec.packbits, st.rec.valbits);
+    VSA_HIP(hipGetLastError());
+  }
+  st.needed = total;
+  return 0;
+}
+
+// the dense list into the result: the pairs themselves, the MUMs behind the
+// filter, the candidates as they lie, or the matches in reference order;
+// *mumsum: the sum of the MUMs' lengths if the filter made it
+int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
+{
+  const RecordForm &rec = st.rec;
+  const uint64_t needed = st.needed;
+  res->stats.candidates = st.domum ? needed : 0;
+  if (rec.keeppairs)
   {
     res->count = needed;
-    res->packbits = lenbits;
+    res->packbits = rec.lenbits;
     if (needed > 0)
     {
-      res->matches = (vsa_match *) keys.release();
-      res->packvals = (uint64_t *) out.release();
+      res->matches = (vsa_match *) st.keys.release();
+      res->packvals = (uint64_t *) st.out.release();
     }
-  } else if (domum && !domumcand)
+  } else if (st.domum && !st.domumcand)
   {
     DevBuf mums;
     uint64_t nm = 0;
-    if (valbits != 0)
+    int rc;
+    if (rec.valbits != 0)
     {
-      if (mumfilter_packed<uint32_t>(keys.as<const uint64_t>(),
-                                     out.as<const uint32_t>(), needed, lenbits, dbbits,
-                                     stream, mums, &nm, &mumsum, 0, valbits,
-                                     qs.seqoffset))
-      {
-        return -100;
-      }
-    } else if (packed)
+      rc = mumfilter_packed<uint32_t>(
+          st.keys.as<const uint64_t>(), st.out.as<const uint32_t>(), needed,
+          rec.lenbits, rec.dbbits, st.stream, mums, &nm, mumsum, 0,
+          rec.valbits, st.qs.seqoffset);
+    } else if (rec.packed)
     {
-      if (mumfilter_packed(keys.as<const uint64_t>(),
-                           out.as<const uint64_t>(), needed, lenbits, dbbits, stream, mums,
-                           &nm, &mumsum))
-      {
-        return -100;
-      }
-    } else if (mumuniqueinquery(out, needed, stream, mums, &nm, 0, nullptr,
-                                index->n, queries->maxlength, &mumsum))
+      rc = mumfilter_packed(st.keys.as<const uint64_t>(),
+                            st.out.as<const uint64_t>(), needed, rec.lenbits,
+                            rec.dbbits, st.stream, mums, &nm, mumsum);
+    } else
+    {
+      rc = mumuniqueinquery(st.out, needed, st.stream, mums, &nm, 0, nullptr,
+                            st.index->n, st.queries->maxlength, mumsum);
+    }
+    if (rc != 0)
     {
       return -100;
     }
     res->count = nm;
     res->matches = (vsa_match *) mums.release();
-  } else if (needed > 0 && !ordered && domum)
+  } else if (needed > 0 && !st.ordered && st.domum)
   {
     // candidates for a filter that sorts them anyway (multi-GPU -mum): as
     // they lie
     res->count = needed;
-    res->matches = (vsa_match *) out.release();
+    res->matches = (vsa_match *) st.out.release();
   } else if (needed > 0)
   {
     // reference order = work-item order; appends of one work-item are
     // contiguous and in order, the radix sort is stable
     DevBuf sk, sm;
-    if (sk.alloc(needed * 8) || sm.alloc(needed * sizeof(vsa_match)))
-    {
-      return -100;
-    }
-    if (sortbykey(keys.as<uint64_t>(), sk.as<uint64_t>(),
-                  out.as<vsa_match>(), sm.as<vsa_match>(), needed,
-                  bitsfor(nitems), stream))
+    if (sk.alloc(needed * 8) || sm.alloc(needed * sizeof(vsa_match)) ||
+        sortbykey(st.keys.as<uint64_t>(), sk.as<uint64_t>(),
+                  st.out.as<vsa_match>(), sm.as<vsa_match>(), needed,
+                  bitsfor(st.nitems), st.stream))
     {
       return -100;
     }
     res->count = needed;
     res->matches = (vsa_match *) sm.release();
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->stats.count = res->count;
-  res->stats.search_kernel_ms = searchms;
-  res->stats.anchor_ms = 0; // (the anchor pass of round 1 is gone)
-  res->stats.first_kernel_ms = tfirst.ms();
-  if (fromplan)
+  return 0;
+}
+
+// -l L (MEM), -mum cand, -mum: the stages above in order
+template <typename IDX>
+int run_query(const vsa_index *index, const vsa_queries *queries, bool domum,
+              bool domumcand, uint32_t searchlength, vsa_result *res,
+              bool ordered = true, uint32_t forcebits = 0)
+{
+  vsa_dev_set_stream(index->stream);
+  QueryRun st(index, queries, domum, domumcand, ordered, searchlength);
+  const DevIndex<IDX> ix = index->view<IDX>();
+  if (workitems<IDX>(st))
   {
-    nwork = plannedwork;
-    res->stats.searches = nwork + queries->nq + plansearches;
+    return -100;
   }
-  res->stats.kernel_searches = nwork;
-  res->stats.total_device_ms = tall.ms();
+  res->stats.searches = st.nitems;
+  if (st.nitems == 0)
+  {
+    return 0;
+  }
+  st.tall.start();
+  if (const int rc = recordform(index, queries, domum, domumcand, ordered,
+                                forcebits, &st.rec))
+  {
+    return rc;
+  }
+  if (decide(st) || (st.memplan && mem_plan(st, ix)) ||
+      (st.reduce && mum_plan(st, ix)))
+  {
+    return -100;
+  }
+  if (const int rc = search(st, ix))
+  {
+    return rc;
+  }
+  uint64_t mumsum = ~0ull;
+  if (compact(st) || finish(st, res, &mumsum))
+  {
+    return -100;
+  }
+  st.tall.stop();
+  VSA_HIP(hipStreamSynchronize(st.stream));
+  res->stats.count = res->count;
+  res->stats.search_kernel_ms = st.searchms;
+  res->stats.anchor_ms = 0; // (the anchor pass of round 1 is gone)
+  res->stats.first_kernel_ms = st.tfirst.ms();
+  res->stats.kernel_searches = st.fromplan ? st.plannedwork : st.nitems;
+  if (st.fromplan)
+  {
+    res->stats.searches = st.plannedwork + queries->nq + st.plansearches;
+  }
+  res->stats.total_device_ms = st.tall.ms();
   if (mumsum != ~0ull)
   {
     res->stats.sumlength = mumsum; // the filter summed the lengths already
     return 0;
   }
-  if (keeppairs)
+  if (st.rec.keeppairs)
   {
     res->stats.sumlength = 0; // of candidates: nobody asks
     return 0;
   }
-  return sumlengths(res->matches, res->count, stream, &res->stats.sumlength);
+  return sumlengths(res->matches, res->count, st.stream,
+                    &res->stats.sumlength);
 }
 
-} // namespace
-
-// ---------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------
-
-extern "C" int vsa_findcompletematches(const vsa_index *index,
-                                       const vsa_queries *queries,
-                                       vsa_result **result)
+// What the query entries share: the checks on their arguments (searchlength:
+// nullptr for -complete), then limits() -- each entry's own checks on
+// lengths -- and run(IDX(), res) on a fresh result for the index's offset
+// width.  The result goes to *result when run returns 0, and is freed
+// otherwise.
+template <typename Limits, typename Run>
+int query_entry(const char *name, const vsa_index *index,
+                const vsa_queries *queries, const uint64_t *searchlength,
+                vsa_result **result, Limits limits, Run run)
 {
   if (index == nullptr || queries == nullptr || result == nullptr)
   {
-    VSA_ERROR("vsa_findcompletematches: NULL argument");
-    return -1;
-  }
-  *result = nullptr;
-  if (queries->device != index->device)
-  {
-    VSA_ERROR("queries live on device %d, index on device %d",
-              queries->device, index->device);
-    return -1;
-  }
-  if (index->bck == nullptr)
-  {
-    VSA_ERROR("table bck is not loaded");
-    return -3;
-  }
-  if (queries->maxlength > 0xFFFFFFF0ull)
-  {
-    VSA_ERROR("query length beyond 32 bits is not supported");
-    return -3;
-  }
-  if (vsa_set_device(index->device) != 0)
-  {
-    return -100;
-  }
-  // Vmengine/exactcompl.c:179-185: the first query shorter than
-  // prefixlength stops the run; queries before it are still matched
-  uint64_t qlimit = queries->nq;
-  bool shortquery = false;
-  if (queries->minlength < index->pl)
-  {
-    for (uint64_t q = 0; q < queries->nq; q++)
-    {
-      if (queries->hlength[q] < index->pl)
-      {
-        qlimit = q;
-        shortquery = true;
-        break;
-      }
-    }
-  }
-  vsa_result *res = newresult(index->device);
-  const int rc = (index->isize == 4)
-                     ? run_complete<uint32_t>(index, queries, qlimit, res)
-                     : run_complete<uint64_t>(index, queries, qlimit, res);
-  if (rc != 0)
-  {
-    vsa_result_free(res);
-    return rc;
-  }
-  *result = res;
-  if (shortquery)
-  {
-    VSA_ERROR("patternlength=%lu must be >= %lu=prefixlen",
-              (unsigned long) queries->hlength[qlimit],
-              (unsigned long) index->pl);
-    return -2;
-  }
-  return 0;
-}
-
-extern "C" int vsa_findmumcandidates(const vsa_index *index,
-                                     const vsa_queries *queries,
-                                     uint64_t searchlength, int ordered,
-                                     vsa_result **result)
-{
-  if (ordered)
-  {
-    return vsa_findquerymatches(index, queries, 1, 1, searchlength, result);
-  }
-  if (index == nullptr || queries == nullptr || result == nullptr)
-  {
-    VSA_ERROR("vsa_findmumcandidates: NULL argument");
-    return -1;
-  }
-  *result = nullptr;
-  if (index->bck == nullptr)
-  {
-    VSA_ERROR("table bck is not loaded");
-    return -3;
-  }
-  if (searchlength < index->pl || searchlength > 0xFFFFFFF0ull)
-  {
-    // Vmengine/fquery.c:440-446
-    VSA_ERROR("searchlength=%lu must be >= %lu=prefixlen",
-              (unsigned long) searchlength, (unsigned long) index->pl);
-    return -2;
-  }
-  if (vsa_set_device(index->device) != 0)
-  {
-    return -100;
-  }
-  vsa_result *res = newresult(index->device);
-  const int rc =
-      (index->isize == 4)
-          ? run_query<uint32_t>(index, queries, true, true,
-                                (uint32_t) searchlength, res, false)
-          : run_query<uint64_t>(index, queries, true, true,
-                                (uint32_t) searchlength, res, false);
-  if (rc != 0)
-  {
-    vsa_result_free(res);
-    return rc;
-  }
-  *result = res;
-  return 0;
-}
-
-extern "C" int vsa_findmumcandidates_packed(const vsa_index *index,
-                                            const vsa_queries *queries,
-                                            uint64_t searchlength,
-                                            uint32_t lengthbits,
-                                            vsa_result **result)
-{
-  if (index == nullptr || queries == nullptr || result == nullptr)
-  {
-    VSA_ERROR("vsa_findmumcandidates_packed: NULL argument");
-    return -1;
-  }
-  *result = nullptr;
-  if (index->bck == nullptr)
-  {
-    VSA_ERROR("table bck is not loaded");
-    return -3;
-  }
-  if (searchlength < index->pl || searchlength > 0xFFFFFFF0ull)
-  {
-    // Vmengine/fquery.c:440-446
-    VSA_ERROR("searchlength=%lu must be >= %lu=prefixlen",
-              (unsigned long) searchlength, (unsigned long) index->pl);
-    return -2;
-  }
-  if (lengthbits == 0)
-  {
-    lengthbits = bitsfor(queries->maxlength);
-  }
-  if (lengthbits > 16)
-  {
-    VSA_ERROR("packed candidates: at most 16 length bits");
-    return -2;
-  }
-  if (vsa_set_device(index->device) != 0)
-  {
-    return -100;
-  }
-  vsa_result *res = newresult(index->device);
-  const int rc =
-      (index->isize == 4)
-          ? run_query<uint32_t>(index, queries, true, true,
-                                (uint32_t) searchlength, res, false,
-                                lengthbits)
-          : run_query<uint64_t>(index, queries, true, true,
-                                (uint32_t) searchlength, res, false,
-                                lengthbits);
-  if (rc != 0)
-  {
-    vsa_result_free(res);
-    return rc;
-  }
-  *result = res;
-  return 0;
-}
-
-extern "C" int vsa_findquerymatches(const vsa_index *index,
-                                    const vsa_queries *queries,
-                                    int domaximaluniquematch,
-                                    int domaximaluniquematchcandidates,
-                                    uint64_t searchlength,
-                                    vsa_result **result)
-{
-  if (index == nullptr || queries == nullptr || result == nullptr)
-  {
-    VSA_ERROR("vsa_findquerymatches: NULL argument");
+    VSA_ERROR("%s: NULL argument", name);
     return -1;
   }
   *result = nullptr;
@@ -1549,30 +1365,23 @@ extern "C" int vsa_findquerymatches(const vsa_index *index,
     return -3;
   }
   // Vmengine/fquery.c:440-446
-  if (searchlength < index->pl)
+  if (searchlength != nullptr && *searchlength < index->pl)
   {
     VSA_ERROR("searchlength=%lu must be >= %lu=prefixlen",
-              (unsigned long) searchlength, (unsigned long) index->pl);
+              (unsigned long) *searchlength, (unsigned long) index->pl);
     return -2;
   }
-  if (searchlength > 0xFFFFFFFFull || queries->maxlength > 0xFFFFFFF0ull)
+  if (const int rc = limits())
   {
-    VSA_ERROR("query or search length beyond 32 bits is not supported");
-    return -3;
+    return rc;
   }
   if (vsa_set_device(index->device) != 0)
   {
     return -100;
   }
   vsa_result *res = newresult(index->device);
-  const bool mum = domaximaluniquematch != 0,
-             cand = domaximaluniquematchcandidates != 0;
   const int rc =
-      (index->isize == 4)
-          ? run_query<uint32_t>(index, queries, mum, cand,
-                                (uint32_t) searchlength, res)
-          : run_query<uint64_t>(index, queries, mum, cand,
-                                (uint32_t) searchlength, res);
+      (index->isize == 4) ? run(uint32_t(), res) : run(uint64_t(), res);
   if (rc != 0)
   {
     vsa_result_free(res);
@@ -1580,6 +1389,145 @@ extern "C" int vsa_findquerymatches(const vsa_index *index,
   }
   *result = res;
   return 0;
+}
+
+// the check of both vsa_findmumcandidates entries on the search length
+// (with the prefix length's message)
+int mumlimit(const vsa_index *index, uint64_t searchlength)
+{
+  if (searchlength > 0xFFFFFFF0ull)
+  {
+    VSA_ERROR("searchlength=%lu must be >= %lu=prefixlen",
+              (unsigned long) searchlength, (unsigned long) index->pl);
+    return -2;
+  }
+  return 0;
+}
+
+} // namespace
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+
+extern "C" int vsa_findcompletematches(const vsa_index *index,
+                                       const vsa_queries *queries,
+                                       vsa_result **result)
+{
+  uint64_t qlimit = 0;
+  bool shortquery = false;
+  const int rc = query_entry(
+      "vsa_findcompletematches", index, queries, nullptr, result,
+      [&] {
+        if (queries->maxlength > 0xFFFFFFF0ull)
+        {
+          VSA_ERROR("query length beyond 32 bits is not supported");
+          return -3;
+        }
+        return 0;
+      },
+      [&](auto idx, vsa_result *res) {
+        // Vmengine/exactcompl.c:179-185: the first query shorter than
+        // prefixlength stops the run; queries before it are still matched
+        qlimit = queries->nq;
+        if (queries->minlength < index->pl)
+        {
+          for (uint64_t q = 0; q < queries->nq; q++)
+          {
+            if (queries->hlength[q] < index->pl)
+            {
+              qlimit = q;
+              shortquery = true;
+              break;
+            }
+          }
+        }
+        return run_complete<decltype(idx)>(index, queries, qlimit, res);
+      });
+  if (rc == 0 && shortquery)
+  {
+    VSA_ERROR("patternlength=%lu must be >= %lu=prefixlen",
+              (unsigned long) queries->hlength[qlimit],
+              (unsigned long) index->pl);
+    return -2;
+  }
+  return rc;
+}
+
+extern "C" int vsa_findmumcandidates(const vsa_index *index,
+                                     const vsa_queries *queries,
+                                     uint64_t searchlength, int ordered,
+                                     vsa_result **result)
+{
+  if (ordered)
+  {
+    return vsa_findquerymatches(index, queries, 1, 1, searchlength, result);
+  }
+  return query_entry(
+      "vsa_findmumcandidates", index, queries, &searchlength, result,
+      [&] { return mumlimit(index, searchlength); },
+      [&](auto idx, vsa_result *res) {
+        return run_query<decltype(idx)>(index, queries, true, true,
+                                        (uint32_t) searchlength, res, false);
+      });
+}
+
+extern "C" int vsa_findmumcandidates_packed(const vsa_index *index,
+                                            const vsa_queries *queries,
+                                            uint64_t searchlength,
+                                            uint32_t lengthbits,
+                                            vsa_result **result)
+{
+  return query_entry(
+      "vsa_findmumcandidates_packed", index, queries, &searchlength, result,
+      [&] {
+        if (const int rc = mumlimit(index, searchlength))
+        {
+          return rc;
+        }
+        if (lengthbits == 0)
+        {
+          lengthbits = bitsfor(queries->maxlength);
+        }
+        if (lengthbits > 16)
+        {
+          VSA_ERROR("packed candidates: at most 16 length bits");
+          return -2;
+        }
+        return 0;
+      },
+      [&](auto idx, vsa_result *res) {
+        return run_query<decltype(idx)>(index, queries, true, true,
+                                        (uint32_t) searchlength, res, false,
+                                        lengthbits);
+      });
+}
+
+extern "C" int vsa_findquerymatches(const vsa_index *index,
+                                    const vsa_queries *queries,
+                                    int domaximaluniquematch,
+                                    int domaximaluniquematchcandidates,
+                                    uint64_t searchlength,
+                                    vsa_result **result)
+{
+  return query_entry(
+      "vsa_findquerymatches", index, queries, &searchlength, result,
+      [&] {
+        if (searchlength > 0xFFFFFFFFull ||
+            queries->maxlength > 0xFFFFFFF0ull)
+        {
+          VSA_ERROR("query or search length beyond 32 bits is not "
+                    "supported");
+          return -3;
+        }
+        return 0;
+      },
+      [&](auto idx, vsa_result *res) {
+        return run_query<decltype(idx)>(
+            index, queries, domaximaluniquematch != 0,
+            domaximaluniquematchcandidates != 0, (uint32_t) searchlength,
+            res);
+      });
 }
 
 static int mumfilter_entry(void *device_candidates, uint64_t ncandidates,
