@@ -211,7 +211,6 @@ int approx_mixed(const vsa_index *index, const vsa_queries *queries,
   // (a macro that returns would leak the three lists)
   auto merge = [&]() -> int {
     DevBuf all, merged, keys, keys2, order, order2, temp;
-    size_t tb = 0;
     if (n == 0)
     {
       return 0;
@@ -244,18 +243,12 @@ int approx_mixed(const vsa_index *index, const vsa_queries *queries,
         sb.which.as<uint64_t>(), queries->seqoffset, keys.as<uint32_t>(),
         order.as<uint32_t>());
     VSA_HIP(hipGetLastError());
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, keys.as<uint32_t>(), keys2.as<uint32_t>(),
-        order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) n, 0u,
-        bitsfor(nq), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, keys.as<uint32_t>(), keys2.as<uint32_t>(),
-        order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) n, 0u,
-        bitsfor(nq), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(
+          p, tb, keys.as<uint32_t>(), keys2.as<uint32_t>(),
+          order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) n, 0u,
+          bitsfor(nq), stream);
+    }));
     VSA_HIP(gather_matches(all.as<vsa_match>(), order2.as<uint32_t>(), n,
                            merged.as<vsa_match>(), stream));
     VSA_HIP(hipStreamSynchronize(stream));

@@ -777,28 +777,6 @@ struct MaxU64
   }
 };
 
-static int apm_exclusive_sum(uint64_t *counts, uint64_t *offsets, uint64_t n,
-                             hipStream_t stream, uint64_t *total)
-{
-  // counts has n + 1 entries, the last one 0
-  DevBuf temp;
-  size_t tb = 0;
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, counts, offsets, (uint64_t) 0,
-                                  (size_t) (n + 1), rocprim::plus<uint64_t>(),
-                                  stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, counts, offsets, (uint64_t) 0,
-                                  (size_t) (n + 1), rocprim::plus<uint64_t>(),
-                                  stream));
-  VSA_HIP(hipMemcpyAsync(total, offsets + n, 8, hipMemcpyDeviceToHost,
-                         stream));
-  VSA_HIP(hipStreamSynchronize(stream));
-  return 0;
-}
-
 // the host-side plan of a batch: thresholds and piece geometry per query
 struct ApmPlan
 {
@@ -823,6 +801,15 @@ struct ApmPlan
   uint64_t npieces(uint64_t nq) const
   {
     return uniform ? nq * upieces : (bylength ? totalpieces : piecebase[nq]);
+  }
+  uint32_t maxk(uint64_t nq) const // the largest threshold
+  {
+    if (uniform)
+    {
+      return uk;
+    }
+    return bylength ? *std::max_element(tk.begin(), tk.end())
+                    : *std::max_element(k.begin(), k.begin() + nq);
   }
 };
 
@@ -1061,83 +1048,106 @@ static int apm_plan(const vsa_index *index, const vsa_queries *queries,
   return 0;
 }
 
-template <typename IDX>
-int run_approx(const vsa_index *index, const vsa_queries *queries,
-               bool doedist, const ApmPlan &plan, vsa_result *res)
-{
-  hipStream_t stream = index->stream;
-  vsa_dev_set_stream(stream);
-  Timer tall(stream), tsearch(stream);
-  const DevIndex<IDX> ix = index->view<IDX>();
-  const DevQueries qs = devqueries(queries);
-  const uint64_t nq = plan.qlimit, npieces = plan.npieces(nq);
-  DevBuf dk, dsplitlen, dpiecebase, pstart, plen, pquery, ppoffset, left,
-      count, offsets, keys, keys2, his, his2, ends, prev, flags, rank, temp,
-      rq, rlo, rhi, rfirst, rcount, roffsets, hitpos, hitregion, matches,
-      dflag, cand, keep, dcount;
-  uint64_t total = 0, nregions = 0, nhits = 0;
-  size_t tb = 0;
+// ---- the stages of the approximate search ---------------------------------
+// run_approx (below) and run_approx_tree (approx_tree.inc) are lists of these.
 
-  res->stats.searches = npieces;
-  if (nq == 0 || npieces == 0)
+// fn(W): W = std::integral_constant<int, words>, the 64-bit words of the
+// longest pattern (1 .. VSA_APM_MAXWORDS)
+template <typename Fn>
+void withwords(int words, Fn &&fn)
+{
+  switch (words)
   {
-    return 0;
+  case 1: return fn(std::integral_constant<int, 1>());
+  case 2: return fn(std::integral_constant<int, 2>());
+  case 3: return fn(std::integral_constant<int, 3>());
+  case 4: return fn(std::integral_constant<int, 4>());
+  case 5: return fn(std::integral_constant<int, 5>());
+  case 6: return fn(std::integral_constant<int, 6>());
+  case 7: return fn(std::integral_constant<int, 7>());
+  default: return fn(std::integral_constant<int, 8>());
   }
-  // sort keys: query number << pbits | text position (32 bits where the
-  // tables are 32 bits wide: the layout of rounds 1 and 2)
-  const uint32_t pbits = sizeof(IDX) == 4 ? 32u : bitsfor(index->n);
-  if (queries->nq >= 0xFFFFFFFFull || pbits + bitsfor(queries->nq) > 64)
+}
+
+// fn(K): K = std::integral_constant<int, maxk>, the band of the alignment
+// (1 .. VSA_APM_BANDK)
+template <typename Fn>
+void withband(uint32_t maxk, Fn &&fn)
+{
+  switch (maxk)
+  {
+  case 1: return fn(std::integral_constant<int, 1>());
+  case 2: return fn(std::integral_constant<int, 2>());
+  default: return fn(std::integral_constant<int, 3>());
+  }
+}
+
+// sort keys: query number << pbits | text position (32 bits where the
+// tables are 32 bits wide: the layout of rounds 1 and 2)
+template <typename IDX>
+int apm_positionbits(const vsa_index *index, const vsa_queries *queries,
+                     uint64_t maxqueries, uint32_t *pbits)
+{
+  *pbits = sizeof(IDX) == 4 ? 32u : bitsfor(index->n);
+  if (queries->nq >= maxqueries || *pbits + bitsfor(queries->nq) > 64)
   {
     VSA_ERROR("approximate search: a batch of %lu reads on a text of %lu "
               "symbols is not covered by the GPU engine",
               (unsigned long) queries->nq, (unsigned long) index->n);
     return VSA_NOT_COVERED;
   }
-  uint32_t hflag = 0;
-  if (dflag.alloc(4))
+  return 0;
+}
+
+// The plan of a batch on the device and the pieces its queries are cut into.
+struct ApmPieces
+{
+  DevBuf k, splitlen, piecebase;     // per query; piecebase has nq + 1 entries
+  DevBuf start, len, query, poffset; // per piece
+  int alloc(uint64_t nq, uint64_t npieces)
   {
-    return -100;
+    return (k.alloc(nq * 4) || splitlen.alloc(nq * 4) ||
+            piecebase.alloc((nq + 1) * 8) || start.alloc(npieces * 8) ||
+            len.alloc(npieces * 8) || query.alloc(npieces * 4) ||
+            poffset.alloc(npieces * 4))
+               ? -100
+               : 0;
   }
-  VSA_HIP(hipMemsetAsync(dflag.p, 0, 4, stream));
-  k_apm_anyspecial<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-      qs, nq, dflag.as<uint32_t>());
-  VSA_HIP(hipMemcpyAsync(&hflag, dflag.p, 4, hipMemcpyDeviceToHost, stream));
-  VSA_HIP(hipStreamSynchronize(stream));
-  if (!doedist && hflag != 0)
+  // the plan arrays from vectors with an entry per query
+  int upload(const std::vector<uint32_t> &hk,
+             const std::vector<uint32_t> &hsplitlen,
+             const std::vector<uint64_t> &hpiecebase, uint64_t nq,
+             hipStream_t stream)
   {
-    VSA_ERROR("Hamming distance search with special symbols in a query is "
-              "not covered by the GPU engine");
-    return VSA_NOT_COVERED;
+    VSA_HIP(hipMemcpyAsync(k.p, hk.data(), nq * 4, hipMemcpyHostToDevice,
+                           stream));
+    VSA_HIP(hipMemcpyAsync(splitlen.p, hsplitlen.data(), nq * 4,
+                           hipMemcpyHostToDevice, stream));
+    VSA_HIP(hipMemcpyAsync(piecebase.p, hpiecebase.data(), (nq + 1) * 8,
+                           hipMemcpyHostToDevice, stream));
+    return 0;
   }
-  // edit distance: start positions by banded alignment unless a query holds
-  // a wildcard (the region scan compares raw bytes for m > 32, so that the
-  // two ways could then differ) or a threshold exceeds the band
-  uint32_t maxk = plan.uniform ? plan.uk : 0;
-  if (plan.bylength)
+  // the pieces from the plan arrays
+  int cut(const DevQueries &qs, uint64_t nq, hipStream_t stream)
   {
-    maxk = *std::max_element(plan.tk.begin(), plan.tk.end());
+    k_apm_pieces<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
+        qs, nq, splitlen.as<uint32_t>(), piecebase.as<uint64_t>(),
+        start.as<uint64_t>(), len.as<uint64_t>(), query.as<uint32_t>(),
+        poffset.as<uint32_t>());
+    VSA_HIP(hipGetLastError());
+    return 0;
   }
-  for (uint64_t q = 0; q < nq && !plan.uniform && !plan.bylength; q++)
-  {
-    maxk = std::max(maxk, plan.k[q]);
-  }
-  const char *nofast = getenv("VSA_APM_SCAN");
-  const bool banded = doedist && hflag == 0 && maxk <= VSA_APM_BANDK &&
-                      !(nofast != nullptr && strcmp(nofast, "1") == 0);
-  if (dk.alloc(nq * 4) || dsplitlen.alloc(nq * 4) ||
-      dpiecebase.alloc((nq + 1) * 8) || pstart.alloc(npieces * 8) ||
-      plen.alloc(npieces * 8) || pquery.alloc(npieces * 4) ||
-      ppoffset.alloc(npieces * 4) || left.alloc(npieces * 8) ||
-      count.alloc((npieces + 1) * 8) || offsets.alloc((npieces + 1) * 8))
-  {
-    return -100;
-  }
-  Timer tband(stream);
-  tall.start();
+};
+
+// the plan arrays of an ApmPlan, in the way the plan was made, and the pieces
+static int apm_pieces(const ApmPlan &plan, const DevQueries &qs, uint64_t nq,
+                      hipStream_t stream, ApmPieces &pc)
+{
   if (plan.bylength)
   {
     const size_t tn = plan.tk.size();
-    DevBuf dtk, dtsplit, dtpieces, dpieces, ptemp;
+    DevBuf dtk, dtsplit, dtpieces, dpieces;
+    uint64_t npieces = 0;
     if (dtk.alloc(tn * 4) || dtsplit.alloc(tn * 4) || dtpieces.alloc(tn * 4) ||
         dpieces.alloc((nq + 1) * 8))
     {
@@ -1151,330 +1161,426 @@ int run_approx(const vsa_index *index, const vsa_queries *queries,
                            hipMemcpyHostToDevice, stream));
     k_apm_filltable<<<gridfor(nq + 1), VSA_BLOCK, 0, stream>>>(
         qs.length, nq, dtk.as<uint32_t>(), dtsplit.as<uint32_t>(),
-        dtpieces.as<uint32_t>(), dk.as<uint32_t>(), dsplitlen.as<uint32_t>(),
-        dpieces.as<uint64_t>());
+        dtpieces.as<uint32_t>(), pc.k.as<uint32_t>(),
+        pc.splitlen.as<uint32_t>(), dpieces.as<uint64_t>());
     VSA_HIP(hipGetLastError());
-    size_t ptb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, ptb, dpieces.as<uint64_t>(),
-                                    dpiecebase.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (nq + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    if (ptemp.alloc(ptb))
+    // (synchronises: the tables are host vectors of this call, and the copies
+    // are done before they can go away)
+    if (exclusive_sum(dpieces.as<uint64_t>(), pc.piecebase.as<uint64_t>(), nq,
+                      stream, &npieces))
     {
       return -100;
     }
-    VSA_HIP(rocprim::exclusive_scan(ptemp.p, ptb, dpieces.as<uint64_t>(),
-                                    dpiecebase.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (nq + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    // the tables are host vectors of this call: the copies must be done
-    // before they can go away (they do not, but keep it simple)
-    VSA_HIP(hipStreamSynchronize(stream));
   } else if (plan.uniform)
   {
     k_apm_fillplan<<<gridfor(nq + 1), VSA_BLOCK, 0, stream>>>(
-        dk.as<uint32_t>(), dsplitlen.as<uint32_t>(),
-        dpiecebase.as<uint64_t>(), nq, plan.uk, plan.usplitlen, plan.upieces);
+        pc.k.as<uint32_t>(), pc.splitlen.as<uint32_t>(),
+        pc.piecebase.as<uint64_t>(), nq, plan.uk, plan.usplitlen,
+        plan.upieces);
     VSA_HIP(hipGetLastError());
-  } else
+  } else if (pc.upload(plan.k, plan.splitlen, plan.piecebase, nq, stream))
   {
-    VSA_HIP(hipMemcpyAsync(dk.p, plan.k.data(), nq * 4,
-                           hipMemcpyHostToDevice, stream));
-    VSA_HIP(hipMemcpyAsync(dsplitlen.p, plan.splitlen.data(), nq * 4,
-                           hipMemcpyHostToDevice, stream));
-    VSA_HIP(hipMemcpyAsync(dpiecebase.p, plan.piecebase.data(),
-                           (nq + 1) * 8, hipMemcpyHostToDevice, stream));
+    return -100;
   }
-  k_apm_pieces<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-      qs, nq, dsplitlen.as<uint32_t>(), dpiecebase.as<uint64_t>(),
-      pstart.as<uint64_t>(), plen.as<uint64_t>(), pquery.as<uint32_t>(),
-      ppoffset.as<uint32_t>());
-  VSA_HIP(hipGetLastError());
-  // A1: exact search of every piece = the K1 kernel on a batch of pieces
+  return pc.cut(qs, nq, stream);
+}
+
+// A1: exact search of every piece = the K1 kernel on a batch of pieces;
+// left[p], count[p] = the suffix array interval of piece p
+template <typename IDX>
+int apm_searchpieces(const DevIndex<IDX> &ix, const DevQueries &qs,
+                     ApmPieces &pc, uint64_t npieces, Timer &tsearch,
+                     hipStream_t stream, uint64_t *left, uint64_t *count)
+{
   DevQueries ps = qs;
-  ps.start = pstart.as<uint64_t>();
-  ps.length = plen.as<uint64_t>();
+  ps.start = pc.start.as<uint64_t>();
+  ps.length = pc.len.as<uint64_t>();
   ps.nq = npieces;
   ps.uniformlen = 0;
   ps.dense = 0;
-  VSA_HIP(hipMemsetAsync(count.as<uint64_t>() + npieces, 0, 8, stream));
+  VSA_HIP(hipMemsetAsync(count + npieces, 0, 8, stream));
   tsearch.start();
   if constexpr (sizeof(IDX) == 4)
   {
     if (ix.esa8 != nullptr)
     {
       k_complete_search<IDX, true><<<gridfor(npieces), VSA_BLOCK, 0, stream>>>(
-          ix, ps, npieces, left.as<uint64_t>(), count.as<uint64_t>());
+          ix, ps, npieces, left, count);
     } else
     {
       k_complete_search<IDX, false>
-          <<<gridfor(npieces), VSA_BLOCK, 0, stream>>>(
-              ix, ps, npieces, left.as<uint64_t>(), count.as<uint64_t>());
+          <<<gridfor(npieces), VSA_BLOCK, 0, stream>>>(ix, ps, npieces, left,
+                                                       count);
     }
   } else
   {
     k_complete_search<IDX, false><<<gridfor(npieces), VSA_BLOCK, 0, stream>>>(
-        ix, ps, npieces, left.as<uint64_t>(), count.as<uint64_t>());
+        ix, ps, npieces, left, count);
   }
   tsearch.stop();
   VSA_HIP(hipGetLastError());
-  if (apm_exclusive_sum(count.as<uint64_t>(), offsets.as<uint64_t>(), npieces,
-                        stream, &total))
+  return 0;
+}
+
+// What the pieces of a batch have hit: source i (a piece; an interval of the
+// tree search in approx_tree.inc) stands for the suffixes left[i],
+// left[i] + 1, .. of the suffix array, offsets[i + 1] - offsets[i] of them,
+// found for query[i] at offset poffset[i] of its pattern.
+struct ApmHits
+{
+  const uint64_t *left, *offsets;
+  const uint32_t *query, *poffset;
+  uint64_t nsources, total; // total = offsets[nsources], > 0
+};
+
+// A2: the regions of the text that have to be verified, one stretch per hit,
+// merged where they overlap, in the order (query, left end).
+struct ApmRegions
+{
+  uint64_t n = 0;
+  uint32_t pbits;      // sort keys: query << pbits | text position
+  DevBuf rq, rlo, rhi; // per region: its query, its first and last position
+  DevBuf rfirst;       // n + 1: the first hit of a region in keys
+  DevBuf keys;         // the keys of the hits, sorted
+};
+
+// segments: the sources of query q are segments[q] .. segments[q + 1] - 1, so
+// that the hits can be sorted inside the queries (radix sort of the whole list
+// only if a query has too many); nullptr: radix sort
+template <typename IDX>
+int apm_regions(const DevIndex<IDX> &ix, const DevQueries &qs, uint64_t nq,
+                const ApmHits &hits, const uint32_t *dk, bool doedist,
+                const uint64_t *segments, hipStream_t stream, ApmRegions &rg)
+{
+  const uint64_t total = hits.total;
+  const uint32_t pbits = rg.pbits;
+  DevBuf keys, his, his2, ends, prev, flags, rank, temp;
+  if (keys.alloc(total * 8) || rg.keys.alloc(total * 8) ||
+      his.alloc(total * sizeof(IDX)) || his2.alloc(total * sizeof(IDX)) ||
+      ends.alloc(total * 8) || prev.alloc(total * 8) ||
+      flags.alloc(total * 4) || rank.alloc(total * 4))
+  {
+    return -100;
+  }
+  k_apm_regions<IDX, IDX><<<gridfor(hits.nsources), VSA_BLOCK, 0, stream>>>(
+      ix, qs, hits.nsources, hits.left, hits.offsets, total, hits.query,
+      hits.poffset, dk, doedist, pbits, keys.as<uint64_t>(), his.as<IDX>());
+  VSA_HIP(hipGetLastError());
+  // sorted by (query, left end): inside the queries where that will do
+  uint64_t bigsegment = 1;
+  if (segments != nullptr)
+  {
+    // (the first word of flags, not yet in use, says whether it did)
+    VSA_HIP(hipMemsetAsync(flags.p, 0, 4, stream));
+    k_apm_sortsegments<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
+        segments, hits.offsets, nq, keys.as<uint64_t>(), his.as<IDX>(),
+        flags.as<unsigned int>());
+    VSA_HIP(hipGetLastError());
+    const Fetch f = {flags.p, 4};
+    if (fetchwords(stream, &f, 1, &bigsegment))
+    {
+      return -100;
+    }
+  }
+  if (bigsegment != 0)
+  {
+    const unsigned int endbit = pbits + bitsfor(nq);
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(
+          p, tb, keys.as<uint64_t>(), rg.keys.as<uint64_t>(), his.as<IDX>(),
+          his2.as<IDX>(), (size_t) total, 0u, endbit, stream);
+    }));
+  } else
+  {
+    // in place: the sorted list is the input list
+    std::swap(keys.p, rg.keys.p);
+    std::swap(his.p, his2.p);
+  }
+  // running maximum of the right ends: a hit that starts behind it starts a
+  // new region
+  k_apm_rightends<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
+      rg.keys.as<uint64_t>(), his2.as<IDX>(), total, pbits,
+      ends.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, ends.as<uint64_t>(),
+                                   prev.as<uint64_t>(), (uint64_t) 0,
+                                   (size_t) total, MaxU64(), stream);
+  }));
+  k_apm_flags<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
+      rg.keys.as<uint64_t>(), prev.as<uint64_t>(), total, pbits,
+      flags.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::inclusive_scan(p, tb, flags.as<uint32_t>(),
+                                   rank.as<uint32_t>(), (size_t) total,
+                                   rocprim::plus<uint32_t>(), stream);
+  }));
+  uint32_t hlast = 0;
+  VSA_HIP(hipMemcpyAsync(&hlast, rank.as<uint32_t>() + total - 1, 4,
+                         hipMemcpyDeviceToHost, stream));
+  VSA_HIP(hipStreamSynchronize(stream));
+  rg.n = hlast;
+  if (rg.rq.alloc(rg.n * 4) || rg.rlo.alloc(rg.n * sizeof(IDX)) ||
+      rg.rhi.alloc(rg.n * sizeof(IDX)) || rg.rfirst.alloc((rg.n + 1) * 4))
+  {
+    return -100;
+  }
+  k_apm_writeregions<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
+      rg.keys.as<uint64_t>(), ends.as<uint64_t>(), prev.as<uint64_t>(),
+      flags.as<uint32_t>(), rank.as<uint32_t>(), total, pbits,
+      rg.rq.as<uint32_t>(), rg.rlo.as<IDX>(), rg.rhi.as<IDX>(),
+      rg.rfirst.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  return 0;
+}
+
+// the longest match at each of n start positions (hitpos, in region
+// hitregion): one record per position
+template <typename IDX>
+int apm_longest(const uint8_t *tis, const DevQueries &qs, const uint32_t *dk,
+                int words, uint64_t n, const IDX *hitpos,
+                const uint32_t *hitregion, const uint32_t *rq, const IDX *rlo,
+                const IDX *rhi, vsa_match *out, hipStream_t stream)
+{
+  withwords(words, [&](auto w) {
+    k_apm_longest<decltype(w)::value><<<gridfor(n), VSA_BLOCK, 0, stream>>>(
+        tis, qs, dk, n, hitpos, hitregion, rq, rlo, rhi, out);
+  });
+  VSA_HIP(hipGetLastError());
+  return 0;
+}
+
+// A3: verification of the regions, count pass then write pass; matches (empty
+// on entry; allocated if *nhits > 0) = the matches, in the order of the regions
+template <typename IDX>
+int apm_verify(const uint8_t *tis, const DevQueries &qs, const uint32_t *dk,
+               int words, bool doedist, ApmRegions &rg, hipStream_t stream,
+               DevBuf &matches, uint64_t *nhits)
+{
+  const uint64_t nregions = rg.n;
+  DevBuf rcount, roffsets, hitpos, hitregion;
+  if (rcount.alloc((nregions + 1) * 8) || roffsets.alloc((nregions + 1) * 8))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemsetAsync(rcount.as<uint64_t>() + nregions, 0, 8, stream));
+  auto pass = [&](auto count) {
+    constexpr bool COUNT = decltype(count)::value;
+    if (doedist)
+    {
+      withwords(words, [&](auto w) {
+        k_apm_verify_edist<decltype(w)::value, COUNT>
+            <<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
+                tis, qs, dk, nregions, rg.rq.as<uint32_t>(),
+                rg.rlo.as<IDX>(), rg.rhi.as<IDX>(), rcount.as<uint64_t>(),
+                roffsets.as<uint64_t>(), hitpos.as<IDX>(),
+                hitregion.as<uint32_t>());
+      });
+    } else
+    {
+      k_apm_verify_hamming<COUNT><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
+          tis, qs, dk, nregions, rg.rq.as<uint32_t>(), rg.rlo.as<IDX>(),
+          rg.rhi.as<IDX>(), rcount.as<uint64_t>(), roffsets.as<uint64_t>(),
+          matches.as<vsa_match>());
+    }
+    return hipGetLastError();
+  };
+  VSA_HIP(pass(std::true_type()));
+  if (exclusive_sum(rcount.as<uint64_t>(), roffsets.as<uint64_t>(), nregions,
+                    stream, nhits))
+  {
+    return -100;
+  }
+  if (*nhits == 0)
+  {
+    return 0;
+  }
+  if (matches.alloc(*nhits * sizeof(vsa_match)) ||
+      (doedist && (hitpos.alloc(*nhits * sizeof(IDX)) ||
+                   hitregion.alloc(*nhits * 4))))
+  {
+    return -100;
+  }
+  VSA_HIP(pass(std::false_type()));
+  // edit distance: the write pass gave the start positions
+  return doedist ? apm_longest<IDX>(tis, qs, dk, words, *nhits,
+                                    hitpos.as<IDX>(),
+                                    hitregion.as<uint32_t>(),
+                                    rg.rq.as<uint32_t>(), rg.rlo.as<IDX>(),
+                                    rg.rhi.as<IDX>(),
+                                    matches.as<vsa_match>(), stream)
+                 : 0;
+}
+
+// A3 for edit distance with thresholds up to VSA_APM_BANDK: the start
+// positions the hits allow (count pass, write pass), a banded alignment at
+// each of them (tband; *naligned = how many), and the ones it accepts
+template <typename IDX>
+int apm_banded(const DevIndex<IDX> &ix, const DevQueries &qs,
+               const uint32_t *dk, uint32_t maxk, ApmRegions &rg,
+               Timer &tband, hipStream_t stream, DevBuf &matches,
+               uint64_t *nhits, uint64_t *naligned)
+{
+  const uint64_t nregions = rg.n;
+  DevBuf rcount, roffsets, hitpos, hitregion, cand, keep, dcount;
+  uint64_t ncand = 0;
+  if (rcount.alloc((nregions + 1) * 8) || roffsets.alloc((nregions + 1) * 8))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemsetAsync(rcount.as<uint64_t>() + nregions, 0, 8, stream));
+  k_apm_candidates<true, IDX><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
+      rg.keys.as<uint64_t>(), rg.pbits, dk, nregions, rg.rq.as<uint32_t>(),
+      rg.rfirst.as<uint32_t>(), rcount.as<uint64_t>(),
+      roffsets.as<uint64_t>(), nullptr, nullptr);
+  VSA_HIP(hipGetLastError());
+  if (exclusive_sum(rcount.as<uint64_t>(), roffsets.as<uint64_t>(), nregions,
+                    stream, &ncand))
+  {
+    return -100;
+  }
+  if (ncand >= 0xFFFFFFFFull)
+  {
+    VSA_ERROR("approximate search: more than 2^32 start positions");
+    return -5;
+  }
+  if (hitpos.alloc(ncand * sizeof(IDX)) || hitregion.alloc(ncand * 4) ||
+      cand.alloc(ncand * sizeof(vsa_match)) || keep.alloc(ncand) ||
+      matches.alloc(ncand * sizeof(vsa_match)) || dcount.alloc(8))
+  {
+    return -100;
+  }
+  k_apm_candidates<false, IDX><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
+      rg.keys.as<uint64_t>(), rg.pbits, dk, nregions, rg.rq.as<uint32_t>(),
+      rg.rfirst.as<uint32_t>(), rcount.as<uint64_t>(),
+      roffsets.as<uint64_t>(), hitpos.as<IDX>(), hitregion.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  tband.start();
+  withband(maxk, [&](auto band) {
+    k_apm_banded<decltype(band)::value>
+        <<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+            ix.tis, ix.n, qs, dk, ncand, hitpos.as<IDX>(),
+            hitregion.as<uint32_t>(), rg.rq.as<uint32_t>(), rg.rlo.as<IDX>(),
+            rg.rhi.as<IDX>(), cand.as<vsa_match>(), keep.as<uint8_t>());
+  });
+  tband.stop();
+  *naligned = ncand;
+  VSA_HIP(hipGetLastError());
+  if (compact_matches(cand.as<vsa_match>(), keep.as<uint8_t>(), ncand,
+                      matches.as<vsa_match>(), dcount.as<uint64_t>(), stream))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemcpyAsync(nhits, dcount.p, 8, hipMemcpyDeviceToHost, stream));
+  VSA_HIP(hipStreamSynchronize(stream));
+  return 0;
+}
+
+// does a query hold a special symbol (a wildcard)?
+static int apm_anyspecial(const DevQueries &qs, uint64_t nq,
+                          hipStream_t stream, uint32_t *any)
+{
+  DevBuf dflag;
+  if (dflag.alloc(4))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemsetAsync(dflag.p, 0, 4, stream));
+  k_apm_anyspecial<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
+      qs, nq, dflag.as<uint32_t>());
+  VSA_HIP(hipMemcpyAsync(any, dflag.p, 4, hipMemcpyDeviceToHost, stream));
+  VSA_HIP(hipStreamSynchronize(stream));
+  return 0;
+}
+
+template <typename IDX>
+int run_approx(const vsa_index *index, const vsa_queries *queries,
+               bool doedist, const ApmPlan &plan, vsa_result *res)
+{
+  hipStream_t stream = index->stream;
+  vsa_dev_set_stream(stream);
+  Timer tall(stream), tsearch(stream), tband(stream);
+  const DevIndex<IDX> ix = index->view<IDX>();
+  const DevQueries qs = devqueries(queries);
+  const uint64_t nq = plan.qlimit, npieces = plan.npieces(nq);
+  ApmPieces pc;
+  ApmRegions rg;
+  DevBuf left, count, offsets, matches;
+  uint64_t total = 0, nhits = 0;
+  uint32_t special = 0;
+  int rc;
+
+  res->stats.searches = npieces;
+  if (nq == 0 || npieces == 0)
+  {
+    return 0;
+  }
+  if ((rc = apm_positionbits<IDX>(index, queries, 0xFFFFFFFFull,
+                                  &rg.pbits)) != 0 ||
+      (rc = apm_anyspecial(qs, nq, stream, &special)) != 0)
+  {
+    return rc;
+  }
+  if (!doedist && special != 0)
+  {
+    VSA_ERROR("Hamming distance search with special symbols in a query is "
+              "not covered by the GPU engine");
+    return VSA_NOT_COVERED;
+  }
+  // edit distance: start positions by banded alignment unless a query holds
+  // a wildcard (the region scan compares raw bytes for m > 32, so that the
+  // two ways could then differ) or a threshold exceeds the band
+  const uint32_t maxk = plan.maxk(nq);
+  const char *nofast = getenv("VSA_APM_SCAN");
+  const bool banded = doedist && special == 0 && maxk <= VSA_APM_BANDK &&
+                      !(nofast != nullptr && strcmp(nofast, "1") == 0);
+  if (pc.alloc(nq, npieces) || left.alloc(npieces * 8) ||
+      count.alloc((npieces + 1) * 8) || offsets.alloc((npieces + 1) * 8))
+  {
+    return -100;
+  }
+  tall.start();
+  if ((rc = apm_pieces(plan, qs, nq, stream, pc)) != 0 ||
+      (rc = apm_searchpieces<IDX>(ix, qs, pc, npieces, tsearch, stream,
+                                  left.as<uint64_t>(),
+                                  count.as<uint64_t>())) != 0)
+  {
+    return rc;
+  }
+  if (exclusive_sum(count.as<uint64_t>(), offsets.as<uint64_t>(), npieces,
+                    stream, &total))
   {
     return -100;
   }
   res->stats.candidates = total;
+  if (total >= 0xFFFFFFFFull)
+  {
+    VSA_ERROR("approximate search: more than 2^32 piece hits");
+    return -5;
+  }
   if (total > 0)
   {
-    if (total >= 0xFFFFFFFFull)
+    const ApmHits hits = {left.as<uint64_t>(), offsets.as<uint64_t>(),
+                          pc.query.as<uint32_t>(), pc.poffset.as<uint32_t>(),
+                          npieces, total};
+    if ((rc = apm_regions<IDX>(ix, qs, nq, hits, pc.k.as<uint32_t>(), doedist,
+                               pc.piecebase.as<uint64_t>(), stream, rg)) != 0)
     {
-      VSA_ERROR("approximate search: more than 2^32 piece hits");
-      return -5;
+      return rc;
     }
-    // A2: regions, sorted by (query, left end), merged
-    if (keys.alloc(total * 8) || keys2.alloc(total * 8) ||
-        his.alloc(total * sizeof(IDX)) || his2.alloc(total * sizeof(IDX)) ||
-        ends.alloc(total * 8) || prev.alloc(total * 8) ||
-        flags.alloc(total * 4) || rank.alloc(total * 4))
+    rc = banded ? apm_banded<IDX>(ix, qs, pc.k.as<uint32_t>(), maxk, rg, tband,
+                                  stream, matches, &nhits,
+                                  &res->stats.kernel_searches)
+                : apm_verify<IDX>(ix.tis, qs, pc.k.as<uint32_t>(),
+                                  (int) ((plan.maxm + 63) / 64), doedist, rg,
+                                  stream, matches, &nhits);
+    if (rc != 0)
     {
-      return -100;
+      return rc;
     }
-    k_apm_regions<IDX, IDX><<<gridfor(npieces), VSA_BLOCK, 0, stream>>>(
-        ix, qs, npieces, left.as<uint64_t>(), offsets.as<uint64_t>(), total,
-        pquery.as<uint32_t>(), ppoffset.as<uint32_t>(), dk.as<uint32_t>(),
-        doedist, pbits, keys.as<uint64_t>(), his.as<IDX>());
-    VSA_HIP(hipGetLastError());
-    // sorted by (query, left end): inside the queries where that will do
-    uint64_t bigsegment = 0;
-    {
-      VSA_HIP(hipMemsetAsync(dflag.p, 0, 4, stream));
-      k_apm_sortsegments<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-          dpiecebase.as<uint64_t>(), offsets.as<uint64_t>(), nq,
-          keys.as<uint64_t>(), his.as<IDX>(), dflag.as<unsigned int>());
-      VSA_HIP(hipGetLastError());
-      const Fetch f = {dflag.p, 4};
-      if (fetchwords(stream, &f, 1, &bigsegment))
-      {
-        return -100;
-      }
-    }
-    if (bigsegment != 0)
-    {
-      const unsigned int endbit = pbits + bitsfor(nq);
-      tb = 0;
-      VSA_HIP(rocprim::radix_sort_pairs(
-          nullptr, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-          his.as<IDX>(), his2.as<IDX>(), (size_t) total, 0u, endbit, stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::radix_sort_pairs(
-          temp.p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-          his.as<IDX>(), his2.as<IDX>(), (size_t) total, 0u, endbit, stream));
-    } else
-    {
-      // in place: the sorted list is the input list
-      std::swap(keys.p, keys2.p);
-      std::swap(his.p, his2.p);
-    }
-    k_apm_rightends<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), his2.as<IDX>(), total, pbits,
-        ends.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, ends.as<uint64_t>(),
-                                    prev.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) total, MaxU64(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, ends.as<uint64_t>(),
-                                    prev.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) total, MaxU64(), stream));
-    k_apm_flags<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), prev.as<uint64_t>(), total, pbits,
-        flags.as<uint32_t>());
-    VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::inclusive_scan(nullptr, tb, flags.as<uint32_t>(),
-                                    rank.as<uint32_t>(), (size_t) total,
-                                    rocprim::plus<uint32_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::inclusive_scan(temp.p, tb, flags.as<uint32_t>(),
-                                    rank.as<uint32_t>(), (size_t) total,
-                                    rocprim::plus<uint32_t>(), stream));
-    uint32_t hlast = 0;
-    VSA_HIP(hipMemcpyAsync(&hlast, rank.as<uint32_t>() + total - 1, 4,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipStreamSynchronize(stream));
-    nregions = hlast;
-    if (rq.alloc(nregions * 4) || rlo.alloc(nregions * sizeof(IDX)) ||
-        rhi.alloc(nregions * sizeof(IDX)) ||
-        rfirst.alloc((nregions + 1) * 4) ||
-        rcount.alloc((nregions + 1) * 8) ||
-        roffsets.alloc((nregions + 1) * 8))
-    {
-      return -100;
-    }
-    k_apm_writeregions<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), ends.as<uint64_t>(), prev.as<uint64_t>(),
-        flags.as<uint32_t>(), rank.as<uint32_t>(), total, pbits,
-        rq.as<uint32_t>(), rlo.as<IDX>(), rhi.as<IDX>(),
-        rfirst.as<uint32_t>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(hipMemsetAsync(rcount.as<uint64_t>() + nregions, 0, 8, stream));
-    // A3: verification, count pass then write pass
-    const uint8_t *tis = ix.tis;
-    const int words = (int) ((plan.maxm + 63) / 64);
-#define APM_VERIFY(W, COUNT)                                                  \
-  k_apm_verify_edist<W, COUNT><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(  \
-      tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),                \
-      rlo.as<IDX>(), rhi.as<IDX>(), rcount.as<uint64_t>(),                    \
-      roffsets.as<uint64_t>(), hitpos.as<IDX>(),                              \
-      hitregion.as<uint32_t>())
-#define APM_VERIFY_W(COUNT)                                                   \
-  switch (words)                                                              \
-  {                                                                           \
-    case 1: APM_VERIFY(1, COUNT); break;                                      \
-    case 2: APM_VERIFY(2, COUNT); break;                                      \
-    case 3: APM_VERIFY(3, COUNT); break;                                      \
-    case 4: APM_VERIFY(4, COUNT); break;                                      \
-    case 5: APM_VERIFY(5, COUNT); break;                                      \
-    case 6: APM_VERIFY(6, COUNT); break;                                      \
-    case 7: APM_VERIFY(7, COUNT); break;                                      \
-    default: APM_VERIFY(8, COUNT); break;                                     \
   }
-    if (banded)
-    {
-      uint64_t ncand = 0;
-      k_apm_candidates<true, IDX>
-          <<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-              keys2.as<uint64_t>(), pbits, dk.as<uint32_t>(), nregions,
-              rq.as<uint32_t>(), rfirst.as<uint32_t>(),
-              rcount.as<uint64_t>(), roffsets.as<uint64_t>(), nullptr,
-              nullptr);
-      VSA_HIP(hipGetLastError());
-      if (apm_exclusive_sum(rcount.as<uint64_t>(), roffsets.as<uint64_t>(),
-                            nregions, stream, &ncand))
-      {
-        return -100;
-      }
-      if (ncand >= 0xFFFFFFFFull)
-      {
-        VSA_ERROR("approximate search: more than 2^32 start positions");
-        return -5;
-      }
-      if (hitpos.alloc(ncand * sizeof(IDX)) || hitregion.alloc(ncand * 4) ||
-          cand.alloc(ncand * sizeof(vsa_match)) || keep.alloc(ncand) ||
-          matches.alloc(ncand * sizeof(vsa_match)) || dcount.alloc(8))
-      {
-        return -100;
-      }
-      k_apm_candidates<false, IDX>
-          <<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-              keys2.as<uint64_t>(), pbits, dk.as<uint32_t>(), nregions,
-              rq.as<uint32_t>(), rfirst.as<uint32_t>(),
-              rcount.as<uint64_t>(), roffsets.as<uint64_t>(),
-              hitpos.as<IDX>(), hitregion.as<uint32_t>());
-      VSA_HIP(hipGetLastError());
-#define APM_BANDED(KK)                                                        \
-  k_apm_banded<KK><<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(                 \
-      tis, ix.n, qs, dk.as<uint32_t>(), ncand, hitpos.as<IDX>(),              \
-      hitregion.as<uint32_t>(), rq.as<uint32_t>(), rlo.as<IDX>(),             \
-      rhi.as<IDX>(), cand.as<vsa_match>(), keep.as<uint8_t>())
-      tband.start();
-      switch (maxk)
-      {
-        case 1: APM_BANDED(1); break;
-        case 2: APM_BANDED(2); break;
-        default: APM_BANDED(3); break;
-      }
-      tband.stop();
-      res->stats.kernel_searches = ncand; // start positions aligned
-#undef APM_BANDED
-      VSA_HIP(hipGetLastError());
-      if (compact_matches(cand.as<vsa_match>(), keep.as<uint8_t>(), ncand,
-                          matches.as<vsa_match>(), dcount.as<uint64_t>(),
-                          stream))
-      {
-        return -100;
-      }
-      VSA_HIP(hipMemcpyAsync(&nhits, dcount.p, 8, hipMemcpyDeviceToHost,
-                             stream));
-      VSA_HIP(hipStreamSynchronize(stream));
-    } else if (doedist)
-    {
-      APM_VERIFY_W(true);
-    } else
-    {
-      k_apm_verify_hamming<true><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-          tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),
-          rlo.as<IDX>(), rhi.as<IDX>(), rcount.as<uint64_t>(),
-          roffsets.as<uint64_t>(), nullptr);
-    }
-    VSA_HIP(hipGetLastError());
-    if (!banded && apm_exclusive_sum(rcount.as<uint64_t>(),
-                                     roffsets.as<uint64_t>(), nregions,
-                                     stream, &nhits))
-    {
-      return -100;
-    }
-    if (!banded && nhits > 0)
-    {
-      if (matches.alloc(nhits * sizeof(vsa_match)))
-      {
-        return -100;
-      }
-      if (doedist)
-      {
-        if (hitpos.alloc(nhits * sizeof(IDX)) || hitregion.alloc(nhits * 4))
-        {
-          return -100;
-        }
-        APM_VERIFY_W(false);
-        VSA_HIP(hipGetLastError());
-#define APM_LONGEST(W)                                                        \
-  k_apm_longest<W><<<gridfor(nhits), VSA_BLOCK, 0, stream>>>(                 \
-      tis, qs, dk.as<uint32_t>(), nhits, hitpos.as<IDX>(),                    \
-      hitregion.as<uint32_t>(), rq.as<uint32_t>(), rlo.as<IDX>(),             \
-      rhi.as<IDX>(), matches.as<vsa_match>())
-        switch (words)
-        {
-          case 1: APM_LONGEST(1); break;
-          case 2: APM_LONGEST(2); break;
-          case 3: APM_LONGEST(3); break;
-          case 4: APM_LONGEST(4); break;
-          case 5: APM_LONGEST(5); break;
-          case 6: APM_LONGEST(6); break;
-          case 7: APM_LONGEST(7); break;
-          default: APM_LONGEST(8); break;
-        }
-#undef APM_LONGEST
-      } else
-      {
-        k_apm_verify_hamming<false>
-            <<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-                tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),
-                rlo.as<IDX>(), rhi.as<IDX>(), rcount.as<uint64_t>(),
-                roffsets.as<uint64_t>(), matches.as<vsa_match>());
-      }
-      VSA_HIP(hipGetLastError());
-    }
-#undef APM_VERIFY_W
-#undef APM_VERIFY
-  }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = nhits;
-  res->matches = (vsa_match *) matches.release();
-  res->stats.count = nhits;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
+  rc = finish(res, matches, nhits, tall, tsearch, stream);
   res->stats.first_kernel_ms = tband.ms(); // the banded alignment (K <= 3)
-  return sumlengths(res->matches, nhits, stream, &res->stats.sumlength);
+  return rc;
 }

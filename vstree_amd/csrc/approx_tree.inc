@@ -480,6 +480,165 @@ static int apm_treeplan(const vsa_index *index, const vsa_queries *queries,
   return 0;
 }
 
+// T1: what the tree search has found.  Interval i = the suffixes left[i] ..
+// left[i] + count[i] - 1 of the suffix array, reported with value[i]
+// (mismatches) for query[i], piece offset poffset[i].  The intervals of cut
+// patterns feed the regions (poffsets: where their hits stand in that list,
+// `total` hits), the ones of uncut patterns the output (doffsets, `ndirect`).
+struct TreeIntervals
+{
+  uint64_t n = 0, total = 0, ndirect = 0;
+  DevBuf mode, counts, offsets; // per query; per piece (+ 1)
+  DevBuf left, count, value, query, poffset, poffsets, doffsets;
+  int alloc(uint64_t nq, uint64_t npieces)
+  {
+    return (mode.alloc(nq * 4) || counts.alloc((npieces + 1) * 8) ||
+            offsets.alloc((npieces + 1) * 8))
+               ? -100
+               : 0;
+  }
+};
+
+// the lcp-interval tree, count pass then write pass (tsearch), and the split
+// of the intervals into the two kinds
+template <typename IDX>
+int apm_treesearch(const DevIndex<IDX> &ix, const DevQueries &qs,
+                   ApmPieces &pc, const std::vector<uint32_t> &mode,
+                   uint64_t nq, uint64_t npieces, bool doedist,
+                   Timer &tsearch, hipStream_t stream, TreeIntervals &iv)
+{
+  DevBuf pcount, dcount;
+  const unsigned int tgrid = (unsigned int) ((npieces + 63) / 64);
+  auto pass = [&](auto edit, auto write) {
+    k_apm_tree<IDX, decltype(edit)::value, decltype(write)::value>
+        <<<tgrid, 64, 0, stream>>>(
+            ix, qs, npieces, pc.start.as<uint64_t>(), pc.len.as<uint64_t>(),
+            pc.query.as<uint32_t>(), pc.poffset.as<uint32_t>(),
+            iv.mode.as<uint32_t>(), iv.counts.as<uint64_t>(),
+            iv.offsets.as<uint64_t>(), iv.left.as<uint64_t>(),
+            iv.count.as<uint64_t>(), iv.value.as<uint32_t>(),
+            iv.query.as<uint32_t>(), iv.poffset.as<uint32_t>());
+    return hipGetLastError();
+  };
+  VSA_HIP(hipMemcpyAsync(iv.mode.p, mode.data(), nq * 4,
+                         hipMemcpyHostToDevice, stream));
+  tsearch.start();
+  VSA_HIP(doedist ? pass(std::true_type(), std::false_type())
+                  : pass(std::false_type(), std::false_type()));
+  VSA_HIP(hipMemsetAsync(iv.counts.as<uint64_t>() + npieces, 0, 8, stream));
+  if (exclusive_sum(iv.counts.as<uint64_t>(), iv.offsets.as<uint64_t>(),
+                    npieces, stream, &iv.n))
+  {
+    return -100;
+  }
+  if (iv.n >= 0xFFFFFFFFull)
+  {
+    VSA_ERROR("approximate search: more than 2^32 intervals");
+    return -5;
+  }
+  if (iv.n == 0)
+  {
+    tsearch.stop();
+    return 0;
+  }
+  if (iv.left.alloc(iv.n * 8) || iv.count.alloc(iv.n * 8) ||
+      iv.value.alloc(iv.n * 4) || iv.query.alloc(iv.n * 4) ||
+      iv.poffset.alloc(iv.n * 4) || pcount.alloc((iv.n + 1) * 8) ||
+      iv.poffsets.alloc((iv.n + 1) * 8) || dcount.alloc((iv.n + 1) * 8) ||
+      iv.doffsets.alloc((iv.n + 1) * 8))
+  {
+    return -100;
+  }
+  VSA_HIP(doedist ? pass(std::true_type(), std::true_type())
+                  : pass(std::false_type(), std::true_type()));
+  tsearch.stop();
+  k_apm_treesplit<<<gridfor(iv.n + 1), VSA_BLOCK, 0, stream>>>(
+      iv.count.as<uint64_t>(), iv.query.as<uint32_t>(),
+      iv.mode.as<uint32_t>(), iv.n, pcount.as<uint64_t>(),
+      dcount.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  if (exclusive_sum(pcount.as<uint64_t>(), iv.poffsets.as<uint64_t>(), iv.n,
+                    stream, &iv.total) ||
+      exclusive_sum(dcount.as<uint64_t>(), iv.doffsets.as<uint64_t>(), iv.n,
+                    stream, &iv.ndirect))
+  {
+    return -100;
+  }
+  return 0;
+}
+
+// T2: uncut patterns -- straight to the output, suffix array order
+template <typename IDX>
+int apm_direct(const DevIndex<IDX> &ix, const DevQueries &qs,
+               const uint32_t *dk, int words, bool doedist,
+               TreeIntervals &iv, hipStream_t stream, DevBuf &directm)
+{
+  const uint64_t ndirect = iv.ndirect;
+  DevBuf hitpos, hitregion, rq, rlo, rhi;
+  if (directm.alloc(ndirect * sizeof(vsa_match)) ||
+      (doedist && (hitpos.alloc(ndirect * sizeof(IDX)) ||
+                   hitregion.alloc(ndirect * 4) || rq.alloc(ndirect * 4) ||
+                   rlo.alloc(ndirect * sizeof(IDX)) ||
+                   rhi.alloc(ndirect * sizeof(IDX)))))
+  {
+    return -100;
+  }
+  k_apm_directhits<IDX, IDX><<<gridfor(ndirect), VSA_BLOCK, 0, stream>>>(
+      ix, qs, dk, iv.n, iv.left.as<uint64_t>(), iv.doffsets.as<uint64_t>(),
+      iv.value.as<uint32_t>(), iv.query.as<uint32_t>(), ndirect, doedist,
+      directm.as<vsa_match>(), hitpos.as<IDX>(), hitregion.as<uint32_t>(),
+      rq.as<uint32_t>(), rlo.as<IDX>(), rhi.as<IDX>());
+  VSA_HIP(hipGetLastError());
+  return doedist ? apm_longest<IDX>(ix.tis, qs, dk, words, ndirect,
+                                    hitpos.as<IDX>(),
+                                    hitregion.as<uint32_t>(),
+                                    rq.as<uint32_t>(), rlo.as<IDX>(),
+                                    rhi.as<IDX>(), directm.as<vsa_match>(),
+                                    stream)
+                 : 0;
+}
+
+// T4: one list in query order (merged) from the two; both are in that order
+// already, and every query is answered by one of them
+static int apm_mergelists(const DevQueries &qs, uint64_t nq, DevBuf &splitm,
+                          uint64_t nsplit, DevBuf &directm, uint64_t ndirect,
+                          hipStream_t stream, DevBuf &merged)
+{
+  const uint64_t nhits = nsplit + ndirect;
+  DevBuf all, qkeys, qkeys2, qindex, qindex2, temp;
+  if (nsplit == 0 || ndirect == 0)
+  {
+    merged.p = nsplit != 0 ? splitm.release() : directm.release();
+    return 0;
+  }
+  if (all.alloc(nhits * sizeof(vsa_match)) || qkeys.alloc(nhits * 4) ||
+      qkeys2.alloc(nhits * 4) || qindex.alloc(nhits * 4) ||
+      qindex2.alloc(nhits * 4) || merged.alloc(nhits * sizeof(vsa_match)))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemcpyAsync(all.p, splitm.p, nsplit * sizeof(vsa_match),
+                         hipMemcpyDeviceToDevice, stream));
+  VSA_HIP(hipMemcpyAsync(all.as<vsa_match>() + nsplit, directm.p,
+                         ndirect * sizeof(vsa_match),
+                         hipMemcpyDeviceToDevice, stream));
+  k_apm_querykeys<<<gridfor(nhits), VSA_BLOCK, 0, stream>>>(
+      all.as<vsa_match>(), nhits, qs.seqoffset, qkeys.as<uint32_t>(),
+      qindex.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::radix_sort_pairs(
+        p, tb, qkeys.as<uint32_t>(), qkeys2.as<uint32_t>(),
+        qindex.as<uint32_t>(), qindex2.as<uint32_t>(), (size_t) nhits, 0u,
+        bitsfor(nq), stream);
+  }));
+  k_apm_gathermatches<<<gridfor(nhits), VSA_BLOCK, 0, stream>>>(
+      all.as<vsa_match>(), qindex2.as<uint32_t>(), nhits,
+      merged.as<vsa_match>());
+  VSA_HIP(hipGetLastError());
+  return 0;
+}
+
 template <typename IDX>
 int run_approx_tree(const vsa_index *index, const vsa_queries *queries,
                     bool doedist, const TreePlan &plan, vsa_result *res)
@@ -490,371 +649,70 @@ int run_approx_tree(const vsa_index *index, const vsa_queries *queries,
   const DevIndex<IDX> ix = index->view<IDX>();
   const DevQueries qs = devqueries(queries);
   const uint64_t nq = plan.qlimit, npieces = plan.piecebase[nq];
-  DevBuf dk, dsplitlen, dmode, dpiecebase, pstart, plen, pquery, ppoffset,
-      counts, offsets, ivleft, ivcount, ivvalue, ivquery, ivpoffset, pcount,
-      poffsets, dcount, doffsets, keys, keys2, his, his2, ends, prev, flags,
-      rank, temp, rq, rlo, rhi, rfirst, rcount, roffsets, hitpos, hitregion,
-      splitm, directm, drq, drlo, drhi, dhitpos, dhitregion, all, qkeys,
-      qkeys2, qindex, qindex2, merged;
-  uint64_t nintervals = 0, total = 0, ndirect = 0, nregions = 0, nsplit = 0;
-  size_t tb = 0;
+  const int words = (int) ((plan.maxm + 63) / 64);
+  ApmPieces pc;
+  TreeIntervals iv;
+  ApmRegions rg;
+  DevBuf splitm, directm, merged;
+  uint64_t nsplit = 0;
+  int rc;
 
   res->stats.searches = npieces;
   if (nq == 0 || npieces == 0)
   {
     return 0;
   }
-  // sort keys: query number << pbits | text position (approx_search.inc)
-  const uint32_t pbits = sizeof(IDX) == 4 ? 32u : bitsfor(index->n);
-  if (queries->nq >= 0x7FFFFFFFull || pbits + bitsfor(queries->nq) > 64)
+  if ((rc = apm_positionbits<IDX>(index, queries, 0x7FFFFFFFull,
+                                  &rg.pbits)) != 0)
   {
-    VSA_ERROR("approximate search: a batch of %lu reads on a text of %lu "
-              "symbols is not covered by the GPU engine",
-              (unsigned long) queries->nq, (unsigned long) index->n);
-    return VSA_NOT_COVERED;
+    return rc;
   }
-  if (dk.alloc(nq * 4) || dsplitlen.alloc(nq * 4) || dmode.alloc(nq * 4) ||
-      dpiecebase.alloc((nq + 1) * 8) || pstart.alloc(npieces * 8) ||
-      plen.alloc(npieces * 8) || pquery.alloc(npieces * 4) ||
-      ppoffset.alloc(npieces * 4) || counts.alloc((npieces + 1) * 8) ||
-      offsets.alloc((npieces + 1) * 8))
+  if (pc.alloc(nq, npieces) || iv.alloc(nq, npieces))
   {
     return -100;
   }
   tall.start();
-  VSA_HIP(hipMemcpyAsync(dk.p, plan.k.data(), nq * 4, hipMemcpyHostToDevice,
-                         stream));
-  VSA_HIP(hipMemcpyAsync(dsplitlen.p, plan.splitlen.data(), nq * 4,
-                         hipMemcpyHostToDevice, stream));
-  VSA_HIP(hipMemcpyAsync(dmode.p, plan.mode.data(), nq * 4,
-                         hipMemcpyHostToDevice, stream));
-  VSA_HIP(hipMemcpyAsync(dpiecebase.p, plan.piecebase.data(), (nq + 1) * 8,
-                         hipMemcpyHostToDevice, stream));
-  k_apm_pieces<<<gridfor(nq), VSA_BLOCK, 0, stream>>>(
-      qs, nq, dsplitlen.as<uint32_t>(), dpiecebase.as<uint64_t>(),
-      pstart.as<uint64_t>(), plen.as<uint64_t>(), pquery.as<uint32_t>(),
-      ppoffset.as<uint32_t>());
-  VSA_HIP(hipGetLastError());
-  // T1: the lcp-interval tree, count pass then write pass
-  tsearch.start();
-  const unsigned int tgrid = (unsigned int) ((npieces + 63) / 64);
-#define APM_TREE(EDIT, WRITE)                                                 \
-  k_apm_tree<IDX, EDIT, WRITE><<<tgrid, 64, 0, stream>>>(                     \
-      ix, qs, npieces, pstart.as<uint64_t>(), plen.as<uint64_t>(),            \
-      pquery.as<uint32_t>(), ppoffset.as<uint32_t>(), dmode.as<uint32_t>(),   \
-      counts.as<uint64_t>(), offsets.as<uint64_t>(), ivleft.as<uint64_t>(),   \
-      ivcount.as<uint64_t>(), ivvalue.as<uint32_t>(),                         \
-      ivquery.as<uint32_t>(), ivpoffset.as<uint32_t>())
-  if (doedist)
-  {
-    APM_TREE(true, false);
-  } else
-  {
-    APM_TREE(false, false);
-  }
-  VSA_HIP(hipGetLastError());
-  VSA_HIP(hipMemsetAsync(counts.as<uint64_t>() + npieces, 0, 8, stream));
-  if (apm_exclusive_sum(counts.as<uint64_t>(), offsets.as<uint64_t>(), npieces,
-                        stream, &nintervals))
+  if (pc.upload(plan.k, plan.splitlen, plan.piecebase, nq, stream) ||
+      pc.cut(qs, nq, stream))
   {
     return -100;
   }
-  if (nintervals >= 0xFFFFFFFFull)
+  if ((rc = apm_treesearch<IDX>(ix, qs, pc, plan.mode, nq, npieces, doedist,
+                                tsearch, stream, iv)) != 0)
   {
-    VSA_ERROR("approximate search: more than 2^32 intervals");
-    return -5;
+    return rc;
   }
-  if (nintervals > 0)
-  {
-    if (ivleft.alloc(nintervals * 8) || ivcount.alloc(nintervals * 8) ||
-        ivvalue.alloc(nintervals * 4) || ivquery.alloc(nintervals * 4) ||
-        ivpoffset.alloc(nintervals * 4) ||
-        pcount.alloc((nintervals + 1) * 8) ||
-        poffsets.alloc((nintervals + 1) * 8) ||
-        dcount.alloc((nintervals + 1) * 8) ||
-        doffsets.alloc((nintervals + 1) * 8))
-    {
-      return -100;
-    }
-    if (doedist)
-    {
-      APM_TREE(true, true);
-    } else
-    {
-      APM_TREE(false, true);
-    }
-    VSA_HIP(hipGetLastError());
-  }
-#undef APM_TREE
-  tsearch.stop();
-  if (nintervals > 0)
-  {
-    k_apm_treesplit<<<gridfor(nintervals + 1), VSA_BLOCK, 0, stream>>>(
-        ivcount.as<uint64_t>(), ivquery.as<uint32_t>(), dmode.as<uint32_t>(),
-        nintervals, pcount.as<uint64_t>(), dcount.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    if (apm_exclusive_sum(pcount.as<uint64_t>(), poffsets.as<uint64_t>(),
-                          nintervals, stream, &total) ||
-        apm_exclusive_sum(dcount.as<uint64_t>(), doffsets.as<uint64_t>(),
-                          nintervals, stream, &ndirect))
-    {
-      return -100;
-    }
-  }
-  res->stats.candidates = total + ndirect;
-  if (total >= 0xFFFFFFFFull || ndirect >= 0xFFFFFFFFull)
+  res->stats.candidates = iv.total + iv.ndirect;
+  if (iv.total >= 0xFFFFFFFFull || iv.ndirect >= 0xFFFFFFFFull)
   {
     VSA_ERROR("approximate search: more than 2^32 piece hits");
     return -5;
   }
-  const uint8_t *tis = ix.tis;
-  const int words = (int) ((plan.maxm + 63) / 64);
-  // T2: uncut patterns -- straight to the output, suffix array order
-  if (ndirect > 0)
+  if (iv.ndirect > 0 &&
+      (rc = apm_direct<IDX>(ix, qs, pc.k.as<uint32_t>(), words, doedist, iv,
+                            stream, directm)) != 0)
   {
-    if (directm.alloc(ndirect * sizeof(vsa_match)) ||
-        (doedist && (dhitpos.alloc(ndirect * sizeof(IDX)) ||
-                     dhitregion.alloc(ndirect * 4) || drq.alloc(ndirect * 4) ||
-                     drlo.alloc(ndirect * sizeof(IDX)) ||
-                     drhi.alloc(ndirect * sizeof(IDX)))))
-    {
-      return -100;
-    }
-    k_apm_directhits<IDX, IDX><<<gridfor(ndirect), VSA_BLOCK, 0, stream>>>(
-        ix, qs, dk.as<uint32_t>(), nintervals, ivleft.as<uint64_t>(),
-        doffsets.as<uint64_t>(), ivvalue.as<uint32_t>(),
-        ivquery.as<uint32_t>(), ndirect, doedist, directm.as<vsa_match>(),
-        dhitpos.as<IDX>(), dhitregion.as<uint32_t>(), drq.as<uint32_t>(),
-        drlo.as<IDX>(), drhi.as<IDX>());
-    VSA_HIP(hipGetLastError());
-    if (doedist)
-    {
-#define APM_LONGEST_D(W)                                                      \
-  k_apm_longest<W><<<gridfor(ndirect), VSA_BLOCK, 0, stream>>>(               \
-      tis, qs, dk.as<uint32_t>(), ndirect, dhitpos.as<IDX>(),                 \
-      dhitregion.as<uint32_t>(), drq.as<uint32_t>(), drlo.as<IDX>(),          \
-      drhi.as<IDX>(), directm.as<vsa_match>())
-      switch (words)
-      {
-        case 1: APM_LONGEST_D(1); break;
-        case 2: APM_LONGEST_D(2); break;
-        case 3: APM_LONGEST_D(3); break;
-        case 4: APM_LONGEST_D(4); break;
-        case 5: APM_LONGEST_D(5); break;
-        case 6: APM_LONGEST_D(6); break;
-        case 7: APM_LONGEST_D(7); break;
-        default: APM_LONGEST_D(8); break;
-      }
-#undef APM_LONGEST_D
-      VSA_HIP(hipGetLastError());
-    }
+    return rc;
   }
-  // T3: pieces -- regions, merged, verified from right to left: the code of
-  // run_approx with the intervals in the place of the pieces
-  if (total > 0)
+  // T3: pieces -- regions, merged, verified from right to left: the stages
+  // of run_approx with the intervals in the place of the pieces
+  if (iv.total > 0)
   {
-    if (keys.alloc(total * 8) || keys2.alloc(total * 8) ||
-        his.alloc(total * sizeof(IDX)) || his2.alloc(total * sizeof(IDX)) ||
-        ends.alloc(total * 8) || prev.alloc(total * 8) ||
-        flags.alloc(total * 4) || rank.alloc(total * 4))
+    const ApmHits hits = {iv.left.as<uint64_t>(), iv.poffsets.as<uint64_t>(),
+                          iv.query.as<uint32_t>(), iv.poffset.as<uint32_t>(),
+                          iv.n, iv.total};
+    if ((rc = apm_regions<IDX>(ix, qs, nq, hits, pc.k.as<uint32_t>(), doedist,
+                               nullptr, stream, rg)) != 0 ||
+        (rc = apm_verify<IDX>(ix.tis, qs, pc.k.as<uint32_t>(), words, doedist,
+                              rg, stream, splitm, &nsplit)) != 0)
     {
-      return -100;
+      return rc;
     }
-    k_apm_regions<IDX, IDX><<<gridfor(nintervals), VSA_BLOCK, 0, stream>>>(
-        ix, qs, nintervals, ivleft.as<uint64_t>(), poffsets.as<uint64_t>(),
-        total, ivquery.as<uint32_t>(), ivpoffset.as<uint32_t>(),
-        dk.as<uint32_t>(), doedist, pbits, keys.as<uint64_t>(), his.as<IDX>());
-    VSA_HIP(hipGetLastError());
-    const unsigned int endbit = pbits + bitsfor(nq);
-    tb = 0;
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        his.as<IDX>(), his2.as<IDX>(), (size_t) total, 0u, endbit, stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        his.as<IDX>(), his2.as<IDX>(), (size_t) total, 0u, endbit, stream));
-    k_apm_rightends<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), his2.as<IDX>(), total, pbits,
-        ends.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, ends.as<uint64_t>(),
-                                    prev.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) total, MaxU64(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, ends.as<uint64_t>(),
-                                    prev.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) total, MaxU64(), stream));
-    k_apm_flags<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), prev.as<uint64_t>(), total, pbits,
-        flags.as<uint32_t>());
-    VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::inclusive_scan(nullptr, tb, flags.as<uint32_t>(),
-                                    rank.as<uint32_t>(), (size_t) total,
-                                    rocprim::plus<uint32_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::inclusive_scan(temp.p, tb, flags.as<uint32_t>(),
-                                    rank.as<uint32_t>(), (size_t) total,
-                                    rocprim::plus<uint32_t>(), stream));
-    uint32_t hlast = 0;
-    VSA_HIP(hipMemcpyAsync(&hlast, rank.as<uint32_t>() + total - 1, 4,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipStreamSynchronize(stream));
-    nregions = hlast;
-    if (rq.alloc(nregions * 4) || rlo.alloc(nregions * sizeof(IDX)) ||
-        rhi.alloc(nregions * sizeof(IDX)) ||
-        rfirst.alloc((nregions + 1) * 4) ||
-        rcount.alloc((nregions + 1) * 8) ||
-        roffsets.alloc((nregions + 1) * 8))
-    {
-      return -100;
-    }
-    k_apm_writeregions<<<gridfor(total), VSA_BLOCK, 0, stream>>>(
-        keys2.as<uint64_t>(), ends.as<uint64_t>(), prev.as<uint64_t>(),
-        flags.as<uint32_t>(), rank.as<uint32_t>(), total, pbits,
-        rq.as<uint32_t>(), rlo.as<IDX>(), rhi.as<IDX>(),
-        rfirst.as<uint32_t>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(hipMemsetAsync(rcount.as<uint64_t>() + nregions, 0, 8, stream));
-#define APM_VERIFY_T(W, COUNT)                                                \
-  k_apm_verify_edist<W, COUNT><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(  \
-      tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),                \
-      rlo.as<IDX>(), rhi.as<IDX>(), rcount.as<uint64_t>(),                    \
-      roffsets.as<uint64_t>(), hitpos.as<IDX>(),                              \
-      hitregion.as<uint32_t>())
-#define APM_VERIFY_TW(COUNT)                                                  \
-  switch (words)                                                              \
-  {                                                                           \
-    case 1: APM_VERIFY_T(1, COUNT); break;                                    \
-    case 2: APM_VERIFY_T(2, COUNT); break;                                    \
-    case 3: APM_VERIFY_T(3, COUNT); break;                                    \
-    case 4: APM_VERIFY_T(4, COUNT); break;                                    \
-    case 5: APM_VERIFY_T(5, COUNT); break;                                    \
-    case 6: APM_VERIFY_T(6, COUNT); break;                                    \
-    case 7: APM_VERIFY_T(7, COUNT); break;                                    \
-    default: APM_VERIFY_T(8, COUNT); break;                                   \
   }
-    if (doedist)
-    {
-      APM_VERIFY_TW(true);
-    } else
-    {
-      k_apm_verify_hamming<true><<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-          tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),
-          rlo.as<IDX>(), rhi.as<IDX>(), rcount.as<uint64_t>(),
-          roffsets.as<uint64_t>(), nullptr);
-    }
-    VSA_HIP(hipGetLastError());
-    if (apm_exclusive_sum(rcount.as<uint64_t>(), roffsets.as<uint64_t>(),
-                          nregions, stream, &nsplit))
-    {
-      return -100;
-    }
-    if (nsplit > 0)
-    {
-      if (splitm.alloc(nsplit * sizeof(vsa_match)))
-      {
-        return -100;
-      }
-      if (doedist)
-      {
-        if (hitpos.alloc(nsplit * sizeof(IDX)) || hitregion.alloc(nsplit * 4))
-        {
-          return -100;
-        }
-        APM_VERIFY_TW(false);
-        VSA_HIP(hipGetLastError());
-#define APM_LONGEST_T(W)                                                      \
-  k_apm_longest<W><<<gridfor(nsplit), VSA_BLOCK, 0, stream>>>(                \
-      tis, qs, dk.as<uint32_t>(), nsplit, hitpos.as<IDX>(),                   \
-      hitregion.as<uint32_t>(), rq.as<uint32_t>(), rlo.as<IDX>(),             \
-      rhi.as<IDX>(), splitm.as<vsa_match>())
-        switch (words)
-        {
-          case 1: APM_LONGEST_T(1); break;
-          case 2: APM_LONGEST_T(2); break;
-          case 3: APM_LONGEST_T(3); break;
-          case 4: APM_LONGEST_T(4); break;
-          case 5: APM_LONGEST_T(5); break;
-          case 6: APM_LONGEST_T(6); break;
-          case 7: APM_LONGEST_T(7); break;
-          default: APM_LONGEST_T(8); break;
-        }
-#undef APM_LONGEST_T
-      } else
-      {
-        k_apm_verify_hamming<false>
-            <<<gridfor(nregions), VSA_BLOCK, 0, stream>>>(
-                tis, qs, dk.as<uint32_t>(), nregions, rq.as<uint32_t>(),
-                rlo.as<IDX>(), rhi.as<IDX>(),
-                rcount.as<uint64_t>(), roffsets.as<uint64_t>(),
-                splitm.as<vsa_match>());
-      }
-      VSA_HIP(hipGetLastError());
-    }
-#undef APM_VERIFY_TW
-#undef APM_VERIFY_T
-  }
-  // T4: one list in query order
-  const uint64_t nhits = nsplit + ndirect;
-  if (nhits > 0)
+  if (apm_mergelists(qs, nq, splitm, nsplit, directm, iv.ndirect, stream,
+                     merged))
   {
-    if (nsplit == 0 || ndirect == 0)
-    {
-      merged.p = nsplit != 0 ? splitm.release() : directm.release();
-    } else
-    {
-      if (all.alloc(nhits * sizeof(vsa_match)) || qkeys.alloc(nhits * 4) ||
-          qkeys2.alloc(nhits * 4) || qindex.alloc(nhits * 4) ||
-          qindex2.alloc(nhits * 4) || merged.alloc(nhits * sizeof(vsa_match)))
-      {
-        return -100;
-      }
-      VSA_HIP(hipMemcpyAsync(all.p, splitm.p, nsplit * sizeof(vsa_match),
-                             hipMemcpyDeviceToDevice, stream));
-      VSA_HIP(hipMemcpyAsync(all.as<vsa_match>() + nsplit, directm.p,
-                             ndirect * sizeof(vsa_match),
-                             hipMemcpyDeviceToDevice, stream));
-      k_apm_querykeys<<<gridfor(nhits), VSA_BLOCK, 0, stream>>>(
-          all.as<vsa_match>(), nhits, qs.seqoffset, qkeys.as<uint32_t>(),
-          qindex.as<uint32_t>());
-      VSA_HIP(hipGetLastError());
-      tb = 0;
-      VSA_HIP(rocprim::radix_sort_pairs(
-          nullptr, tb, qkeys.as<uint32_t>(), qkeys2.as<uint32_t>(),
-          qindex.as<uint32_t>(), qindex2.as<uint32_t>(), (size_t) nhits, 0u,
-          bitsfor(nq), stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::radix_sort_pairs(
-          temp.p, tb, qkeys.as<uint32_t>(), qkeys2.as<uint32_t>(),
-          qindex.as<uint32_t>(), qindex2.as<uint32_t>(), (size_t) nhits, 0u,
-          bitsfor(nq), stream));
-      k_apm_gathermatches<<<gridfor(nhits), VSA_BLOCK, 0, stream>>>(
-          all.as<vsa_match>(), qindex2.as<uint32_t>(), nhits,
-          merged.as<vsa_match>());
-      VSA_HIP(hipGetLastError());
-    }
+    return -100;
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = nhits;
-  res->matches = (vsa_match *) merged.release();
-  res->stats.count = nhits;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
-  return sumlengths(res->matches, nhits, stream, &res->stats.sumlength);
+  return finish(res, merged, nsplit + iv.ndirect, tall, tsearch, stream);
 }

@@ -542,7 +542,6 @@ int partition_impl(const vsa_result *result, uint32_t nparts, int ownpart,
                  cells = (uint64_t) nparts * nblocks;
   DevBuf hist, top, offsets, summary, temp;
   uint64_t host[2 * VSA_PART_MAX + 1];
-  size_t tb = 0;
   if (hist.alloc((cells + 1) * 4) || top.alloc(cells * 8) ||
       offsets.alloc((cells + 1) * 8) ||
       summary.alloc((2 * VSA_PART_MAX + 1) * 8))
@@ -578,16 +577,11 @@ int partition_impl(const vsa_result *result, uint32_t nparts, int ownpart,
   VSA_HIP(hipGetLastError());
   auto widen = rocprim::make_transform_iterator(hist.as<uint32_t>(),
                                                 U32ToU64());
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, widen, offsets.as<uint64_t>(),
-                                  (uint64_t) 0, (size_t) (cells + 1),
-                                  rocprim::plus<uint64_t>(), stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, widen, offsets.as<uint64_t>(),
-                                  (uint64_t) 0, (size_t) (cells + 1),
-                                  rocprim::plus<uint64_t>(), stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, widen, offsets.as<uint64_t>(),
+                                   (uint64_t) 0, (size_t) (cells + 1),
+                                   rocprim::plus<uint64_t>(), stream);
+  }));
   k_partition_summary<<<nparts, 1024, 0, stream>>>(
       offsets.as<uint64_t>(), top.as<unsigned long long>(), nparts, nblocks,
       summary.as<uint64_t>(),

@@ -150,20 +150,6 @@ size_t ldsbytes(Form form, const DevQueries &qs)
   return form == Form::Staged ? (size_t) VSA_BLOCK * qs.uniformlen : 0;
 }
 
-// A rocPRIM algorithm, called the rocPRIM way: once for the size of its
-// scratch space, which temp then holds, once to do the work.
-template <typename Algo>
-hipError_t rocprim_run(DevBuf &temp, Algo algo)
-{
-  size_t bytes = 0;
-  hipError_t e = algo(nullptr, bytes);
-  if (e == hipSuccess && temp.alloc(bytes) != 0)
-  {
-    e = hipErrorOutOfMemory;
-  }
-  return e == hipSuccess ? algo(temp.p, bytes) : e;
-}
-
 // ---- K1 pipeline ----
 
 template <typename IDX>
@@ -186,7 +172,7 @@ int run_complete(const vsa_index *index, const vsa_queries *queries,
   }
   const DevQueries qs = devqueries(queries);
   const Form form = pickform(index, queries, qs, Stage::Complete, 0);
-  DevBuf left, count, offsets, temp, matches;
+  DevBuf left, count, offsets, matches;
   uint64_t total = 0;
 
   res->stats.searches = qlimit;
@@ -209,15 +195,11 @@ int run_complete(const vsa_index *index, const vsa_queries *queries,
   });
   tsearch.stop();
   VSA_HIP(hipGetLastError());
-  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-    return rocprim::exclusive_scan(p, tb, count.as<uint64_t>(),
-                                   offsets.as<uint64_t>(), (uint64_t) 0,
-                                   (size_t) (qlimit + 1),
-                                   rocprim::plus<uint64_t>(), stream);
-  }));
-  VSA_HIP(hipMemcpyAsync(&total, offsets.as<uint64_t>() + qlimit, 8,
-                         hipMemcpyDeviceToHost, stream));
-  VSA_HIP(hipStreamSynchronize(stream));
+  if (exclusive_sum(count.as<uint64_t>(), offsets.as<uint64_t>(), qlimit,
+                    stream, &total))
+  {
+    return -100;
+  }
   if (total > 0)
   {
     if (matches.alloc(total * sizeof(vsa_match)))
@@ -229,15 +211,8 @@ int run_complete(const vsa_index *index, const vsa_queries *queries,
         matches.as<vsa_match>());
     VSA_HIP(hipGetLastError());
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = total;
-  res->matches = (vsa_match *) matches.release();
-  res->stats.count = total;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
-  // every complete match has the length of its query
-  return sumlengths(res->matches, total, stream, &res->stats.sumlength);
+  // (every complete match has the length of its query)
+  return finish(res, matches, total, tall, tsearch, stream);
 }
 
 // ---- K2 (+K4) pipeline ----

@@ -23,49 +23,12 @@
 // Every kernel is a template over the width of the tables (IDX = uint32_t for
 // totallength + 1 < 2^32, uint64_t above: include/types.h:41-61 of the
 // reference lifts the limit the same way, a 64-bit Uint).
-#include <cstring>
-#include <algorithm>
 #include <cmath>
-#include "esa_device.hpp"
+#include "search_host.hpp"
 #include <rocprim/rocprim.hpp>
 
-#define VB_BLOCK 256
+#define VB_BLOCK VSA_BLOCK // (gridfor() counts in blocks of this size)
 #define VB_LCP_CHUNK 32
-
-namespace
-{
-
-struct DevBuf
-{
-  void *p = nullptr;
-  ~DevBuf()
-  {
-    vsa_dev_free(p);
-  }
-  int alloc(size_t bytes)
-  {
-    vsa_dev_free(p);
-    p = nullptr;
-    return vsa_dev_alloc(&p, bytes > 0 ? bytes : 16);
-  }
-  void free()
-  {
-    vsa_dev_free(p);
-    p = nullptr;
-  }
-  template <typename T>
-  T *as()
-  {
-    return (T *) p;
-  }
-};
-
-inline dim3 gridfor(uint64_t items)
-{
-  return vsa_grid((items + VB_BLOCK - 1) / VB_BLOCK);
-}
-
-} // namespace
 
 // ---- B1: keys -------------------------------------------------------------
 
@@ -485,15 +448,10 @@ template <typename IDX>
 int maxscan_inplace(IDX *data, uint64_t count, hipStream_t stream)
 {
   DevBuf temp;
-  size_t tb = 0;
-  VSA_HIP(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t) count,
-                                  MaxOp(), stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::inclusive_scan(temp.p, tb, data, data, (size_t) count,
-                                  MaxOp(), stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::inclusive_scan(p, tb, data, data, (size_t) count, MaxOp(),
+                                   stream);
+  }));
   return 0;
 }
 
@@ -529,16 +487,11 @@ int build_bucket_table(const uint8_t *tis, uint64_t n, const IDX *sa,
       tis, n, sa, pl, numofchars, left.as<IDX>(), mid.as<IDX>());
   VSA_HIP(hipGetLastError());
   // suffix-min over the codes = inclusive min-scan on the reversed array
-  size_t tb = 0;
   auto rin = rocprim::make_reverse_iterator(left.as<IDX>() + nc);
-  VSA_HIP(rocprim::inclusive_scan(nullptr, tb, rin, rin, (size_t) nc, MinOp(),
-                                  stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::inclusive_scan(temp.p, tb, rin, rin, (size_t) nc, MinOp(),
-                                  stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::inclusive_scan(p, tb, rin, rin, (size_t) nc, MinOp(),
+                                   stream);
+  }));
   k_bck_finish<IDX><<<codegrid, VB_BLOCK, 0, stream>>>(
       left.as<IDX>(), mid.as<IDX>(), nc, out);
   VSA_HIP(hipGetLastError());
@@ -594,17 +547,11 @@ int build_tables(vsa_index *ix)
         tis, n, ix->numofchars, bits, H, keys.as<uint64_t>(),
         sa2.as<IDX>());
     VSA_HIP(hipGetLastError());
-    size_t tb = 0;
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        sa2.as<IDX>(), sa, (size_t) count, 0u, H * bits, stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        sa2.as<IDX>(), sa, (size_t) count, 0u, H * bits, stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(
+          p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(), sa2.as<IDX>(), sa,
+          (size_t) count, 0u, H * bits, stream);
+    }));
     temp.free();
     keys.free();
     sa2.free();
@@ -639,22 +586,14 @@ int build_tables(vsa_index *ix)
     {
       return -100;
     }
-    {
-      size_t tb = 0;
-      auto counting = rocprim::counting_iterator<IDX>(0);
-      VSA_HIP(rocprim::select(nullptr, tb, counting, flag.as<uint8_t>(),
-                              pos.as<IDX>(), dcount.as<uint64_t>(),
-                              (size_t) count, stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::select(temp.p, tb, counting, flag.as<uint8_t>(),
-                              pos.as<IDX>(), dcount.as<uint64_t>(),
-                              (size_t) count, stream));
-      VSA_HIP(hipMemcpyAsync(&m, dcount.p, 8, hipMemcpyDeviceToHost, stream));
-      VSA_HIP(hipStreamSynchronize(stream));
-    }
+    auto counting = rocprim::counting_iterator<IDX>(0);
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::select(p, tb, counting, flag.as<uint8_t>(),
+                             pos.as<IDX>(), dcount.as<uint64_t>(),
+                             (size_t) count, stream);
+    }));
+    VSA_HIP(hipMemcpyAsync(&m, dcount.p, 8, hipMemcpyDeviceToHost, stream));
+    VSA_HIP(hipStreamSynchronize(stream));
     flag.free();
     uint64_t h = H;
     const char *trace = getenv("VSA_BUILD_TRACE");
@@ -677,19 +616,12 @@ int build_tables(vsa_index *ix)
           pos.as<IDX>(), m, sa, head.as<IDX>(), isa.as<IDX>(),
           h, n, ckey.as<CK>(), csuf.as<IDX>());
       VSA_HIP(hipGetLastError());
-      size_t tb = 0;
-      VSA_HIP(rocprim::radix_sort_pairs(
-          nullptr, tb, ckey.as<CK>(), ckey2.as<CK>(),
-          csuf.as<IDX>(), csuf2.as<IDX>(), (size_t) m, 0u,
-          2 * DoublingKey<IDX>::rankbits, stream));
-      if (t2.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::radix_sort_pairs(
-          t2.p, tb, ckey.as<CK>(), ckey2.as<CK>(),
-          csuf.as<IDX>(), csuf2.as<IDX>(), (size_t) m, 0u,
-          2 * DoublingKey<IDX>::rankbits, stream));
+      VSA_HIP(rocprim_run(t2, [&](void *p, size_t &tb) {
+        return rocprim::radix_sort_pairs(
+            p, tb, ckey.as<CK>(), ckey2.as<CK>(), csuf.as<IDX>(),
+            csuf2.as<IDX>(), (size_t) m, 0u, 2 * DoublingKey<IDX>::rankbits,
+            stream);
+      }));
       k_doubling_heads<IDX><<<gridfor(m), VB_BLOCK, 0, stream>>>(
           ckey2.as<CK>(), pos.as<IDX>(), m,
           newhead.as<IDX>());
@@ -707,17 +639,11 @@ int build_tables(vsa_index *ix)
           rflag.as<uint8_t>());
       VSA_HIP(hipGetLastError());
       uint64_t m2 = 0;
-      tb = 0;
-      VSA_HIP(rocprim::select(nullptr, tb, pos.as<IDX>(),
-                              rflag.as<uint8_t>(), pos2.as<IDX>(),
-                              dcount.as<uint64_t>(), (size_t) m, stream));
-      if (t2.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::select(t2.p, tb, pos.as<IDX>(),
-                              rflag.as<uint8_t>(), pos2.as<IDX>(),
-                              dcount.as<uint64_t>(), (size_t) m, stream));
+      VSA_HIP(rocprim_run(t2, [&](void *p, size_t &tb) {
+        return rocprim::select(p, tb, pos.as<IDX>(), rflag.as<uint8_t>(),
+                               pos2.as<IDX>(), dcount.as<uint64_t>(),
+                               (size_t) m, stream);
+      }));
       VSA_HIP(hipMemcpyAsync(&m2, dcount.p, 8, hipMemcpyDeviceToHost,
                              stream));
       VSA_HIP(hipStreamSynchronize(stream));
@@ -782,19 +708,12 @@ int build_tables(vsa_index *ix)
       {
         return -100;
       }
-      size_t tb = 0;
-      VSA_HIP(rocprim::radix_sort_pairs(
-          nullptr, tb, llvidx.as<IDX>(), sidx.as<IDX>(),
-          llvval.as<IDX>(), sval.as<IDX>(), (size_t) needed, 0u,
-          (unsigned int) (8 * sizeof(IDX)), stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::radix_sort_pairs(
-          temp.p, tb, llvidx.as<IDX>(), sidx.as<IDX>(),
-          llvval.as<IDX>(), sval.as<IDX>(), (size_t) needed, 0u,
-          (unsigned int) (8 * sizeof(IDX)), stream));
+      VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+        return rocprim::radix_sort_pairs(
+            p, tb, llvidx.as<IDX>(), sidx.as<IDX>(), llvval.as<IDX>(),
+            sval.as<IDX>(), (size_t) needed, 0u,
+            (unsigned int) (8 * sizeof(IDX)), stream);
+      }));
       k_llv_pairs<IDX><<<gridfor(needed), VB_BLOCK, 0, stream>>>(
           sidx.as<IDX>(), sval.as<IDX>(), needed,
           (IDX *) ix->llv);

@@ -256,27 +256,34 @@ int compact_matches(const vsa_match *in, const uint8_t *keep,
                            hipStream_t stream)
 {
   DevBuf slots, temp;
-  size_t tb = 0;
   auto keepit = rocprim::make_transform_iterator(keep, KeepToU32());
 
   if (slots.alloc(count * 4))
   {
     return -100;
   }
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, keepit, slots.as<uint32_t>(),
-                                  (uint32_t) 0, (size_t) count,
-                                  rocprim::plus<uint32_t>(), stream));
-  if (temp.alloc(tb))
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, keepit, slots.as<uint32_t>(),
-                                  (uint32_t) 0, (size_t) count,
-                                  rocprim::plus<uint32_t>(), stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, keepit, slots.as<uint32_t>(),
+                                   (uint32_t) 0, (size_t) count,
+                                   rocprim::plus<uint32_t>(), stream);
+  }));
   k_scatter_kept<<<gridfor(count), VSA_BLOCK, 0, stream>>>(
       in, keep, slots.as<uint32_t>(), count, out, nkept);
   VSA_HIP(hipGetLastError());
   return 0;
+}
+
+int exclusive_sum(uint64_t *counts, uint64_t *offsets, uint64_t n,
+                  hipStream_t stream, uint64_t *total)
+{
+  DevBuf temp;
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, counts, offsets, (uint64_t) 0,
+                                   (size_t) (n + 1),
+                                   rocprim::plus<uint64_t>(), stream);
+  }));
+  const Fetch f = {offsets + n, 8};
+  return fetchwords(stream, &f, 1, total);
 }
 
 int sumlengths(const vsa_match *matches, uint64_t n, hipStream_t stream,
@@ -288,20 +295,15 @@ int sumlengths(const vsa_match *matches, uint64_t n, hipStream_t stream,
     return 0;
   }
   DevBuf out, temp;
-  size_t tb = 0;
   auto in = rocprim::make_transform_iterator(matches, MatchLength());
   if (out.alloc(sizeof(uint64_t)) != 0)
   {
     return -100;
   }
-  VSA_HIP(rocprim::reduce(nullptr, tb, in, out.as<uint64_t>(), (uint64_t) 0,
-                          (size_t) n, rocprim::plus<uint64_t>(), stream));
-  if (temp.alloc(tb) != 0)
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::reduce(temp.p, tb, in, out.as<uint64_t>(), (uint64_t) 0,
-                          (size_t) n, rocprim::plus<uint64_t>(), stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::reduce(p, tb, in, out.as<uint64_t>(), (uint64_t) 0,
+                           (size_t) n, rocprim::plus<uint64_t>(), stream);
+  }));
   VSA_HIP(hipMemcpyAsync(result, out.p, sizeof(uint64_t),
                          hipMemcpyDeviceToHost, stream));
   VSA_HIP(hipStreamSynchronize(stream));
@@ -323,17 +325,12 @@ int sortbykey(uint64_t *keys_in, uint64_t *keys_out, vsa_match *in,
               hipStream_t stream)
 {
   DevBuf temp;
-  size_t tb = 0;
   if (n >= 0xFFFFFFFFull)
   {
-    VSA_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, in, out,
-                                      (size_t) n, 0u, endbit, stream));
-    if (temp.alloc(tb) != 0)
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_pairs(temp.p, tb, keys_in, keys_out, in, out,
-                                      (size_t) n, 0u, endbit, stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_pairs(p, tb, keys_in, keys_out, in, out,
+                                       (size_t) n, 0u, endbit, stream);
+    }));
     return 0;
   }
   DevBuf order, order2;
@@ -343,18 +340,12 @@ int sortbykey(uint64_t *keys_in, uint64_t *keys_out, vsa_match *in,
   }
   k_iota_u32<<<gridfor(n), VSA_BLOCK, 0, stream>>>(order.as<uint32_t>(), n);
   VSA_HIP(hipGetLastError());
-  VSA_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out,
-                                    order.as<uint32_t>(),
-                                    order2.as<uint32_t>(), (size_t) n, 0u,
-                                    endbit, stream));
-  if (temp.alloc(tb) != 0)
-  {
-    return -100;
-  }
-  VSA_HIP(rocprim::radix_sort_pairs(temp.p, tb, keys_in, keys_out,
-                                    order.as<uint32_t>(),
-                                    order2.as<uint32_t>(), (size_t) n, 0u,
-                                    endbit, stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::radix_sort_pairs(p, tb, keys_in, keys_out,
+                                     order.as<uint32_t>(),
+                                     order2.as<uint32_t>(), (size_t) n, 0u,
+                                     endbit, stream);
+  }));
   VSA_HIP(gather_matches(in, order2.as<uint32_t>(), n, out, stream));
   return 0;
 }

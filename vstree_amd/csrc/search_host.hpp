@@ -1,7 +1,9 @@
 // Host-side helpers shared by the translation units of the search engine
 // (esa_search.hip, selfmum_search.hip, approx_entry.hip, selfmatch_entry.hip,
-// candidate_partition.hip, index_derive.hip).  Small things are inline here;
-// what instantiates rocPRIM is defined once, in search_common.hip.
+// candidate_partition.hip, index_derive.hip, index_build.hip).  Small things
+// are inline here; what instantiates rocPRIM is defined once, in
+// search_common.hip.  (rocprim_run() is a template over its caller's lambda:
+// it instantiates nothing of rocPRIM by itself.)
 #ifndef VSA_SEARCH_HOST_HPP
 #define VSA_SEARCH_HOST_HPP
 #include <cstring>
@@ -20,10 +22,14 @@ struct DevBuf
   {
     vsa_dev_free(p);
   }
-  int alloc(size_t bytes)
+  void free()
   {
     vsa_dev_free(p);
     p = nullptr;
+  }
+  int alloc(size_t bytes)
+  {
+    free();
     return vsa_dev_alloc(&p, bytes > 0 ? bytes : 16);
   }
   template <typename T>
@@ -92,6 +98,25 @@ struct Fetch
 VSA_HIDDEN int fetchwords(hipStream_t stream, const Fetch *items, int count,
                           uint64_t *out);
 
+// A rocPRIM algorithm, called the rocPRIM way: once for the size of its
+// scratch space, which temp then holds, once to do the work.
+template <typename Algo>
+hipError_t rocprim_run(DevBuf &temp, Algo algo)
+{
+  size_t bytes = 0;
+  hipError_t e = algo(nullptr, bytes);
+  if (e == hipSuccess && temp.alloc(bytes) != 0)
+  {
+    e = hipErrorOutOfMemory;
+  }
+  return e == hipSuccess ? algo(temp.p, bytes) : e;
+}
+
+// offsets[] = exclusive sums of counts[0..n], whose last entry is 0;
+// *total = offsets[n], i.e. the sum of all counts (search_common.hip)
+VSA_HIDDEN int exclusive_sum(uint64_t *counts, uint64_t *offsets, uint64_t n,
+                             hipStream_t stream, uint64_t *total);
+
 inline uint64_t blocksfor(uint64_t items)
 {
   return (items + VSA_BLOCK - 1) / VSA_BLOCK;
@@ -117,6 +142,21 @@ VSA_HIDDEN int compact_matches(const vsa_match *in, const uint8_t *keep,
 
 VSA_HIDDEN int sumlengths(const vsa_match *matches, uint64_t n,
                           hipStream_t stream, uint64_t *result);
+
+// The end of a driver: the call is over when the stream is, and its n
+// matches, the two times and the sum of the lengths go into the result.
+inline int finish(vsa_result *res, DevBuf &matches, uint64_t n, Timer &tall,
+                  Timer &tsearch, hipStream_t stream)
+{
+  tall.stop();
+  VSA_HIP(hipStreamSynchronize(stream));
+  res->count = n;
+  res->matches = (vsa_match *) matches.release();
+  res->stats.count = n;
+  res->stats.search_kernel_ms = tsearch.ms();
+  res->stats.total_device_ms = tall.ms();
+  return sumlengths(res->matches, n, stream, &res->stats.sumlength);
+}
 
 inline unsigned int bitsfor(uint64_t maxvalue)
 {

@@ -155,7 +155,6 @@ static int lcp_select(const uint8_t *lcp, uint64_t n, uint32_t lmin,
   const uint64_t perblock = (uint64_t) VSA_BLOCK * VSA_SEL_PER;
   const uint64_t nblocks = (n + perblock - 1) / perblock;
   DevBuf totals, offsets, temp;
-  size_t tb = 0;
 
   *count = 0;
   if (n == 0)
@@ -172,19 +171,16 @@ static int lcp_select(const uint8_t *lcp, uint64_t n, uint32_t lmin,
   VSA_HIP(hipGetLastError());
   auto widen =
       rocprim::make_transform_iterator(totals.as<uint32_t>(), U32ToU64());
-  VSA_HIP(rocprim::exclusive_scan(nullptr, tb, widen, offsets.as<uint64_t>(),
-                                  (uint64_t) 0, (size_t) (nblocks + 1),
-                                  rocprim::plus<uint64_t>(), stream));
-  if (temp.alloc(tb))
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::exclusive_scan(p, tb, widen, offsets.as<uint64_t>(),
+                                   (uint64_t) 0, (size_t) (nblocks + 1),
+                                   rocprim::plus<uint64_t>(), stream);
+  }));
+  const Fetch f = {offsets.as<uint64_t>() + nblocks, 8};
+  if (fetchwords(stream, &f, 1, count))
   {
     return -100;
   }
-  VSA_HIP(rocprim::exclusive_scan(temp.p, tb, widen, offsets.as<uint64_t>(),
-                                  (uint64_t) 0, (size_t) (nblocks + 1),
-                                  rocprim::plus<uint64_t>(), stream));
-  VSA_HIP(hipMemcpyAsync(count, offsets.as<uint64_t>() + nblocks, 8,
-                         hipMemcpyDeviceToHost, stream));
-  VSA_HIP(hipStreamSynchronize(stream));
   if (*count == 0)
   {
     return 0;
@@ -349,9 +345,8 @@ int run_supermax(const vsa_index *index, uint64_t searchlength,
   Timer tall(stream), tsearch(stream);
   const DevIndex<IDX> ix = index->view<IDX>();
   const uint64_t n = index->n;
-  DevBuf cand, dcount, temp, right, depth, counts, offsets, matches;
+  DevBuf cand, right, depth, counts, offsets, matches;
   uint64_t ncand = 0, total = 0;
-  size_t tb = 0;
 
   res->stats.searches = n;
   tall.start();
@@ -376,22 +371,11 @@ int run_supermax(const vsa_index *index, uint64_t searchlength,
         ix, cand.as<POS>(), ncand, searchlength, right.as<POS>(),
         depth.as<uint64_t>(), counts.as<uint64_t>());
     VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, counts.as<uint64_t>(),
-                                    offsets.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (ncand + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    if (temp.alloc(tb))
+    if (exclusive_sum(counts.as<uint64_t>(), offsets.as<uint64_t>(), ncand,
+                      stream, &total))
     {
       return -100;
     }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, counts.as<uint64_t>(),
-                                    offsets.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (ncand + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    VSA_HIP(hipMemcpyAsync(&total, offsets.as<uint64_t>() + ncand, 8,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipStreamSynchronize(stream));
     if (total > 0)
     {
       if (matches.alloc(total * sizeof(vsa_match)))
@@ -405,14 +389,7 @@ int run_supermax(const vsa_index *index, uint64_t searchlength,
       VSA_HIP(hipGetLastError());
     }
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = total;
-  res->matches = (vsa_match *) matches.release();
-  res->stats.count = total;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
-  return sumlengths(res->matches, total, stream, &res->stats.sumlength);
+  return finish(res, matches, total, tall, tsearch, stream);
 }
 
 // ---- maximal repeats, vmatch -l L IDX --------------------------------------
@@ -679,6 +656,46 @@ k_rep_dbquery(const vsa_match *__restrict__ m, uint64_t n,
   }
 }
 
+// The largest depth decides how many bits of a key (depth, position) the
+// sort has to look at: *dbits for the depth, *endbit for the whole key.
+static int keybits(const char *what, const char *item, uint64_t maxd,
+                   uint64_t n, unsigned int *dbits, unsigned int *endbit)
+{
+  *dbits = bitsfor(maxd);
+  *endbit = *dbits + bitsfor(n);
+  if (*endbit > 64)
+  {
+    VSA_ERROR("%s: a %s of %llu symbols in a text of %llu: the sort key does "
+              "not fit 64 bits", what, item, (unsigned long long) maxd,
+              (unsigned long long) n);
+    return -3;
+  }
+  return 0;
+}
+
+// Intervals report in the order of their keys: order2[] = order[] sorted
+// (stably) by bits [0, endbit) of keys[]; offsets[t] = the first slot of
+// interval order2[t], which reports counts[order2[t]] matches; *total = the
+// number of slots.  (offsets has n + 1 entries.)
+static int reportorder(uint64_t *keys, uint32_t *order, const uint64_t *counts,
+                       uint64_t n, unsigned int endbit, uint32_t *order2,
+                       uint64_t *offsets, hipStream_t stream, uint64_t *total)
+{
+  DevBuf keys2, sorted, temp;
+  if (keys2.alloc(n * 8) || sorted.alloc((n + 1) * 8))
+  {
+    return -100;
+  }
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::radix_sort_pairs(p, tb, keys, keys2.as<uint64_t>(), order,
+                                     order2, (size_t) n, 0u, endbit, stream);
+  }));
+  k_rep_gathercounts<<<gridfor(n), VSA_BLOCK, 0, stream>>>(
+      counts, order2, n, sorted.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  return exclusive_sum(sorted.as<uint64_t>(), offsets, n, stream, total);
+}
+
 template <typename IDX, typename POS>
 int run_repeats(const vsa_index *index, uint64_t searchlength,
                 vsa_result *res)
@@ -689,10 +706,9 @@ int run_repeats(const vsa_index *index, uint64_t searchlength,
   const DevIndex<IDX> ix = index->view<IDX>();
   const uint64_t n = index->n;
   const uint32_t nc = index->numofchars;
-  DevBuf cand, dcount, temp, evl, eve, evd, counts, keys, keys2, order,
-      order2, sorted, offsets, matches, keep, kept;
+  DevBuf cand, dcount, temp, evl, eve, evd, counts, keys, order, order2,
+      offsets, matches, keep, kept;
   uint64_t ncand = 0, total = 0;
-  size_t tb = 0;
 
   res->stats.searches = n;
   if (dcount.alloc(8))
@@ -718,9 +734,8 @@ int run_repeats(const vsa_index *index, uint64_t searchlength,
   {
     if (evl.alloc(ncand * sizeof(POS)) || eve.alloc(ncand * sizeof(POS)) ||
         evd.alloc(ncand * 4) || counts.alloc(ncand * 8) ||
-        keys.alloc(ncand * 8) || keys2.alloc(ncand * 8) ||
-        order.alloc(ncand * 4) || order2.alloc(ncand * 4) ||
-        sorted.alloc((ncand + 1) * 8) || offsets.alloc((ncand + 1) * 8))
+        keys.alloc(ncand * 8) || order.alloc(ncand * 4) ||
+        order2.alloc(ncand * 4) || offsets.alloc((ncand + 1) * 8))
     {
       return -100;
     }
@@ -733,68 +748,30 @@ int run_repeats(const vsa_index *index, uint64_t searchlength,
     k_iota32<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(order.as<uint32_t>(),
                                                        ncand);
     VSA_HIP(hipGetLastError());
-    // the largest depth decides how many key bits the sort has to look at
     uint32_t maxd = 0;
-    tb = 0;
-    VSA_HIP(rocprim::reduce(nullptr, tb, evd.as<uint32_t>(),
-                            dcount.as<uint32_t>(), (uint32_t) 0,
-                            (size_t) ncand, rocprim::maximum<uint32_t>(),
-                            stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::reduce(temp.p, tb, evd.as<uint32_t>(),
-                            dcount.as<uint32_t>(), (uint32_t) 0,
-                            (size_t) ncand, rocprim::maximum<uint32_t>(),
-                            stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::reduce(p, tb, evd.as<uint32_t>(), dcount.as<uint32_t>(),
+                             (uint32_t) 0, (size_t) ncand,
+                             rocprim::maximum<uint32_t>(), stream);
+    }));
     VSA_HIP(hipMemcpyAsync(&maxd, dcount.p, 4, hipMemcpyDeviceToHost,
                            stream));
     VSA_HIP(hipStreamSynchronize(stream));
-    const unsigned int dbits = bitsfor(maxd), endbit = dbits + bitsfor(n);
-    if (endbit > 64)
+    unsigned int dbits, endbit;
+    if (keybits("maximal repeats", "repeat", maxd, n, &dbits, &endbit))
     {
-      VSA_ERROR("maximal repeats: a repeat of %u symbols in a text of %llu: "
-                "the sort key does not fit 64 bits", maxd,
-                (unsigned long long) n);
       return -3;
     }
     k_rep_keys<POS><<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
         eve.as<POS>(), evd.as<uint32_t>(), keys.as<uint64_t>(), ncand, dbits);
     VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::radix_sort_pairs(
-        nullptr, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) ncand, 0u,
-        endbit, stream));
-    if (temp.alloc(tb))
+    if (reportorder(keys.as<uint64_t>(), order.as<uint32_t>(),
+                    counts.as<uint64_t>(), ncand, endbit,
+                    order2.as<uint32_t>(), offsets.as<uint64_t>(), stream,
+                    &total))
     {
       return -100;
     }
-    VSA_HIP(rocprim::radix_sort_pairs(
-        temp.p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(),
-        order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) ncand, 0u,
-        endbit, stream));
-    k_rep_gathercounts<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        counts.as<uint64_t>(), order2.as<uint32_t>(), ncand,
-        sorted.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    tb = 0;
-    VSA_HIP(rocprim::exclusive_scan(nullptr, tb, sorted.as<uint64_t>(),
-                                    offsets.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (ncand + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::exclusive_scan(temp.p, tb, sorted.as<uint64_t>(),
-                                    offsets.as<uint64_t>(), (uint64_t) 0,
-                                    (size_t) (ncand + 1),
-                                    rocprim::plus<uint64_t>(), stream));
-    VSA_HIP(hipMemcpyAsync(&total, offsets.as<uint64_t>() + ncand, 8,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipStreamSynchronize(stream));
     if (total > 0)
     {
       if (matches.alloc(total * sizeof(vsa_match)))
@@ -832,14 +809,7 @@ int run_repeats(const vsa_index *index, uint64_t searchlength,
       }
     }
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = total;
-  res->matches = (vsa_match *) matches.release();
-  res->stats.count = total;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
-  return sumlengths(res->matches, total, stream, &res->stats.sumlength);
+  return finish(res, matches, total, tall, tsearch, stream);
 }
 
 // ---- right branching tandem repeats, vmatch -tandem -l L IDX ---------------
@@ -1242,10 +1212,9 @@ int run_tandems(const vsa_index *index, uint64_t searchlength,
   Timer tall(stream), tsearch(stream);
   const DevIndex<IDX> ix = index->view<IDX>();
   const uint64_t n = index->n;
-  DevBuf cand, unit, counts, keys, keys2, order, order2, sorted, offsets,
-      temp, dcount, matches;
+  DevBuf cand, unit, counts, keys, order, order2, offsets, temp, dcount,
+      matches;
   uint64_t ncand = 0, total = 0;
-  size_t tb = 0;
 
   res->stats.searches = n;
   if (dcount.alloc(8))
@@ -1271,9 +1240,8 @@ int run_tandems(const vsa_index *index, uint64_t searchlength,
   {
     if (unit.alloc(ncand * sizeof(TandemUnit<POS>)) ||
         counts.alloc(ncand * 8) ||
-        keys.alloc(ncand * sizeof(POS)) || keys2.alloc(ncand * 8) ||
-        order.alloc(ncand * 4) || order2.alloc(ncand * 4) ||
-        sorted.alloc((ncand + 1) * 8) || offsets.alloc((ncand + 1) * 8))
+        keys.alloc(ncand * sizeof(POS)) || order.alloc(ncand * 4) ||
+        order2.alloc(ncand * 4) || offsets.alloc((ncand + 1) * 8))
     {
       return -100;
     }
@@ -1303,43 +1271,27 @@ int run_tandems(const vsa_index *index, uint64_t searchlength,
     VSA_HIP(hipGetLastError());
     // Only the intervals that report something go on: of the 1.8e8 positions
     // of the 3 Gbp probe 2.8e6 (sorting all of them was 12 of its 50 ms).
-    // order[] = their numbers, keysk[] their keys.
+    // order[] = their numbers, keysk[] their keys.  (Their number waits in
+    // offsets[0] until it is fetched.)
     uint64_t nkeep = 0, maxd = 0;
     DevBuf keysk;
-    {
-      auto reports = rocprim::make_transform_iterator(
-          counts.as<uint64_t>(),
-          [] __device__(uint64_t c) { return (uint8_t) (c != 0 ? 1 : 0); });
-      tb = 0;
-      VSA_HIP(rocprim::select(nullptr, tb,
-                              rocprim::counting_iterator<uint32_t>(0), reports,
-                              order.as<uint32_t>(), sorted.as<uint64_t>(),
-                              (size_t) ncand, stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::select(temp.p, tb,
-                              rocprim::counting_iterator<uint32_t>(0), reports,
-                              order.as<uint32_t>(), sorted.as<uint64_t>(),
-                              (size_t) ncand, stream));
-    }
-    // the largest depth decides how many key bits the sort has to look at
+    auto reports = rocprim::make_transform_iterator(
+        counts.as<uint64_t>(),
+        [] __device__(uint64_t c) { return (uint8_t) (c != 0 ? 1 : 0); });
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::select(p, tb, rocprim::counting_iterator<uint32_t>(0),
+                             reports, order.as<uint32_t>(),
+                             offsets.as<uint64_t>(), (size_t) ncand, stream);
+    }));
     auto depth = rocprim::make_transform_iterator(unit.as<TandemUnit<POS>>(),
                                                   TandemDepth<POS>());
-    tb = 0;
-    VSA_HIP(rocprim::reduce(nullptr, tb, depth, dcount.as<uint32_t>(),
-                            (uint32_t) 0, (size_t) ncand,
-                            rocprim::maximum<uint32_t>(), stream));
-    if (temp.alloc(tb))
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::reduce(p, tb, depth, dcount.as<uint32_t>(),
+                             (uint32_t) 0, (size_t) ncand,
+                             rocprim::maximum<uint32_t>(), stream);
+    }));
     {
-      return -100;
-    }
-    VSA_HIP(rocprim::reduce(temp.p, tb, depth, dcount.as<uint32_t>(),
-                            (uint32_t) 0, (size_t) ncand,
-                            rocprim::maximum<uint32_t>(), stream));
-    {
-      const Fetch f[2] = {{dcount.p, 4}, {sorted.p, 8}};
+      const Fetch f[2] = {{dcount.p, 4}, {offsets.p, 8}};
       uint64_t got[2];
       if (fetchwords(stream, f, 2, got))
       {
@@ -1350,58 +1302,25 @@ int run_tandems(const vsa_index *index, uint64_t searchlength,
     }
     if (nkeep > 0)
     {
+      unsigned int dbits, endbit;
       if (keysk.alloc(nkeep * 8))
       {
         return -100;
       }
-      const unsigned int dbits = bitsfor(maxd), endbit = dbits + bitsfor(n);
-      if (endbit > 64)
+      if (keybits("tandem repeats", "unit", maxd, n, &dbits, &endbit))
       {
-        VSA_ERROR("tandem repeats: a unit of %llu symbols in a text of %llu: "
-                  "the sort key does not fit 64 bits",
-                  (unsigned long long) maxd, (unsigned long long) n);
         return -3;
       }
       k_tan_keys<POS><<<gridfor(nkeep), VSA_BLOCK, 0, stream>>>(
           keys.as<POS>(), unit.as<TandemUnit<POS>>(), order.as<uint32_t>(),
           nkeep, dbits, keysk.as<uint64_t>());
       VSA_HIP(hipGetLastError());
-      tb = 0;
-      VSA_HIP(rocprim::radix_sort_pairs(
-          nullptr, tb, keysk.as<uint64_t>(), keys2.as<uint64_t>(),
-          order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) nkeep, 0u,
-          endbit, stream));
-      if (temp.alloc(tb))
+      if (reportorder(keysk.as<uint64_t>(), order.as<uint32_t>(),
+                      counts.as<uint64_t>(), nkeep, endbit,
+                      order2.as<uint32_t>(), offsets.as<uint64_t>(), stream,
+                      &total))
       {
         return -100;
-      }
-      VSA_HIP(rocprim::radix_sort_pairs(
-          temp.p, tb, keysk.as<uint64_t>(), keys2.as<uint64_t>(),
-          order.as<uint32_t>(), order2.as<uint32_t>(), (size_t) nkeep, 0u,
-          endbit, stream));
-      k_rep_gathercounts<<<gridfor(nkeep), VSA_BLOCK, 0, stream>>>(
-          counts.as<uint64_t>(), order2.as<uint32_t>(), nkeep,
-          sorted.as<uint64_t>());
-      VSA_HIP(hipGetLastError());
-      tb = 0;
-      VSA_HIP(rocprim::exclusive_scan(nullptr, tb, sorted.as<uint64_t>(),
-                                      offsets.as<uint64_t>(), (uint64_t) 0,
-                                      (size_t) (nkeep + 1),
-                                      rocprim::plus<uint64_t>(), stream));
-      if (temp.alloc(tb))
-      {
-        return -100;
-      }
-      VSA_HIP(rocprim::exclusive_scan(temp.p, tb, sorted.as<uint64_t>(),
-                                      offsets.as<uint64_t>(), (uint64_t) 0,
-                                      (size_t) (nkeep + 1),
-                                      rocprim::plus<uint64_t>(), stream));
-      {
-        const Fetch f = {offsets.as<uint64_t>() + nkeep, 8};
-        if (fetchwords(stream, &f, 1, &total))
-        {
-          return -100;
-        }
       }
     }
     if (total > 0)
@@ -1416,12 +1335,5 @@ int run_tandems(const vsa_index *index, uint64_t searchlength,
       VSA_HIP(hipGetLastError());
     }
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->count = total;
-  res->matches = (vsa_match *) matches.release();
-  res->stats.count = total;
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.total_device_ms = tall.ms();
-  return sumlengths(res->matches, total, stream, &res->stats.sumlength);
+  return finish(res, matches, total, tall, tsearch, stream);
 }

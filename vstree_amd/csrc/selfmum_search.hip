@@ -45,7 +45,6 @@ int run_selfmum(const vsa_index *index, uint64_t searchlength,
                                       1024,
                                   4096),
            needed = 0, maxshard = 0;
-  double searchms = 0;
 
   res->stats.searches = jhi > jlo ? jhi - jlo : 0;
   DevBuf summary;
@@ -84,7 +83,6 @@ int run_selfmum(const vsa_index *index, uint64_t searchlength,
       needed = got[0];
       maxshard = got[1];
     }
-    searchms = tsearch.ms(); // the streaming pass (of the last attempt)
     if (maxshard <= shardcap)
     {
       break;
@@ -111,17 +109,11 @@ int run_selfmum(const vsa_index *index, uint64_t searchlength,
         doff.as<uint64_t>(), peaks.as<IDX>());
     VSA_HIP(hipGetLastError());
     // the reference reports in suffix-array order
-    size_t tb = 0;
-    VSA_HIP(rocprim::radix_sort_keys(nullptr, tb, peaks.as<IDX>(),
-                                     sorted.as<IDX>(), (size_t) needed,
-                                     0u, bitsfor(n), stream));
-    if (temp.alloc(tb))
-    {
-      return -100;
-    }
-    VSA_HIP(rocprim::radix_sort_keys(temp.p, tb, peaks.as<IDX>(),
-                                     sorted.as<IDX>(), (size_t) needed,
-                                     0u, bitsfor(n), stream));
+    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+      return rocprim::radix_sort_keys(p, tb, peaks.as<IDX>(),
+                                      sorted.as<IDX>(), (size_t) needed, 0u,
+                                      bitsfor(n), stream);
+    }));
     k_selfmum_emit<IDX><<<gridfor(needed), VSA_BLOCK, 0, stream>>>(
         ix, sorted.as<IDX>(), needed, searchlength,
         index->querysepposition, cand.as<vsa_match>(), keep.as<uint8_t>());
@@ -131,24 +123,15 @@ int run_selfmum(const vsa_index *index, uint64_t searchlength,
     {
       return -100;
     }
+    const Fetch f = {dcount.p, 8};
+    if (fetchwords(stream, &f, 1, &nm))
     {
-      const Fetch f = {dcount.p, 8};
-      if (fetchwords(stream, &f, 1, &nm))
-      {
-        return -100;
-      }
+      return -100;
     }
-    VSA_HIP(hipStreamSynchronize(stream));
-    res->count = nm;
-    res->matches = (vsa_match *) mums.release();
   }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(stream));
-  res->stats.count = res->count;
   res->stats.candidates = needed;
-  res->stats.search_kernel_ms = searchms;
-  res->stats.total_device_ms = tall.ms();
-  return sumlengths(res->matches, res->count, stream, &res->stats.sumlength);
+  // (tsearch: the streaming pass of the last attempt)
+  return finish(res, mums, nm, tall, tsearch, stream);
 }
 
 } // namespace
