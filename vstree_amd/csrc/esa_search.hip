@@ -16,8 +16,13 @@
 //                            form, k_query_search_planned
 //   mem_workplan.inc     K2m k_repeat_bits / k_mem_plan: which offsets of a
 //                            read a MEM search has to look at
-//   mum_filter.inc       K4  candidates as (sort key, value) pairs sorted by
-//                            dbstart, prefix-max scan of the right ends,
+//   candidate_sort.inc   K4s candidates as (sort key, value) pairs thrown
+//                            into buckets by the high bits of dbstart from
+//                            where they were produced, every bucket sorted
+//                            in LDS (short or concentrated lists: compaction
+//                            and rocPRIM's radix sort)
+//   mum_filter.inc       K4  the pairs in dbstart order:
+//                            prefix-max scan of the right ends,
 //                            flags from the keys (runs of equal dbstarts
 //                            looked at as runs), survivors written as records
 //                            in order (kurtz/cleanMUMcand.c:55-118)
@@ -42,6 +47,12 @@
 //   VSA_TUNE=2        no work reduction: every offset of every read is
 //                     searched by the list form of the search kernel (the
 //                     cross-check of first pass + work plan)
+//   VSA_TUNE=4        MUM candidates sorted by rocPRIM's radix sort whatever
+//                     their number (A/B and cross-check of the bucket sort)
+//   VSA_TUNE=8        ... by the bucket sort whatever their number (tests on
+//                     small texts; by default lists below VSA_CS_MINPAIRS
+//                     take rocPRIM)
+//                     (a bit mask: 2, 4 and 8 combine)
 //   VSA_NO_ESA8=1     no deep tables: the reference walk, probe for probe
 //   VSA_DEEP_PREFIX=D their depth (default ceil(log4 n), at most 16)
 //   VSA_FORCE_WIDE=1  64-bit device tables whatever the size of the text
@@ -55,6 +66,8 @@
 #include "mum_workplan.inc"
 #include "mem_workplan.inc"
 #include "mum_filter.inc"
+#include "candidate_sort.inc"
+#include <atomic>
 
 // ---------------------------------------------------------------------------
 // host side
@@ -464,14 +477,23 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
 // candidates never exist as 32-byte records.
 // keys_in / vals_in: anything rocPRIM can read (pointers, or iterators over
 // rows of pairs as they come out of the exchange: no copy into two arrays)
+// presort(k2, v2, flag) (optional): delivers the first attempt's order in
+// place of rocPRIM's sort without keys_in / vals_in, or raises a bit of *flag
+// (candidate_bucketsort).  With one, a raised flag word ends the call: it
+// returns VSA_PRESORT_GAVE_UP with the word in *nmums, and the caller comes
+// again with the list (firstpass = 1 if only "a run was too long" is up: the
+// second attempt at once).
+#define VSA_PRESORT_GAVE_UP 1
 template <typename VAL = uint64_t, typename KeyIn = const uint64_t *,
-          typename ValIn = const VAL *>
+          typename ValIn = const VAL *, typename Presort = std::nullptr_t>
 int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
                      unsigned int lenbits, unsigned int dbbits,
                      hipStream_t stream, DevBuf &mums, uint64_t *nmums,
                      uint64_t *sumlength, uint64_t carry = 0,
-                     unsigned int valbits = 0, uint64_t seqoffset = 0)
+                     unsigned int valbits = 0, uint64_t seqoffset = 0,
+                     Presort presort = nullptr, int firstpass = 0)
 {
+  constexpr bool havepresort = !std::is_same<Presort, std::nullptr_t>::value;
   // VAL, valbits, seqoffset: see k_mum_writepacked
   // carry: as for mumuniqueinquery
   *nmums = 0;
@@ -503,16 +525,32 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
   // k_mumf_flags; decided afterwards from a flag that comes back with the
   // counts), by (dbstart, length down) otherwise.
   uint64_t got[3] = {0, 0, 0};
-  for (int pass = 0; pass < 2; pass++)
+  for (int pass = firstpass; pass < 2; pass++)
   {
     const bool byruns = pass == 0;
     const unsigned int firstbit = byruns ? lenbits : 0u;
+    bool sorted = false;
     VSA_HIP(hipMemsetAsync(dcount.p, 0, 24, stream));
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::radix_sort_pairs(p, tb, keys_in, k2.as<uint64_t>(),
-                                       vals_in, v2.as<VAL>(), (size_t) ncand,
-                                       firstbit, lenbits + dbbits, stream);
-    }));
+    if constexpr (havepresort)
+    {
+      if (byruns)
+      {
+        if (presort(k2.as<uint64_t>(), v2.as<VAL>(),
+                    dcount.as<unsigned int>() + 4))
+        {
+          return -100;
+        }
+        sorted = true;
+      }
+    }
+    if (!sorted)
+    {
+      VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+        return rocprim::radix_sort_pairs(p, tb, keys_in, k2.as<uint64_t>(),
+                                         vals_in, v2.as<VAL>(), (size_t) ncand,
+                                         firstbit, lenbits + dbbits, stream);
+      }));
+    }
     if (byruns)
     {
       const dim3 tg = vsa_grid(ntiles);
@@ -545,6 +583,11 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
       if (got[2] == 0)
       {
         break;
+      }
+      if constexpr (havepresort)
+      {
+        *nmums = got[2];
+        return VSA_PRESORT_GAVE_UP;
       }
       continue;
     }
@@ -1180,12 +1223,134 @@ int compact(QueryRun &st)
   return 0;
 }
 
+// Lists shorter than this are sorted by rocPRIM unless VSA_TUNE says
+// otherwise: a speed heuristic only.  On a 300 Mbp and on a 3 Gbp index (16-
+// byte staging entries below 45 k candidates there) the bucket path won at
+// every size tried, from 19 k candidates on (profiles/r05/sizes_probe.txt,
+// sizes_probe_3g.txt); below the smallest size measured things stay as they
+// were.
+#define VSA_CS_MINPAIRS (1u << 14)
+
+// bucket sorts run, calls that came back from one to rocPRIM (a bucket
+// overflowed), calls that came back for the second attempt (a run was too
+// long), and the geometry of the last one: for tests and probes
+// (vsa_debug_candidate_sort; not part of the ABI)
+std::atomic<uint64_t> g_cs_runs{0}, g_cs_overflows{0}, g_cs_longruns{0},
+    g_cs_shift{0}, g_cs_buckets{0};
+
+// -mum on packed records: does the sort read the candidates where they were
+// produced (candidate_sort.inc), without compact()?
+bool feedsbuckets(const QueryRun &st)
+{
+  const uint64_t total = st.needed + st.nplan + st.nfirst;
+  const uint32_t tune = st.index->tune;
+  // (beyond VSA_CS_MAXBUCKETS buckets, some 25 M candidates: a scatter
+  // workgroup's counters no longer fit into LDS)
+  if (!(st.domum && !st.domumcand && st.rec.packed && (tune & 4u) == 0 &&
+        total > 0 && (total >= VSA_CS_MINPAIRS || (tune & 8u) != 0) &&
+        cs_geometry(st.index->n, total, st.rec.lenbits, st.rec.dbbits)
+                .nbuckets <= VSA_CS_MAXBUCKETS))
+  {
+    return false;
+  }
+  // (an index whose last batches overflowed the buckets: see cs_skip)
+  if ((tune & 8u) == 0 && st.index->cs_skip > 0)
+  {
+    st.index->cs_skip--;
+    return false;
+  }
+  return true;
+}
+
+// MUMs of a packed run through the bucket sort; VSA_PRESORT_GAVE_UP (and the
+// flag word in *nm) if the list has to go through compact() and rocPRIM
+template <typename VAL>
+int mumfilter_buckets(QueryRun &st, DevBuf &mums, uint64_t *nm,
+                      uint64_t *mumsum)
+{
+  const RecordForm &rec = st.rec;
+  const uint64_t total = st.needed + st.nplan + st.nfirst;
+  CsSources src = CsSources();
+  if (st.needed > 0)
+  {
+    src.reg[0] = {st.rawout.p, st.rawkeys.as<uint64_t>(),
+                  st.cursor.as<unsigned long long>(), st.shardcap, st.needed};
+  }
+  if (st.nplan > 0)
+  {
+    src.reg[1] = {st.prawout.p, st.prawkeys.as<uint64_t>(),
+                  st.pcursor.as<unsigned long long>(), st.pcap, st.nplan};
+  }
+  if (st.nfirst > 0)
+  {
+    src.first = {st.wfmlen.as<uint32_t>(), st.wfmdb.as<uint64_t>(),
+                 st.queries->nq, st.qs.seqoffset, rec.packbits, rec.valbits};
+  }
+  auto presort = [&](uint64_t *k2, VAL *v2, unsigned int *flag) {
+    CsGeometry g;
+    const int rc = candidate_bucketsort<VAL>(src, total, st.index->n,
+                                             rec.lenbits, rec.dbbits, k2, v2,
+                                             flag, st.stream, &g);
+    if (rc == 0)
+    {
+      g_cs_runs++;
+      g_cs_shift = g.shift;
+      g_cs_buckets = g.nbuckets;
+    }
+    return rc;
+  };
+  return mumfilter_packed<VAL>((const uint64_t *) nullptr,
+                               (const VAL *) nullptr, total, rec.lenbits,
+                               rec.dbbits, st.stream, mums, nm, mumsum, 0,
+                               rec.valbits,
+                               sizeof(VAL) == 4 ? st.qs.seqoffset : 0,
+                               presort);
+}
+
 // the dense list into the result: the pairs themselves, the MUMs behind the
 // filter, the candidates as they lie, or the matches in reference order;
 // *mumsum: the sum of the MUMs' lengths if the filter made it
+// (-mum on packed records: the bucket sort in front of the filter takes the
+// candidates from their producers; the dense list is made only if it gives up)
 int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
 {
   const RecordForm &rec = st.rec;
+  int firstpass = 0;
+  if (feedsbuckets(st))
+  {
+    DevBuf mums;
+    uint64_t nm = 0;
+    const int rc = rec.valbits != 0
+                       ? mumfilter_buckets<uint32_t>(st, mums, &nm, mumsum)
+                       : mumfilter_buckets<uint64_t>(st, mums, &nm, mumsum);
+    if (rc == 0)
+    {
+      st.index->cs_penalty = 0;
+      res->stats.candidates = st.needed + st.nplan + st.nfirst;
+      res->count = nm;
+      res->matches = (vsa_match *) mums.release();
+      return 0;
+    }
+    if (rc != VSA_PRESORT_GAVE_UP)
+    {
+      return -100;
+    }
+    if ((nm & VSA_CS_OVERFLOW) != 0)
+    {
+      g_cs_overflows++;
+      st.index->cs_penalty =
+          std::min(64u, std::max(1u, 2 * st.index->cs_penalty));
+      st.index->cs_skip = st.index->cs_penalty;
+    } else
+    {
+      g_cs_longruns++;
+      firstpass = 1; // (the buckets were fine: straight to the second attempt)
+    }
+  }
+  if (compact(st))
+  {
+    return -100;
+  }
   const uint64_t needed = st.needed;
   res->stats.candidates = st.domum ? needed : 0;
   if (rec.keeppairs)
@@ -1207,12 +1372,13 @@ int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
       rc = mumfilter_packed<uint32_t>(
           st.keys.as<const uint64_t>(), st.out.as<const uint32_t>(), needed,
           rec.lenbits, rec.dbbits, st.stream, mums, &nm, mumsum, 0,
-          rec.valbits, st.qs.seqoffset);
+          rec.valbits, st.qs.seqoffset, nullptr, firstpass);
     } else if (rec.packed)
     {
       rc = mumfilter_packed(st.keys.as<const uint64_t>(),
                             st.out.as<const uint64_t>(), needed, rec.lenbits,
-                            rec.dbbits, st.stream, mums, &nm, mumsum);
+                            rec.dbbits, st.stream, mums, &nm, mumsum, 0, 0, 0,
+                            nullptr, firstpass);
     } else
     {
       rc = mumuniqueinquery(st.out, needed, st.stream, mums, &nm, 0, nullptr,
@@ -1282,7 +1448,7 @@ int run_query(const vsa_index *index, const vsa_queries *queries, bool domum,
     return rc;
   }
   uint64_t mumsum = ~0ull;
-  if (compact(st) || finish(st, res, &mumsum))
+  if (finish(st, res, &mumsum))
   {
     return -100;
   }
@@ -1681,4 +1847,17 @@ extern "C" int vsa_mumuniqueinquery_range_packed(const void *device_rows,
   return vsa_mumuniqueinquery_range_packed2(device_rows, nrows, nullptr, 0,
                                             lengthbits, totallength, device,
                                             carry_dbright, result);
+}
+
+// For tests and probes, not part of the ABI: how often this process sorted
+// MUM candidates by buckets, how often a bucket overflowed and the list went
+// to rocPRIM after all, how often a run was too long for the first attempt,
+// and shift and number of buckets of the last bucket sort.
+extern "C" void vsa_debug_candidate_sort(uint64_t out[5])
+{
+  out[0] = g_cs_runs;
+  out[1] = g_cs_overflows;
+  out[2] = g_cs_longruns;
+  out[3] = g_cs_shift;
+  out[4] = g_cs_buckets;
 }

@@ -126,6 +126,16 @@ struct vsa_index
   // asks for this least length and kept; nullptr before
   mutable uint32_t *repbits = nullptr;
   mutable uint32_t repleast = 0;
+  // the bucket sort of the MUM candidates (candidate_sort.inc) backs off on
+  // an index whose batches overflow it: after an overflow the next cs_penalty
+  // -mum calls go straight to rocPRIM, and the penalty doubles (up to 64)
+  // with every overflow in a row; a bucket sort that succeeds clears it.
+  // One index that serves concentrated and spread batches in turn therefore
+  // sends spread batches to rocPRIM too while it backs off (they lose what
+  // the bucket sort would have gained, nothing else).  Plain words, written
+  // by the host thread of a call: two threads on one index may miscount the
+  // skips, which changes the path of a call and never its result.
+  mutable uint32_t cs_skip = 0, cs_penalty = 0;
 
   template <typename IDX>
   DevIndex<IDX> view() const
