@@ -1017,7 +1017,7 @@ def test_packed_candidates_and_filter_in_ranges(V):
 
 def test_mum_filter_runs_of_equal_dbstart(V):
     """the filter sorts by dbstart alone and settles runs of equal dbstarts
-    by looking at the run (k_mum_keyflags_runs); beyond 64 members it sorts on
+    by looking at the run (k_mumf_flags<false>); beyond 64 members it sorts on
     all bits instead.  Reads of different lengths from the same start: short
     runs with a unique longest member, with the longest twice, and a run of
     101 -- all against the oracle."""

@@ -21,11 +21,15 @@
 //                            where they were produced, every bucket sorted
 //                            in LDS (short or concentrated lists: compaction
 //                            and rocPRIM's radix sort)
-//   mum_filter.inc       K4  the pairs in dbstart order:
-//                            prefix-max scan of the right ends,
-//                            flags from the keys (runs of equal dbstarts
-//                            looked at as runs), survivors written as records
-//                            in order (kurtz/cleanMUMcand.c:55-118)
+//   mum_filter.inc       K4  one filter on sorted (key, value) pairs, in
+//                            tiles: running maximum of the right ends, flags
+//                            from the keys, survivors written as records in
+//                            order (kurtz/cleanMUMcand.c:55-118).  Three
+//                            sorters in front of it: the bucket sort and
+//                            rocPRIM on dbstart alone (runs of equal dbstarts
+//                            looked at as runs), rocPRIM on all bits (a run
+//                            too long for that; candidate records, as
+//                            composite key + index)
 // The other families have translation units of their own since round 4:
 //   selfmum_search.hip       K3, the scan over an index that holds its queries
 //   approx_entry.hip         -complete -e/-h (approx_search.inc, approx_tree.inc)
@@ -274,188 +278,179 @@ k_mum_compositekeys(const vsa_match *__restrict__ cand, uint64_t n,
   }
 }
 
-// carry = the reference's running `dbright` when it reaches the first of
-// these candidates: 0 for a whole job, the largest right end of all
-// candidates with a smaller dbstart when the list is one dbstart range of a
-// job that is filtered in pieces (multi-GPU).  *maxright (optional) receives
-// the largest right end in this list.
-int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
-                     DevBuf &mums, uint64_t *nmums, uint64_t carry = 0,
-                     uint64_t *maxright = nullptr, uint64_t dbbound = 0,
-                     uint64_t lenbound = 0, uint64_t *sumlength = nullptr)
+// ---- K4: three sorters, one filter (mum_filter.inc) ----
+
+// What a sorter fills and the filter reads: the pairs in dbstart order, the
+// flag word both may raise (device; bit 0: a run was too long for the filter
+// by runs, VSA_CS_OVERFLOW: the bucket sort gave up), the filter's tiles
+struct SortedPairs
 {
-  // *sumlength (if asked for) = sum of the lengths of the MUMs, or ~0 if this
-  // call did not compute it
-  // dbbound / lenbound: upper bounds of dbstart and length if the caller
-  // knows them (index length, longest query), else 0: they are looked up
-  *nmums = 0;
-  if (maxright != nullptr)
+  DevBuf k2, v2, flag, keep, tmax, tcarry, tcount, toff, tsum, tsumscan;
+  uint64_t n = 0, ntiles = 0;
+  // ... and the room for the MUMs
+  int alloc(uint64_t ncand, size_t valbytes, DevBuf &mums)
   {
-    *maxright = 0;
+    n = ncand;
+    ntiles = (ncand + VSA_FT_TILE - 1) / VSA_FT_TILE;
+    return tmax.alloc((ntiles + 1) * 8) || tcarry.alloc((ntiles + 1) * 8) ||
+           tcount.alloc((ntiles + 1) * 8) || toff.alloc((ntiles + 1) * 8) ||
+           tsum.alloc((ntiles + 1) * 8) || tsumscan.alloc((ntiles + 1) * 8) ||
+           k2.alloc(ncand * 8) || v2.alloc(ncand * valbytes) ||
+           keep.alloc(ntiles * VSA_FT_TILE) || flag.alloc(8) ||
+           mums.alloc(ncand * sizeof(vsa_match));
   }
-  if (sumlength != nullptr)
+};
+
+// number of MUMs, sum of their lengths, the flag word
+struct MumCounts
+{
+  uint64_t nmums, sumlength, flags;
+};
+
+// The filter on sorted pairs: SORTED = on all bits of the keys, else on
+// dbstart alone (then bit 0 of c->flags may come back up, and the MUMs are
+// not to be used).  carry = the reference's running `dbright` when it reaches
+// the first of these candidates: 0 for a whole job, the largest right end of
+// all candidates with a smaller dbstart when the list is one dbstart range of
+// a job that is filtered in pieces (multi-GPU).
+template <bool SORTED, typename WRITER>
+int mumfilter_tiles(SortedPairs &s, unsigned int lenbits, uint64_t carry,
+                    WRITER write, hipStream_t stream, DevBuf &mums,
+                    MumCounts *c)
+{
+  using VAL = typename WRITER::VAL;
+  const dim3 tg = vsa_grid(s.ntiles);
+  k_mumf_tilemax<<<tg, VSA_BLOCK, 0, stream>>>(
+      s.k2.as<uint64_t>(), s.n, lenbits, s.tmax.as<uint64_t>());
+  k_mumf_scan<1><<<1, VSA_BLOCK, 0, stream>>>(
+      s.tmax.as<uint64_t>(), s.ntiles, carry, s.tcarry.as<uint64_t>());
+  k_mumf_flags<SORTED><<<tg, VSA_BLOCK, 0, stream>>>(
+      s.k2.as<uint64_t>(), s.n, lenbits, s.tcarry.as<uint64_t>(),
+      s.keep.as<uint8_t>(), s.tcount.as<uint64_t>(), s.tsum.as<uint64_t>(),
+      s.flag.as<unsigned int>());
+  // (offsets of the tiles and, in a second workgroup, the sum of the lengths)
+  k_mumf_scan<0><<<2, VSA_BLOCK, 0, stream>>>(
+      s.tcount.as<uint64_t>(), s.ntiles, 0, s.toff.as<uint64_t>(),
+      s.tsum.as<uint64_t>(), s.tsumscan.as<uint64_t>());
+  k_mumf_write<WRITER><<<tg, VSA_BLOCK, 0, stream>>>(
+      s.k2.as<uint64_t>(), s.v2.as<VAL>(), s.keep.as<uint8_t>(), s.n,
+      s.toff.as<uint64_t>(), write, mums.as<vsa_match>());
+  VSA_HIP(hipGetLastError());
+  const Fetch f[3] = {{s.toff.as<uint64_t>() + s.ntiles, 8},
+                      {s.tsumscan.as<uint64_t>() + s.ntiles, 8},
+                      {s.flag.p, 8}};
+  uint64_t got[3];
+  if (fetchwords(stream, f, 3, got))
   {
-    *sumlength = (ncand == 0) ? 0 : ~0ull;
+    return -100;
   }
+  c->nmums = got[0];
+  c->sumlength = got[1];
+  c->flags = got[2];
+  return 0;
+}
+
+// sorter: rocPRIM's radix sort on bits [firstbit, endbit) of the keys (and
+// the flag word zeroed in front of it).
+// keys_in / vals_in: anything rocPRIM can read (pointers, or iterators over
+// rows of pairs as they come out of the exchange: no copy into two arrays)
+template <typename VAL, typename KeyIn, typename ValIn>
+int sort_radix(KeyIn keys_in, ValIn vals_in, SortedPairs &s,
+               unsigned int firstbit, unsigned int endbit, hipStream_t stream)
+{
+  DevBuf temp;
+  VSA_HIP(hipMemsetAsync(s.flag.p, 0, 8, stream));
+  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
+    return rocprim::radix_sort_pairs(p, tb, keys_in, s.k2.as<uint64_t>(),
+                                     vals_in, s.v2.as<VAL>(), (size_t) s.n,
+                                     firstbit, endbit, stream);
+  }));
+  return 0;
+}
+
+// MUMs of a packed candidate list: keys and values as PairRecord (rec) reads
+// them (k_query_search with packbits), so the candidates never exist as
+// 32-byte records.  Sorted by dbstart alone and filtered by runs; a run that
+// is too long for that (or allbits: the caller knows of one) sends the list
+// through the sort on all bits.
+template <typename VAL, typename KeyIn, typename ValIn>
+int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
+                     PairRecord<VAL> rec, unsigned int dbbits, uint64_t carry,
+                     bool allbits, hipStream_t stream, DevBuf &mums,
+                     MumCounts *c)
+{
+  *c = MumCounts();
   if (ncand == 0)
   {
     return 0;
   }
-  DevBuf ends, dbright, keep, temp, dcount, sorted, k1, k2, i1, i2;
-  bool onkeys = false; // the filter runs on the sorted composite keys
-  if (ends.alloc(ncand * 8) || dbright.alloc(ncand * 8) ||
-      keep.alloc(ncand) || dcount.alloc(sizeof(MaxPair) + 16))
+  SortedPairs s;
+  if (s.alloc(ncand, sizeof(VAL), mums))
   {
     return -100;
   }
-  // how many bits do dbstart and length need?
-  MaxPair mx;
-  mx.db = dbbound;
-  mx.len = lenbound;
-  if (dbbound == 0 || lenbound == 0)
+  const unsigned int endbit = rec.lenbits + dbbits;
+  if (!allbits)
   {
-    auto in = rocprim::make_transform_iterator(cand.as<vsa_match>(),
-                                               MaxPairOf());
-    MaxPair init;
-    init.db = init.len = 0;
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::reduce(p, tb, in, dcount.as<MaxPair>(), init,
-                             (size_t) ncand, MaxPairOp(), stream);
-    }));
-    VSA_HIP(hipMemcpyAsync(&mx, dcount.p, sizeof mx, hipMemcpyDeviceToHost,
-                           stream));
-    VSA_HIP(hipStreamSynchronize(stream));
+    if (sort_radix<VAL>(keys_in, vals_in, s, rec.lenbits, endbit, stream) ||
+        mumfilter_tiles<false>(s, rec.lenbits, carry, rec, stream, mums, c))
+    {
+      return -100;
+    }
+    allbits = (c->flags & 1u) != 0;
   }
-  const unsigned int lenbits = bitsfor(mx.len), dbbits = bitsfor(mx.db);
-  if (lenbits + dbbits <= 64 && ncand < 0xFFFFFFFFull)
+  if (allbits &&
+      (sort_radix<VAL>(keys_in, vals_in, s, 0, endbit, stream) ||
+       mumfilter_tiles<true>(s, rec.lenbits, carry, rec, stream, mums, c)))
   {
-    // one radix sort of (composite key, index) over just the bits in use;
-    // the keys carry all the filter looks at
-    onkeys = true;
-    if (k1.alloc(ncand * 8) || k2.alloc(ncand * 8) || i1.alloc(ncand * 4) ||
-        i2.alloc(ncand * 4))
-    {
-      return -100;
-    }
-    k_mum_compositekeys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        cand.as<vsa_match>(), ncand, lenbits, k1.as<uint64_t>(),
-        i1.as<uint32_t>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::radix_sort_pairs(p, tb, k1.as<uint64_t>(),
-                                       k2.as<uint64_t>(), i1.as<uint32_t>(),
-                                       i2.as<uint32_t>(), (size_t) ncand, 0u,
-                                       lenbits + dbbits, stream);
-    }));
-    k_mum_keyends<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        k2.as<uint64_t>(), ncand, lenbits, ends.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-  } else
-  {
-    // wide values: least significant key first (length descending), then a
-    // stable sort by dbstart
-    DevBuf kout;
-    if (k1.alloc(ncand * 8) || k2.alloc(ncand * 8) || kout.alloc(ncand * 8) ||
-        sorted.alloc(ncand * sizeof(vsa_match)))
-    {
-      return -100;
-    }
-    k_mum_keys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        cand.as<vsa_match>(), ncand, k1.as<uint64_t>(), k2.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    if (sortbykey(k1.as<uint64_t>(), kout.as<uint64_t>(),
-                  cand.as<vsa_match>(), sorted.as<vsa_match>(), ncand, 64,
-                  stream))
-    {
-      return -100;
-    }
-    k_mum_keys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        sorted.as<vsa_match>(), ncand, k1.as<uint64_t>(), k2.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
-    if (sortbykey(k2.as<uint64_t>(), kout.as<uint64_t>(),
-                  sorted.as<vsa_match>(), cand.as<vsa_match>(), ncand, 64,
-                  stream))
-    {
-      return -100;
-    }
-    VSA_HIP(hipMemcpyAsync(sorted.p, cand.p, ncand * sizeof(vsa_match),
-                           hipMemcpyDeviceToDevice, stream));
-    k_mum_rightends<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        sorted.as<vsa_match>(), ncand, ends.as<uint64_t>());
-    VSA_HIP(hipGetLastError());
+    return -100;
   }
+  return 0;
+}
+
+// wide records (dbstart and length do not fit into one key, or 2^32
+// candidates and more): least significant key first (length descending), then
+// a stable sort by dbstart; the filter on the sorted records
+int mumfilter_wide(DevBuf &cand, uint64_t ncand, uint64_t carry,
+                   hipStream_t stream, DevBuf &mums, uint64_t *nmums)
+{
+  DevBuf ends, dbright, keep, temp, dcount, sorted, k1, k2, kout;
+  if (ends.alloc(ncand * 8) || dbright.alloc(ncand * 8) ||
+      keep.alloc(ncand) || dcount.alloc(8) || k1.alloc(ncand * 8) ||
+      k2.alloc(ncand * 8) || kout.alloc(ncand * 8) ||
+      sorted.alloc(ncand * sizeof(vsa_match)) ||
+      mums.alloc(ncand * sizeof(vsa_match)))
+  {
+    return -100;
+  }
+  k_mum_keys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+      cand.as<vsa_match>(), ncand, k1.as<uint64_t>(), k2.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  if (sortbykey(k1.as<uint64_t>(), kout.as<uint64_t>(), cand.as<vsa_match>(),
+                sorted.as<vsa_match>(), ncand, 64, stream))
+  {
+    return -100;
+  }
+  k_mum_keys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+      sorted.as<vsa_match>(), ncand, k1.as<uint64_t>(), k2.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  if (sortbykey(k2.as<uint64_t>(), kout.as<uint64_t>(),
+                sorted.as<vsa_match>(), cand.as<vsa_match>(), ncand, 64,
+                stream))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemcpyAsync(sorted.p, cand.p, ncand * sizeof(vsa_match),
+                         hipMemcpyDeviceToDevice, stream));
+  k_mum_rightends<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+      sorted.as<vsa_match>(), ncand, ends.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
   VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
     return rocprim::exclusive_scan(p, tb, ends.as<uint64_t>(),
                                    dbright.as<uint64_t>(), carry,
                                    (size_t) ncand, rocprim::maximum<uint64_t>(),
                                    stream);
   }));
-  if (maxright != nullptr)
-  {
-    // sorted by dbstart, so the running maximum behind the last element
-    uint64_t lastend = 0, lastmax = 0;
-    VSA_HIP(hipMemcpyAsync(&lastend, ends.as<uint64_t>() + ncand - 1, 8,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipMemcpyAsync(&lastmax, dbright.as<uint64_t>() + ncand - 1, 8,
-                           hipMemcpyDeviceToHost, stream));
-    VSA_HIP(hipStreamSynchronize(stream));
-    *maxright = std::max(lastend, lastmax);
-  }
-  if (mums.alloc(ncand * sizeof(vsa_match)))
-  {
-    return -100;
-  }
-  if (onkeys)
-  {
-    DevBuf slots;
-    uint64_t hsum = 0;
-    if (slots.alloc(ncand * 4))
-    {
-      return -100;
-    }
-    k_mum_keyflags<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-        k2.as<uint64_t>(), dbright.as<uint64_t>(), ncand, lenbits,
-        keep.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    auto keepit =
-        rocprim::make_transform_iterator(keep.as<uint8_t>(), KeepToU32());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::exclusive_scan(p, tb, keepit, slots.as<uint32_t>(),
-                                     (uint32_t) 0, (size_t) ncand,
-                                     rocprim::plus<uint32_t>(), stream);
-    }));
-    DevBuf blocksum;
-    const size_t nblocks = blocksfor(ncand);
-    if (blocksum.alloc(vsa_grid_blocks(nblocks) * 8))
-    {
-      return -100;
-    }
-    k_mum_writekept<<<vsa_grid(nblocks), VSA_BLOCK, 0, stream>>>(
-        cand.as<vsa_match>(), i2.as<uint32_t>(), keep.as<uint8_t>(),
-        slots.as<uint32_t>(), ncand, mums.as<vsa_match>(),
-        dcount.as<uint64_t>(), blocksum.as<unsigned long long>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::reduce(p, tb, blocksum.as<unsigned long long>(),
-                             dcount.as<unsigned long long>() + 1, 0ull, nblocks,
-                             rocprim::plus<unsigned long long>(), stream);
-    }));
-    {
-      const Fetch f[2] = {{dcount.p, 8}, {dcount.as<uint64_t>() + 1, 8}};
-      uint64_t got[2];
-      if (fetchwords(stream, f, 2, got))
-      {
-        return -100;
-      }
-      *nmums = got[0];
-      hsum = got[1];
-    }
-    if (sumlength != nullptr)
-    {
-      *sumlength = hsum;
-    }
-    return 0;
-  }
   k_mum_flags<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
       sorted.as<vsa_match>(), ends.as<uint64_t>(), dbright.as<uint64_t>(),
       ncand, keep.as<uint8_t>());
@@ -470,172 +465,75 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
   return 0;
 }
 
-// The filter of mumuniqueinquery on a packed candidate list: keys =
-// dbstart << lenbits | (2^lenbits - 1 - length), values = queryseq << 16 |
-// querystart (k_query_search with packbits).  One sort of the pairs, the
-// filter on the keys, and the surviving pairs become the records: the
-// candidates never exist as 32-byte records.
-// keys_in / vals_in: anything rocPRIM can read (pointers, or iterators over
-// rows of pairs as they come out of the exchange: no copy into two arrays)
-// presort(k2, v2, flag) (optional): delivers the first attempt's order in
-// place of rocPRIM's sort without keys_in / vals_in, or raises a bit of *flag
-// (candidate_bucketsort).  With one, a raised flag word ends the call: it
-// returns VSA_PRESORT_GAVE_UP with the word in *nmums, and the caller comes
-// again with the list (firstpass = 1 if only "a run was too long" is up: the
-// second attempt at once).
-#define VSA_PRESORT_GAVE_UP 1
-template <typename VAL = uint64_t, typename KeyIn = const uint64_t *,
-          typename ValIn = const VAL *, typename Presort = std::nullptr_t>
-int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
-                     unsigned int lenbits, unsigned int dbbits,
-                     hipStream_t stream, DevBuf &mums, uint64_t *nmums,
-                     uint64_t *sumlength, uint64_t carry = 0,
-                     unsigned int valbits = 0, uint64_t seqoffset = 0,
-                     Presort presort = nullptr, int firstpass = 0)
+// MUMs of candidate records, any order.  carry: see mumfilter_tiles.
+// dbbound / lenbound: upper bounds of dbstart and length if the caller knows
+// them (index length, longest query), else 0: they are looked up.
+// *sumlength = sum of the lengths of the MUMs, or ~0 if this call did not
+// compute it (the wide form).
+int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
+                     DevBuf &mums, uint64_t *nmums, uint64_t *sumlength,
+                     uint64_t carry = 0, uint64_t dbbound = 0,
+                     uint64_t lenbound = 0)
 {
-  constexpr bool havepresort = !std::is_same<Presort, std::nullptr_t>::value;
-  // VAL, valbits, seqoffset: see k_mum_writepacked
-  // carry: as for mumuniqueinquery
   *nmums = 0;
   *sumlength = 0;
   if (ncand == 0)
   {
     return 0;
   }
-  DevBuf k2, v2, dbright, keep, slots, temp, dcount, blocksum;
-  const size_t nblocks = blocksfor(ncand);
-  // the passes behind the sort run by tiles (mum_filter.inc); the rocPRIM
-  // scans of round 2 are what the rare second pass falls back on
-  const uint64_t ntiles = (ncand + VSA_FT_TILE - 1) / VSA_FT_TILE;
-  DevBuf tmax, tcarry, tcount, toff, tsum, tsumscan;
-  if (tmax.alloc((ntiles + 1) * 8) || tcarry.alloc((ntiles + 1) * 8) ||
-      tcount.alloc((ntiles + 1) * 8) || toff.alloc((ntiles + 1) * 8) ||
-      tsum.alloc((ntiles + 1) * 8) || tsumscan.alloc((ntiles + 1) * 8))
+  // how many bits do dbstart and length need?
+  MaxPair mx;
+  mx.db = dbbound;
+  mx.len = lenbound;
+  if (dbbound == 0 || lenbound == 0)
   {
-    return -100;
-  }
-  if (k2.alloc(ncand * 8) || v2.alloc(ncand * sizeof(VAL)) ||
-      keep.alloc(ntiles * VSA_FT_TILE) || dcount.alloc(24) ||
-      blocksum.alloc(vsa_grid_blocks(nblocks) * 8) ||
-      mums.alloc(ncand * sizeof(vsa_match)))
-  {
-    return -100;
-  }
-  // Sorted by dbstart alone where the runs of equal dbstarts are short (see
-  // k_mumf_flags; decided afterwards from a flag that comes back with the
-  // counts), by (dbstart, length down) otherwise.
-  uint64_t got[3] = {0, 0, 0};
-  for (int pass = firstpass; pass < 2; pass++)
-  {
-    const bool byruns = pass == 0;
-    const unsigned int firstbit = byruns ? lenbits : 0u;
-    bool sorted = false;
-    VSA_HIP(hipMemsetAsync(dcount.p, 0, 24, stream));
-    if constexpr (havepresort)
-    {
-      if (byruns)
-      {
-        if (presort(k2.as<uint64_t>(), v2.as<VAL>(),
-                    dcount.as<unsigned int>() + 4))
-        {
-          return -100;
-        }
-        sorted = true;
-      }
-    }
-    if (!sorted)
-    {
-      VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-        return rocprim::radix_sort_pairs(p, tb, keys_in, k2.as<uint64_t>(),
-                                         vals_in, v2.as<VAL>(), (size_t) ncand,
-                                         firstbit, lenbits + dbbits, stream);
-      }));
-    }
-    if (byruns)
-    {
-      const dim3 tg = vsa_grid(ntiles);
-      k_mumf_tilemax<<<tg, VSA_BLOCK, 0, stream>>>(
-          k2.as<uint64_t>(), ncand, lenbits, tmax.as<uint64_t>());
-      k_mumf_scan<1><<<1, VSA_BLOCK, 0, stream>>>(
-          tmax.as<uint64_t>(), ntiles, carry, tcarry.as<uint64_t>());
-      k_mumf_flags<<<tg, VSA_BLOCK, 0, stream>>>(
-          k2.as<uint64_t>(), ncand, lenbits, tcarry.as<uint64_t>(),
-          keep.as<uint8_t>(), tcount.as<uint64_t>(), tsum.as<uint64_t>(),
-          dcount.as<unsigned int>() + 4);
-      // (offsets of the tiles and, in a second workgroup, the sum of the
-      // lengths)
-      k_mumf_scan<0><<<2, VSA_BLOCK, 0, stream>>>(
-          tcount.as<uint64_t>(), ntiles, 0, toff.as<uint64_t>(),
-          tsum.as<uint64_t>(), tsumscan.as<uint64_t>());
-      k_mumf_write<VAL><<<tg, VSA_BLOCK, 0, stream>>>(
-          k2.as<uint64_t>(), v2.as<VAL>(), keep.as<uint8_t>(), ncand,
-          toff.as<uint64_t>(), lenbits, valbits, seqoffset,
-          mums.as<vsa_match>());
-      VSA_HIP(hipGetLastError());
-      // number of MUMs, sum of their lengths, "a run was too long"
-      const Fetch f[3] = {{toff.as<uint64_t>() + ntiles, 8},
-                          {tsumscan.as<uint64_t>() + ntiles, 8},
-                          {dcount.as<uint64_t>() + 2, 8}};
-      if (fetchwords(stream, f, 3, got))
-      {
-        return -100;
-      }
-      if (got[2] == 0)
-      {
-        break;
-      }
-      if constexpr (havepresort)
-      {
-        *nmums = got[2];
-        return VSA_PRESORT_GAVE_UP;
-      }
-      continue;
-    }
-    // a run of more than 64 equal dbstarts: sorted on all bits by now
-    if (dbright.alloc(ncand * 8) || slots.alloc(ncand * 4))
+    DevBuf temp, dmax;
+    if (dmax.alloc(sizeof(MaxPair)))
     {
       return -100;
     }
-    // running maximum of the right ends, which are a function of the keys
-    auto ends = rocprim::make_transform_iterator(k2.as<uint64_t>(),
-                                                 KeyToRightEnd{lenbits});
+    auto in = rocprim::make_transform_iterator(cand.as<vsa_match>(),
+                                               MaxPairOf());
+    MaxPair init;
+    init.db = init.len = 0;
     VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::exclusive_scan(p, tb, ends, dbright.as<uint64_t>(), carry,
-                                     (size_t) ncand,
-                                     rocprim::maximum<uint64_t>(), stream);
+      return rocprim::reduce(p, tb, in, dmax.as<MaxPair>(), init,
+                             (size_t) ncand, MaxPairOp(), stream);
     }));
-    k_mum_keyflags<<<vsa_grid(nblocks), VSA_BLOCK, 0, stream>>>(
-        k2.as<uint64_t>(), dbright.as<uint64_t>(), ncand, lenbits,
-        keep.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    auto keepit =
-        rocprim::make_transform_iterator(keep.as<uint8_t>(), KeepToU32());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::exclusive_scan(p, tb, keepit, slots.as<uint32_t>(),
-                                     (uint32_t) 0, (size_t) ncand,
-                                     rocprim::plus<uint32_t>(), stream);
-    }));
-    k_mum_writepacked<VAL><<<vsa_grid(nblocks), VSA_BLOCK, 0, stream>>>(
-        k2.as<uint64_t>(), v2.as<VAL>(), keep.as<uint8_t>(),
-        slots.as<uint32_t>(), ncand, lenbits, valbits, seqoffset,
-        mums.as<vsa_match>(), dcount.as<uint64_t>(),
-        blocksum.as<unsigned long long>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::reduce(p, tb, blocksum.as<unsigned long long>(),
-                             dcount.as<unsigned long long>() + 1, 0ull, nblocks,
-                             rocprim::plus<unsigned long long>(), stream);
-    }));
-    const Fetch f[3] = {{dcount.p, 8}, {dcount.as<uint64_t>() + 1, 8},
-                        {dcount.as<uint64_t>() + 2, 8}};
-    if (fetchwords(stream, f, 3, got))
-    {
-      return -100;
-    }
-    break; // (the second pass: sorted on all bits, nothing left to decide)
+    VSA_HIP(hipMemcpyAsync(&mx, dmax.p, sizeof mx, hipMemcpyDeviceToHost,
+                           stream));
+    VSA_HIP(hipStreamSynchronize(stream));
   }
-  *nmums = got[0];
-  *sumlength = got[1];
+  const unsigned int lenbits = bitsfor(mx.len), dbbits = bitsfor(mx.db);
+  if (lenbits + dbbits > 64 || ncand >= 0xFFFFFFFFull)
+  {
+    *sumlength = ~0ull;
+    return mumfilter_wide(cand, ncand, carry, stream, mums, nmums);
+  }
+  // sorter: (composite key, index) over just the bits in use; the pair list
+  // of the records
+  SortedPairs s;
+  DevBuf k1, i1;
+  MumCounts c;
+  if (s.alloc(ncand, 4, mums) || k1.alloc(ncand * 8) ||
+      i1.alloc(ncand * 4))
+  {
+    return -100;
+  }
+  k_mum_compositekeys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+      cand.as<vsa_match>(), ncand, lenbits, k1.as<uint64_t>(),
+      i1.as<uint32_t>());
+  VSA_HIP(hipGetLastError());
+  if (sort_radix<uint32_t>(k1.as<uint64_t>(), i1.as<uint32_t>(), s, 0,
+                           lenbits + dbbits, stream) ||
+      mumfilter_tiles<true>(s, lenbits, carry,
+                            GatheredRecord{cand.as<vsa_match>()}, stream,
+                            mums, &c))
+  {
+    return -100;
+  }
+  *nmums = c.nmums;
+  *sumlength = c.sumlength;
   return 0;
 }
 
@@ -1262,11 +1160,10 @@ bool feedsbuckets(const QueryRun &st)
   return true;
 }
 
-// MUMs of a packed run through the bucket sort; VSA_PRESORT_GAVE_UP (and the
-// flag word in *nm) if the list has to go through compact() and rocPRIM
+// MUMs of a packed run through the bucket sort and the filter by runs;
+// c->flags != 0: the list has to go through compact() and rocPRIM
 template <typename VAL>
-int mumfilter_buckets(QueryRun &st, DevBuf &mums, uint64_t *nm,
-                      uint64_t *mumsum)
+int mumfilter_buckets(QueryRun &st, DevBuf &mums, MumCounts *c)
 {
   const RecordForm &rec = st.rec;
   const uint64_t total = st.needed + st.nplan + st.nfirst;
@@ -1286,25 +1183,26 @@ int mumfilter_buckets(QueryRun &st, DevBuf &mums, uint64_t *nm,
     src.first = {st.wfmlen.as<uint32_t>(), st.wfmdb.as<uint64_t>(),
                  st.queries->nq, st.qs.seqoffset, rec.packbits, rec.valbits};
   }
-  auto presort = [&](uint64_t *k2, VAL *v2, unsigned int *flag) {
-    CsGeometry g;
-    const int rc = candidate_bucketsort<VAL>(src, total, st.index->n,
-                                             rec.lenbits, rec.dbbits, k2, v2,
-                                             flag, st.stream, &g);
-    if (rc == 0)
-    {
-      g_cs_runs++;
-      g_cs_shift = g.shift;
-      g_cs_buckets = g.nbuckets;
-    }
-    return rc;
-  };
-  return mumfilter_packed<VAL>((const uint64_t *) nullptr,
-                               (const VAL *) nullptr, total, rec.lenbits,
-                               rec.dbbits, st.stream, mums, nm, mumsum, 0,
-                               rec.valbits,
-                               sizeof(VAL) == 4 ? st.qs.seqoffset : 0,
-                               presort);
+  SortedPairs s;
+  CsGeometry g;
+  if (s.alloc(total, sizeof(VAL), mums))
+  {
+    return -100;
+  }
+  VSA_HIP(hipMemsetAsync(s.flag.p, 0, 8, st.stream));
+  if (candidate_bucketsort<VAL>(src, total, st.index->n, rec.lenbits,
+                                rec.dbbits, s.k2.as<uint64_t>(),
+                                s.v2.as<VAL>(), s.flag.as<unsigned int>(),
+                                st.stream, &g))
+  {
+    return -100;
+  }
+  g_cs_runs++;
+  g_cs_shift = g.shift;
+  g_cs_buckets = g.nbuckets;
+  const PairRecord<VAL> pr = {rec.lenbits, rec.valbits,
+                              sizeof(VAL) == 4 ? st.qs.seqoffset : 0};
+  return mumfilter_tiles<false>(s, rec.lenbits, 0, pr, st.stream, mums, c);
 }
 
 // the dense list into the result: the pairs themselves, the MUMs behind the
@@ -1315,27 +1213,26 @@ int mumfilter_buckets(QueryRun &st, DevBuf &mums, uint64_t *nm,
 int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
 {
   const RecordForm &rec = st.rec;
-  int firstpass = 0;
+  bool allbits = false; // the packed list at once through its second attempt
   if (feedsbuckets(st))
   {
     DevBuf mums;
-    uint64_t nm = 0;
-    const int rc = rec.valbits != 0
-                       ? mumfilter_buckets<uint32_t>(st, mums, &nm, mumsum)
-                       : mumfilter_buckets<uint64_t>(st, mums, &nm, mumsum);
-    if (rc == 0)
-    {
-      st.index->cs_penalty = 0;
-      res->stats.candidates = st.needed + st.nplan + st.nfirst;
-      res->count = nm;
-      res->matches = (vsa_match *) mums.release();
-      return 0;
-    }
-    if (rc != VSA_PRESORT_GAVE_UP)
+    MumCounts c;
+    if (rec.valbits != 0 ? mumfilter_buckets<uint32_t>(st, mums, &c)
+                         : mumfilter_buckets<uint64_t>(st, mums, &c))
     {
       return -100;
     }
-    if ((nm & VSA_CS_OVERFLOW) != 0)
+    if (c.flags == 0)
+    {
+      st.index->cs_penalty = 0;
+      res->stats.candidates = st.needed + st.nplan + st.nfirst;
+      res->count = c.nmums;
+      res->matches = (vsa_match *) mums.release();
+      *mumsum = c.sumlength;
+      return 0;
+    }
+    if ((c.flags & VSA_CS_OVERFLOW) != 0)
     {
       g_cs_overflows++;
       st.index->cs_penalty =
@@ -1344,7 +1241,7 @@ int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
     } else
     {
       g_cs_longruns++;
-      firstpass = 1; // (the buckets were fine: straight to the second attempt)
+      allbits = true; // (the buckets were fine: a run was too long)
     }
   }
   if (compact(st))
@@ -1365,30 +1262,32 @@ int finish(QueryRun &st, vsa_result *res, uint64_t *mumsum)
   } else if (st.domum && !st.domumcand)
   {
     DevBuf mums;
-    uint64_t nm = 0;
+    MumCounts c = MumCounts();
     int rc;
     if (rec.valbits != 0)
     {
-      rc = mumfilter_packed<uint32_t>(
+      rc = mumfilter_packed(
           st.keys.as<const uint64_t>(), st.out.as<const uint32_t>(), needed,
-          rec.lenbits, rec.dbbits, st.stream, mums, &nm, mumsum, 0,
-          rec.valbits, st.qs.seqoffset, nullptr, firstpass);
+          PairRecord<uint32_t>{rec.lenbits, rec.valbits, st.qs.seqoffset},
+          rec.dbbits, 0, allbits, st.stream, mums, &c);
     } else if (rec.packed)
     {
       rc = mumfilter_packed(st.keys.as<const uint64_t>(),
-                            st.out.as<const uint64_t>(), needed, rec.lenbits,
-                            rec.dbbits, st.stream, mums, &nm, mumsum, 0, 0, 0,
-                            nullptr, firstpass);
+                            st.out.as<const uint64_t>(), needed,
+                            PairRecord<uint64_t>{rec.lenbits, 0, 0},
+                            rec.dbbits, 0, allbits, st.stream, mums, &c);
     } else
     {
-      rc = mumuniqueinquery(st.out, needed, st.stream, mums, &nm, 0, nullptr,
-                            st.index->n, st.queries->maxlength, mumsum);
+      rc = mumuniqueinquery(st.out, needed, st.stream, mums, &c.nmums,
+                            &c.sumlength, 0, st.index->n,
+                            st.queries->maxlength);
     }
     if (rc != 0)
     {
       return -100;
     }
-    res->count = nm;
+    *mumsum = c.sumlength;
+    res->count = c.nmums;
     res->matches = (vsa_match *) mums.release();
   } else if (needed > 0 && !st.ordered && st.domum)
   {
@@ -1690,9 +1589,10 @@ static int mumfilter_entry(void *device_candidates, uint64_t ncandidates,
   Timer tall(stream);
   DevBuf cand, mums;
   cand.p = device_candidates; // borrowed, released below
-  uint64_t nm = 0;
+  uint64_t nm = 0, sum = 0;
   tall.start();
-  const int rc = mumuniqueinquery(cand, ncandidates, stream, mums, &nm, carry);
+  const int rc = mumuniqueinquery(cand, ncandidates, stream, mums, &nm, &sum,
+                                  carry);
   tall.stop();
   cand.release();
   if (rc != 0)
@@ -1706,7 +1606,10 @@ static int mumfilter_entry(void *device_candidates, uint64_t ncandidates,
   res->stats.count = nm;
   res->stats.candidates = ncandidates;
   res->stats.total_device_ms = tall.ms();
-  if (sumlengths(res->matches, nm, stream, &res->stats.sumlength) != 0)
+  res->stats.sumlength = sum;
+  // (the wide form does not sum the lengths)
+  if (sum == ~0ull &&
+      sumlengths(res->matches, nm, stream, &res->stats.sumlength) != 0)
   {
     vsa_result_free(res);
     return -100;
@@ -1800,7 +1703,7 @@ extern "C" int vsa_mumuniqueinquery_range_packed2(const void *device_rows,
   vsa_dev_set_stream(stream);
   Timer tall(stream);
   DevBuf mums;
-  uint64_t nm = 0, sum = 0;
+  MumCounts c = MumCounts();
   const uint64_t total = nrows + nmore;
   tall.start();
   int rc = 0;
@@ -1815,9 +1718,10 @@ extern "C" int vsa_mumuniqueinquery_range_packed2(const void *device_rows,
         rocprim::counting_iterator<size_t>(0), RowWord{rows, more, nrows, 0});
     auto rowvals = rocprim::make_transform_iterator(
         rocprim::counting_iterator<size_t>(0), RowWord{rows, more, nrows, 1});
-    rc = mumfilter_packed<uint64_t>(rowkeys, rowvals, total, lengthbits,
-                                    bitsfor(totallength), stream, mums, &nm,
-                                    &sum, carry_dbright);
+    rc = mumfilter_packed(rowkeys, rowvals, total,
+                          PairRecord<uint64_t>{lengthbits, 0, 0},
+                          bitsfor(totallength), carry_dbright, false, stream,
+                          mums, &c);
   }
   tall.stop();
   if (rc != 0)
@@ -1826,11 +1730,11 @@ extern "C" int vsa_mumuniqueinquery_range_packed2(const void *device_rows,
     return rc;
   }
   (void) hipStreamSynchronize(stream);
-  res->count = nm;
+  res->count = c.nmums;
   res->matches = (vsa_match *) mums.release();
-  res->stats.count = nm;
+  res->stats.count = c.nmums;
   res->stats.candidates = total;
-  res->stats.sumlength = sum;
+  res->stats.sumlength = c.sumlength;
   res->stats.total_device_ms = tall.ms();
   *result = res;
   return 0;

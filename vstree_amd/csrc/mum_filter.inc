@@ -1,65 +1,39 @@
-// K4: MUM candidates -> MUMs -- kernels; included by esa_search.hip (one translation unit:
-// the kernels share the device functions of esa_device.hpp and the host
-// pipelines of esa_search.hip launch them).
-
-// ---------------------------------------------------------------------------
-// K4: MUM candidates -> MUMs (kurtz/cleanMUMcand.c:55-118)
-// ---------------------------------------------------------------------------
-
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_keys(const vsa_match *__restrict__ cand, uint64_t n,
-           uint64_t *__restrict__ keylen, uint64_t *__restrict__ keydb)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    keylen[i] = ~cand[i].length; // decreasing length
-    keydb[i] = cand[i].dbstart;
-  }
-}
-
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_rightends(const vsa_match *__restrict__ cand, uint64_t n,
-                uint64_t *__restrict__ rightend)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    rightend[i] = cand[i].dbstart + cand[i].length - 1;
-  }
-}
-
-// dbright[i] = max(0, rightend[0..i)) is what the reference's running
-// variable holds when it looks at candidate i.  Candidate i survives iff it
-// is not covered (dbright < rightend) and its successor does not end at the
-// same position with the same start.
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_flags(const vsa_match *__restrict__ cand,
-            const uint64_t *__restrict__ rightend,
-            const uint64_t *__restrict__ dbright, uint64_t n,
-            uint8_t *__restrict__ keep)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i >= n)
-  {
-    return;
-  }
-  bool k = dbright[i] < rightend[i];
-  if (k && i + 1 < n)
-  {
-    // dbright[i+1] = rightend[i] here
-    if (rightend[i + 1] == rightend[i] &&
-        cand[i + 1].dbstart == cand[i].dbstart)
-    {
-      k = false;
-    }
-  }
-  keep[i] = k ? 1 : 0;
-}
-
-// ---- the same on the sorted composite keys (dbstart << lenbits | lenmask -
-// length): the filter needs nothing else of a candidate, so the 32-byte
-// records are touched once, when the survivors are written in order
+// K4: MUM candidates -> MUMs (kurtz/cleanMUMcand.c:55-118) -- kernels;
+// included by esa_search.hip (one translation unit: the kernels share the
+// device functions of esa_device.hpp and the host pipelines of esa_search.hip
+// launch them).
+//
+// One filter behind every sort.  A candidate is a key dbstart << lenbits |
+// (2^lenbits - 1 - length) and a value that travels with it; the key carries
+// all the rule looks at.  With the reference's running `dbright` = the largest
+// right end in front of a candidate (carry = its value in front of the list),
+// candidate i survives iff it is not covered (dbright < its right end) and no
+// other candidate with its dbstart is at least as long.  The keys arrive
+//   sorted by dbstart ALONE (the bucket sort, or one radix pass saved): the
+//     reference's order inside a run of equal dbstarts is "longest first", and
+//     of such a run only the longest can survive, and only if no other member
+//     is as long (the others find dbright at or beyond their right end).  That
+//     is decidable without the order: earlier members of a survivor's own run
+//     are shorter than it, so they do not disturb the running maximum, and the
+//     run itself is looked at as a run.  Runs are short (two reads starting at
+//     the same position); a run longer than VSA_RUN_LIMIT raises bit 0 of
+//     *overflow and the caller sorts on all bits instead;
+//   or sorted on ALL bits (that second attempt; records, whose values are
+//     their indices): the longer members of the run are in front and in the
+//     running maximum already, and an equal one, if any, is the next key.
+// Either way the filter is five launches over tiles: a tile of VSA_FT_TILE
+// keys knows the maximum of its right ends without knowing anything else
+// (pass A), one workgroup turns the tile maxima into the running maximum in
+// front of each tile (S1), every tile then decides its candidates for good,
+// counts the survivors and sums their lengths (pass B), one workgroup turns
+// the counts into offsets (S2), and the survivors are written in order (pass
+// C) -- from the pair, or gathered from the caller's 32-byte records, which
+// are touched only there.  (Until round 3: rocPRIM max-scan, flags, rocPRIM
+// sum-scan, writer, reduce -- 0.3 ms for 11.6 M candidates, each pass paying
+// its launch and a look-back chain over thousands of workgroups.)
+//
+// At the end of the file: the three kernels of the wide form, for records
+// whose dbstart and length do not fit into one key.
 
 // right end of a candidate from its sort key
 struct KeyToRightEnd
@@ -72,189 +46,7 @@ struct KeyToRightEnd
   }
 };
 
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_keyends(const uint64_t *__restrict__ key, uint64_t n,
-              unsigned int lenbits, uint64_t *__restrict__ rightend)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    const uint64_t lenmask = (1ull << lenbits) - 1;
-    const uint64_t k = key[i];
-    rightend[i] = (k >> lenbits) + (lenmask - (k & lenmask)) - 1;
-  }
-}
-
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_keyflags(const uint64_t *__restrict__ key,
-               const uint64_t *__restrict__ dbright, uint64_t n,
-               unsigned int lenbits, uint8_t *__restrict__ keep)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i >= n)
-  {
-    return;
-  }
-  const KeyToRightEnd rightend = {lenbits};
-  const uint64_t e = rightend(key[i]);
-  bool k = dbright[i] < e;
-  if (k && i + 1 < n)
-  {
-    if (rightend(key[i + 1]) == e &&
-        (key[i + 1] >> lenbits) == (key[i] >> lenbits))
-    {
-      k = false;
-    }
-  }
-  keep[i] = k ? 1 : 0;
-}
-
-// out[slot[i]] = cand[idx[i]] for the survivors; *nkept and the sum of the
-// lengths per workgroup on the way (no atomics: ~45 k of them on one
-// address cost more than the whole gather)
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_writekept(const vsa_match *__restrict__ cand,
-                const uint32_t *__restrict__ idx,
-                const uint8_t *__restrict__ keep,
-                const uint32_t *__restrict__ slot, uint64_t n,
-                vsa_match *__restrict__ out, uint64_t *__restrict__ nkept,
-                unsigned long long *__restrict__ blocksum)
-{
-  __shared__ unsigned long long part[VSA_BLOCK / 64];
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  unsigned long long len = 0;
-  if (i < n)
-  {
-    const uint32_t k = keep[i], s = slot[i];
-    if (k != 0)
-    {
-      const uint4 *src = reinterpret_cast<const uint4 *>(cand + idx[i]);
-      uint4 *dst = reinterpret_cast<uint4 *>(out + s);
-      const uint4 lo = src[0], hi = src[1];
-      dst[0] = lo;
-      dst[1] = hi;
-      len = ((unsigned long long) lo.y << 32) | lo.x;
-    }
-    if (i == n - 1)
-    {
-      *nkept = (uint64_t) s + k;
-    }
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-  {
-    len += __shfl_xor(len, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0)
-  {
-    part[threadIdx.x >> 6] = len;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    unsigned long long t = 0;
-#pragma unroll
-    for (int w = 0; w < VSA_BLOCK / 64; w++)
-    {
-      t += part[w];
-    }
-    blocksum[vsa_bid()] = t;
-  }
-}
-
-// the survivors of a packed candidate list (sorted keys, values that went
-// with them) as match records, in order
-// VAL = uint64_t: value = queryseq << 16 | querystart; uint32_t: value =
-// query number in the batch << valbits | querystart, queryseq = that number
-// + seqoffset
-template <typename VAL>
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_writepacked(const uint64_t *__restrict__ key,
-                  const VAL *__restrict__ value,
-                  const uint8_t *__restrict__ keep,
-                  const uint32_t *__restrict__ slot, uint64_t n,
-                  unsigned int lenbits, unsigned int valbits,
-                  uint64_t seqoffset, vsa_match *__restrict__ out,
-                  uint64_t *__restrict__ nkept,
-                  unsigned long long *__restrict__ blocksum)
-{
-  __shared__ unsigned long long part[VSA_BLOCK / 64];
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  unsigned long long len = 0;
-  if (i < n)
-  {
-    const uint32_t k = keep[i], s = slot[i];
-    if (k != 0)
-    {
-      const uint64_t lenmask = (1ull << lenbits) - 1;
-      const uint64_t kk = key[i], v = value[i];
-      vsa_match m;
-      m.length = lenmask - (kk & lenmask);
-      m.dbstart = kk >> lenbits;
-      if (sizeof(VAL) == 4)
-      {
-        m.queryseq = (v >> valbits) + seqoffset;
-        m.querystart = v & ((1ull << valbits) - 1);
-      } else
-      {
-        m.queryseq = v >> 16;
-        m.querystart = v & 0xFFFFu;
-      }
-      out[s] = m;
-      len = m.length;
-    }
-    if (i == n - 1)
-    {
-      *nkept = (uint64_t) s + k;
-    }
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-  {
-    len += __shfl_xor(len, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0)
-  {
-    part[threadIdx.x >> 6] = len;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    unsigned long long t = 0;
-#pragma unroll
-    for (int w = 0; w < VSA_BLOCK / 64; w++)
-    {
-      t += part[w];
-    }
-    blocksum[vsa_bid()] = t;
-  }
-}
-
-// The flags for keys sorted by dbstart ONLY (one radix pass saved: the
-// length bits are not sorted on), as k_mumf_flags below computes them.  The reference's order inside a run of
-// equal dbstarts is "longest first", and of such a run only the longest can
-// survive, and only if no other member is as long (cleanMUMcand.c:65-116: the
-// others find dbright at or beyond their right end).  That is decidable
-// without the order: a candidate survives iff the running maximum of the
-// right ends in front of it -- earlier members of its own run are shorter
-// than a survivor, so they do not disturb the test -- is below its right
-// end, and no other member of its run is at least as long.  Runs are short
-// (two reads starting at the same position); a run longer than
-// VSA_RUN_LIMIT raises *overflow and the caller sorts on all bits instead.
 #define VSA_RUN_LIMIT 64
-
-// ---- the filter behind the sort in three streaming passes (round 3) ---------
-//
-// Until round 3 the sorted keys went through five kernels -- rocPRIM exclusive
-// max-scan of the right ends, flags, rocPRIM exclusive sum-scan of the flags,
-// the writer, a reduce -- 0.3 ms for 11.6 M candidates, each pass paying its
-// launch and a look-back chain over thousands of workgroups for 93 MB of keys.
-// The two scans are scans over TILES here: a tile of VSA_FT_TILE keys knows
-// the maximum of its right ends without knowing anything else (pass A), one
-// workgroup turns the tile maxima into the running maximum in front of each
-// tile (S1), every tile then decides its candidates for good and counts the
-// survivors (pass B), one workgroup turns the counts into offsets (S2), and
-// the survivors are written (pass C, which also sums their lengths per tile).
 #define VSA_FT_ITEMS 4
 #define VSA_FT_TILE (VSA_BLOCK * VSA_FT_ITEMS)
 
@@ -380,9 +172,11 @@ k_mumf_scan(const uint64_t *__restrict__ in, uint64_t count, uint64_t start,
   }
 }
 
-// pass B: keep flags (the test for runs described above, with the running
-// maximum from the tile's carry and the keys in front inside the tile) and the
-// number of survivors per tile
+// pass B: keep flags (the running maximum from the tile's carry and the keys
+// in front inside the tile; SORTED: keys sorted on all bits, else on dbstart
+// alone, see above), the number of survivors and the sum of their lengths per
+// tile.  The SORTED form does not touch *overflow.
+template <bool SORTED>
 __global__ void __launch_bounds__(VSA_BLOCK)
 k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
              unsigned int lenbits, const uint64_t *__restrict__ tilecarry,
@@ -417,7 +211,11 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
   {
     const uint64_t i = i0 + k;
     bool ok = i < n && run < e[k];
-    if (ok)
+    if (SORTED)
+    {
+      // (same dbstart and same length = same key)
+      ok = ok && !(i + 1 < n && key[i + 1] == kk[k]);
+    } else if (ok)
     {
       const uint64_t d = kk[k] >> lenbits;
       uint32_t steps = 0;
@@ -466,17 +264,59 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
   }
 }
 
+// What pass C makes of a survivor.  From its pair -- VAL = uint64_t: value =
+// queryseq << 16 | querystart; uint32_t: value = query number in the batch <<
+// valbits | querystart, queryseq = that number + seqoffset:
+template <typename V>
+struct PairRecord
+{
+  using VAL = V;
+  unsigned int lenbits, valbits;
+  uint64_t seqoffset;
+  __device__ void operator()(uint64_t kkey, uint64_t v, vsa_match *dst) const
+  {
+    const uint64_t lenmask = (1ull << lenbits) - 1;
+    vsa_match m;
+    m.length = lenmask - (kkey & lenmask);
+    m.dbstart = kkey >> lenbits;
+    if (sizeof(VAL) == 4)
+    {
+      m.queryseq = (v >> valbits) + seqoffset;
+      m.querystart = v & ((1ull << valbits) - 1);
+    } else
+    {
+      m.queryseq = v >> 16;
+      m.querystart = v & 0xFFFFu;
+    }
+    *dst = m;
+  }
+};
+
+// ... or the caller's record whose index the value is
+struct GatheredRecord
+{
+  using VAL = uint32_t;
+  const vsa_match *cand;
+  __device__ void operator()(uint64_t, uint64_t v, vsa_match *dst) const
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(cand + v);
+    const uint4 lo = src[0], hi = src[1];
+    reinterpret_cast<uint4 *>(dst)[0] = lo;
+    reinterpret_cast<uint4 *>(dst)[1] = hi;
+  }
+};
+
 // pass C: the survivors as records, in order.  A tile is walked in rows of
 // VSA_BLOCK consecutive candidates, one per thread, so that the records of
 // neighbouring lanes lie next to each other in the output (four consecutive
 // candidates per thread wrote 32 bytes per lane 128 bytes apart: 188 us
 // instead of 100 for the 11 M records of the headline batch)
-template <typename VAL>
+template <typename WRITER>
 __global__ void __launch_bounds__(VSA_BLOCK)
-k_mumf_write(const uint64_t *__restrict__ key, const VAL *__restrict__ value,
+k_mumf_write(const uint64_t *__restrict__ key,
+             const typename WRITER::VAL *__restrict__ value,
              const uint8_t *__restrict__ keep, uint64_t n,
-             const uint64_t *__restrict__ tileoff, unsigned int lenbits,
-             unsigned int valbits, uint64_t seqoffset,
+             const uint64_t *__restrict__ tileoff, WRITER write,
              vsa_match *__restrict__ out)
 {
   if (vsa_bid() * VSA_FT_TILE >= n) // (a launch folded into two dimensions)
@@ -484,7 +324,6 @@ k_mumf_write(const uint64_t *__restrict__ key, const VAL *__restrict__ value,
     return;
   }
   __shared__ uint64_t sh[VSA_BLOCK / 64 + 1];
-  const uint64_t lenmask = (1ull << lenbits) - 1;
   uint64_t base = tileoff[vsa_bid()];
 #pragma unroll
   for (int r = 0; r < VSA_FT_ITEMS; r++)
@@ -497,20 +336,61 @@ k_mumf_write(const uint64_t *__restrict__ key, const VAL *__restrict__ value,
     base += total;
     if (k)
     {
-      const uint64_t kkey = key[i], v = value[i];
-      vsa_match m;
-      m.length = lenmask - (kkey & lenmask);
-      m.dbstart = kkey >> lenbits;
-      if (sizeof(VAL) == 4)
-      {
-        m.queryseq = (v >> valbits) + seqoffset;
-        m.querystart = v & ((1ull << valbits) - 1);
-      } else
-      {
-        m.queryseq = v >> 16;
-        m.querystart = v & 0xFFFFu;
-      }
-      out[slot] = m;
+      write(key[i], value[i], out + slot);
     }
   }
+}
+
+// ---- wide records: dbstart and length as two sort keys, the filter on the
+// sorted records themselves (mumfilter_wide)
+
+__global__ void __launch_bounds__(VSA_BLOCK)
+k_mum_keys(const vsa_match *__restrict__ cand, uint64_t n,
+           uint64_t *__restrict__ keylen, uint64_t *__restrict__ keydb)
+{
+  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
+  if (i < n)
+  {
+    keylen[i] = ~cand[i].length; // decreasing length
+    keydb[i] = cand[i].dbstart;
+  }
+}
+
+__global__ void __launch_bounds__(VSA_BLOCK)
+k_mum_rightends(const vsa_match *__restrict__ cand, uint64_t n,
+                uint64_t *__restrict__ rightend)
+{
+  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
+  if (i < n)
+  {
+    rightend[i] = cand[i].dbstart + cand[i].length - 1;
+  }
+}
+
+// dbright[i] = max(0, rightend[0..i)) is what the reference's running
+// variable holds when it looks at candidate i.  Candidate i survives iff it
+// is not covered (dbright < rightend) and its successor does not end at the
+// same position with the same start.
+__global__ void __launch_bounds__(VSA_BLOCK)
+k_mum_flags(const vsa_match *__restrict__ cand,
+            const uint64_t *__restrict__ rightend,
+            const uint64_t *__restrict__ dbright, uint64_t n,
+            uint8_t *__restrict__ keep)
+{
+  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
+  if (i >= n)
+  {
+    return;
+  }
+  bool k = dbright[i] < rightend[i];
+  if (k && i + 1 < n)
+  {
+    // dbright[i+1] = rightend[i] here
+    if (rightend[i + 1] == rightend[i] &&
+        cand[i + 1].dbstart == cand[i].dbstart)
+    {
+      k = false;
+    }
+  }
+  keep[i] = k ? 1 : 0;
 }
