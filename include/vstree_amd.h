@@ -293,6 +293,11 @@ const void *vsa_result_device_matches(const vsa_result *result);
 int vsa_result_copy_device(const vsa_result *result, void *device_matches,
                            uint64_t capacity);
 void vsa_result_free(vsa_result *result);
+/* a match list from host memory (fetched earlier, filtered or made by the
+   caller) as a result on HIP device `device`: for the consumers of results
+   that stay on the device (vsa_coverage_mark) */
+int vsa_result_from_host(const vsa_match *matches, uint64_t count, int device,
+                         vsa_result **result);
 
 /* ---- the engine: Vmengine/vmengineexport.h:4-81 ----------------------- */
 
@@ -795,6 +800,175 @@ int64_t vsa_sink_format(vsa_sink *sink, const vsa_match *matches, uint64_t n,
 /* the same to a FILE * */
 int vsa_sink_write(vsa_sink *sink, const vsa_match *matches, uint64_t n,
                    void *file);
+
+/* ---- match coverage: vmatch -dbnomatch / -qnomatch / -dbmaskmatch /
+   -qmaskmatch (Vmatch/markmat.c, nomatch.c, showmasked.c,
+   initpost.c:28-74,156-267) on match lists that stay in HBM ---------------
+
+   A vsa_coverage is the reference's marktable (Markinfo.markmatchtable,
+   Vmatch/markinfo.h) in device memory, in a layout of our own: ONE BIT PER
+   POSITION of a Multiseq, position p = bit (p & 63) of the 64-bit word
+   p >> 6 (LSB first), the bits behind the last position 0.  Word index and
+   bit arithmetic are 64 bit: tables of 2^32 bits and more are addressed like
+   the others.  The positions of the separators are set from the start
+   (initmarktable, markmat.c:15-28), so no run of clear bits spans two
+   sequences. */
+
+typedef struct vsa_coverage vsa_coverage;
+
+/* initmarktable over the Multiseq of the index: totallength bits, the
+   numofsequences - 1 separator positions set */
+int vsa_coverage_open_index(const vsa_index *index, vsa_coverage **coverage);
+/* ... over the query Multiseq as the reference lays it out
+   (kurtz-basic/multiseq.c:129-166): sequence i starts at the sum of
+   (length_j + 1) over j < i, whatever the batch looks like in memory (byte
+   batches, uniform and dense batches, packed batches).  The offset of the
+   batch (vsa_queries_set_offset) at the time of the call is subtracted from
+   the queryseq of every match marked later. */
+int vsa_coverage_open_queries(const vsa_queries *queries,
+                              vsa_coverage **coverage);
+void vsa_coverage_close(vsa_coverage *coverage);
+uint64_t vsa_coverage_numofbits(const vsa_coverage *coverage);
+
+#define VSA_COVERAGE_QUERY  0 /* dbstart absolute, queryseq / querystart
+                                 relative, length for both instances:
+                                 vsa_findquerymatches, vsa_findcompletematches */
+#define VSA_COVERAGE_SELF   1 /* dbstart = start1, queryseq = start2, both
+                                 absolute in the index: maximal, supermaximal
+                                 and tandem repeats, self-index MUMs          */
+#define VSA_COVERAGE_APPROX 2 /* vsa_findapproxcompletematches: database
+                                 instance only, length = length1, the
+                                 querystart field is a distance               */
+#define VSA_COVERAGE_DATABASE 0 /* -dbnomatch / -dbmaskmatch: markdb = True  */
+#define VSA_COVERAGE_QUERIES  1 /* -qnomatch / -qmaskmatch:   markdb = False */
+
+/* an instance of at least this many positions is set by a whole wavefront,
+   a shorter one by the lane that holds its record */
+#define VSA_COVERAGE_COOP_THRESHOLD 1024u
+uint64_t vsa_coverage_coop_threshold(void);
+/* positions one workgroup of the extraction kernels looks at */
+#define VSA_COVERAGE_EXTRACT_TILE 65536u
+
+/*
+  Markfields (Vmatch/markinfo.h:13-23) and what markmatches
+  (Vmatch/markmat.c:42-118) reads besides: the four keep flags are 1 by
+  default (DEFAULTMARKFIELDS, Vmatch/parsevm.c:83-87); `keepleft` clears
+  markleft, `keepright` markright, `keepleftifsamesequence`
+  markleftifdifferentsequence, `keeprightifsamesequence`
+  markrightifdifferentsequence (Vmatch/keepflags.c:9-27).
+    self layout   hasnoqueryfiles holds: both instances go into the table of
+                  the index -- the left one if markleft and (markleftif... or
+                  the two sequence numbers differ), the right one likewise.
+                  On an index with queries Storeposition2 and Storeseqnum2
+                  count from the first query sequence (procfinal.c:463-469);
+                  the database side marks the right instance at that relative
+                  position, as the reference does; the query side needs such
+                  an index ("option -qnomatch requires index containing query
+                  sequences or option -q", initpost.c:48-62) and marks the
+                  right instance at its absolute position.
+    query layout  (-q) the database side marks the left instance if markleft,
+                  the query side the right instance in a table over the
+                  queries, moved to seqlength - (querystart + length) if
+                  palindromic (procfinal.c:152-158).  The two same-sequence
+                  flags must be 1: with -q their keywords are the reference's
+                  error (parsevm.c:70-80), which is returned (-2).
+    approximate   the database side like the query layout.
+  VSA_NOT_COVERED, table untouched: a packed-pair result; selfpalindromic
+  lists; the query side of -complete lists (complete != 0 or the approximate
+  layout: the reference marks query offsets in a table of the database there,
+  initpost.c:25-26,66-70).
+*/
+typedef struct
+{
+  int layout;          /* VSA_COVERAGE_QUERY | _SELF | _APPROX             */
+  int side;            /* VSA_COVERAGE_DATABASE | _QUERIES                  */
+  int palindromic;     /* matches of the reverse-complement pass (-p)      */
+  int selfpalindromic; /* vmatch -p IDX: not covered                       */
+  int complete;        /* the list comes from vsa_findcompletematches      */
+  int markleft, markright;
+  int markleftifdifferentsequence, markrightifdifferentsequence;
+} vsa_coverageparams;
+
+/* markmatches for every record of the list; several calls accumulate */
+int vsa_coverage_mark(vsa_coverage *coverage, const vsa_result *result,
+                      const vsa_coverageparams *params);
+/* dst |= src: tables of equal size on the same device (several lists,
+   several batches, or -- after a copy the caller makes -- several GPUs) */
+int vsa_coverage_merge(vsa_coverage *dst, const vsa_coverage *src);
+
+typedef struct
+{
+  uint64_t positions;  /* of the Multiseq without its separators: the
+                          "sequence length" of showmaskedseq's last line
+                          (Vmatch/showmasked.c:137-153)                    */
+  uint64_t marked;     /* ... of them marked: "number of masked symbols"   */
+  uint64_t separators;
+  double mark_ms;      /* HIP-event time of the last vsa_coverage_mark     */
+  double extract_ms;   /* ... of the last vsa_coverage_nomatch             */
+  double count_ms;     /* ... of the count this call made                  */
+} vsa_coveragestats;
+
+int vsa_coverage_getstats(const vsa_coverage *coverage,
+                          vsa_coveragestats *stats);
+/* min(capacity, ceil(bits / 64)) words of the table to the host */
+int vsa_coverage_fetch_bits(const vsa_coverage *coverage, uint64_t *words,
+                            uint64_t capacity);
+const void *vsa_coverage_device_bits(const vsa_coverage *coverage);
+
+/*
+  nomatchsubstringsout (Vmatch/nomatch.c:168-274): the maximal runs of
+  unmarked positions inside [first, first + len) that are at least minlength
+  (>= 1) long, in ascending order.  The runs come as a vsa_result (fetch,
+  device pointer and free are those of a match list) whose records read
+    length = length of the run,  dbstart = its absolute start,
+    queryseq = number of its sequence,  querystart = start inside it.
+  _all: the whole table, the range of the runs with -q (initpost.c:181-190).
+  _database / _queries: the ranges of the runs without -q (initpost.c:167-180)
+  over a table of the index -- [0, DATABASELENGTH) and [DATABASELENGTH + 1,
+  totallength).  DATABASELENGTH is totallength - totalquerylength - 1
+  (include/multidef.h:91) also where the index holds no queries: the
+  reference then leaves the LAST position of the text out of its scan, and so
+  does _database (_all does not).  _queries needs an index with queries;
+  both are _all on a table over a query batch.
+*/
+int vsa_coverage_nomatch(vsa_coverage *coverage, uint64_t minlength,
+                         uint64_t first, uint64_t len,
+                         vsa_result **intervals);
+int vsa_coverage_nomatch_all(vsa_coverage *coverage, uint64_t minlength,
+                             vsa_result **intervals);
+int vsa_coverage_nomatch_database(vsa_coverage *coverage, uint64_t minlength,
+                                  vsa_result **intervals);
+int vsa_coverage_nomatch_queries(vsa_coverage *coverage, uint64_t minlength,
+                                 vsa_result **intervals);
+
+/*
+  shownomatch (Vmatch/nomatch.c:36-135) for such records, host code: the
+  lines `>seqnum relstart length`, with VSA_SHOW_ABSOLUTE `>abs_start length`
+  (abs_start counts from posoffset).  posoffset != 0 is the query part of an
+  index with queries: the reference never advances its sequence counter
+  there and prints `>0 (start - posoffset) length` for every run; so does
+  this.  Returns the bytes written or a negative code.
+*/
+int64_t vsa_nomatch_format(const vsa_match *intervals, uint64_t n,
+                           uint32_t showmode, uint64_t posoffset,
+                           char *buffer, uint64_t capacity);
+
+/*
+  showmaskedseq (Vmatch/showmasked.c:49-153) on the characters of a Multiseq,
+  host code: chars[p] of every marked position p < nbits becomes maskchar, or
+  with VSA_MASK_TOUPPER / VSA_MASK_TOLOWER (the reference's MASKTOUPPER /
+  MASKTOLOWER, -dbmaskmatch toupper) its upper / lower case form; a marked
+  character that is not of the other case stays if it is '*' and is otherwise
+  the reference's error "cannot convert character %c to upper case" (-4; the
+  characters in front of it are changed already).  Separators
+  (chars[p] == VSA_SEPARATOR) are left alone.  *masked (may be NULL) = the
+  number of masked symbols.  Line wrapping and description lines stay with
+  the caller.
+*/
+#define VSA_MASK_TOUPPER 256
+#define VSA_MASK_TOLOWER 257
+int vsa_mask_apply(const uint64_t *bits, uint64_t nbits, uint8_t *chars,
+                   int maskchar, uint64_t *masked);
 
 #ifdef __cplusplus
 }

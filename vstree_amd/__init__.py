@@ -110,6 +110,23 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CoverageParams(C.Structure):
+    _fields_ = [(k, C.c_int) for k in
+                ("layout", "side", "palindromic", "selfpalindromic",
+                 "complete", "markleft", "markright",
+                 "markleftifdifferentsequence",
+                 "markrightifdifferentsequence")]
+
+
+class CoverageStats(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("marked", C.c_uint64),
+                ("separators", C.c_uint64), ("mark_ms", C.c_double),
+                ("extract_ms", C.c_double), ("count_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROCESSMATCH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 
@@ -194,6 +211,7 @@ def _load():
         "vsa_result_fetch": (I, [V, V, U64]),
         "vsa_result_device_matches": (V, [V]),
         "vsa_result_free": (None, [V]),
+        "vsa_result_from_host": (I, [V, U64, I, PP]),
         "vsa_result_copy_device": (I, [V, V, U64]),
         "vsa_mumuniqueinquery": (I, [V, U64, I, PP]),
         "vsa_mumuniqueinquery_range": (I, [V, U64, I, U64, PP]),
@@ -247,6 +265,22 @@ def _load():
         "vsa_device_trim": (I, [I]),
         "vsa_device_meminfo": (I, [I, C.POINTER(U64), C.POINTER(U64)]),
         "vsa_measure_stream_read": (I, [U64, I, C.POINTER(C.c_double)]),
+        "vsa_coverage_open_index": (I, [V, PP]),
+        "vsa_coverage_open_queries": (I, [V, PP]),
+        "vsa_coverage_close": (None, [V]),
+        "vsa_coverage_numofbits": (U64, [V]),
+        "vsa_coverage_coop_threshold": (U64, []),
+        "vsa_coverage_mark": (I, [V, V, C.POINTER(CoverageParams)]),
+        "vsa_coverage_merge": (I, [V, V]),
+        "vsa_coverage_getstats": (I, [V, C.POINTER(CoverageStats)]),
+        "vsa_coverage_fetch_bits": (I, [V, V, U64]),
+        "vsa_coverage_device_bits": (V, [V]),
+        "vsa_coverage_nomatch": (I, [V, U64, U64, U64, PP]),
+        "vsa_coverage_nomatch_all": (I, [V, U64, PP]),
+        "vsa_coverage_nomatch_database": (I, [V, U64, PP]),
+        "vsa_coverage_nomatch_queries": (I, [V, U64, PP]),
+        "vsa_nomatch_format": (C.c_int64, [V, U64, U32, U64, V, U64]),
+        "vsa_mask_apply": (I, [V, U64, V, I, C.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -434,6 +468,15 @@ class Result:
 
     def __init__(self, handle):
         self._h = handle
+
+    @classmethod
+    def from_host(cls, matches, device=0):
+        """a MATCH_DTYPE array as a match list on the device"""
+        matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+        h = C.c_void_p()
+        _check(lib.vsa_result_from_host(_ptr(matches), len(matches), device,
+                                        C.byref(h)))
+        return cls(h)
 
     @property
     def count(self):
@@ -860,6 +903,156 @@ class Sink:
 
     def __del__(self):
         self.close()
+
+
+# ---- match coverage (vmatch -dbnomatch / -qnomatch / -dbmaskmatch /
+# -qmaskmatch) ---------------------------------------------------------------
+
+COVERAGE_QUERY, COVERAGE_SELF, COVERAGE_APPROX = 0, 1, 2
+COVERAGE_DATABASE, COVERAGE_QUERIES = 0, 1
+COVERAGE_COOP_THRESHOLD = int(lib.vsa_coverage_coop_threshold())
+COVERAGE_EXTRACT_TILE = 65536
+MASK_TOUPPER, MASK_TOLOWER = 256, 257
+# record of Coverage.nomatch: a run of unmarked positions
+INTERVAL_DTYPE = np.dtype([("length", "<u8"), ("start", "<u8"),
+                           ("seqnum", "<u8"), ("relstart", "<u8")])
+_KEEP = {"keepleft": "markleft", "keepright": "markright",
+         "keepleftifsamesequence": "markleftifdifferentsequence",
+         "keeprightifsamesequence": "markrightifdifferentsequence"}
+
+
+def coverage_options(keep=None, withquery=False, option="-dbnomatch"):
+    """the four keep flags of `-dbnomatch N [keyword]` / `-dbmaskmatch C
+    [keyword]` (Vmatch/keepflags.c:9-27, defaults Vmatch/parsevm.c:83-87) as
+    keyword arguments of Coverage.mark; withquery: -q is given, where a
+    keyword is the reference's error (parsevm.c:70-80)"""
+    flags = {v: 1 for v in _KEEP.values()}
+    if keep is not None:
+        if keep not in _KEEP:
+            raise VsaError(-2, "illegal argument \"%s\" to option %s: "
+                           "possible arguments are: keepleft, keepright, "
+                           "keepleftifsamesequence, keeprightifsamesequence"
+                           % (keep, option))
+        if withquery:
+            raise VsaError(-2, "argument \"%s\" to option %s not allowed if "
+                           "option -q is used" % (keep, option))
+        flags[_KEEP[keep]] = 0
+    return flags
+
+
+class Coverage:
+    """One bit per position of a Multiseq in HBM (vsa_coverage): the
+    reference's marktable.  Coverage.over_index(index) /
+    Coverage.over_queries(queries)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def over_index(cls, index):
+        h = C.c_void_p()
+        _check(lib.vsa_coverage_open_index(index._h, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def over_queries(cls, queries):
+        h = C.c_void_p()
+        _check(lib.vsa_coverage_open_queries(queries._h, C.byref(h)))
+        return cls(h)
+
+    @property
+    def nbits(self):
+        return int(lib.vsa_coverage_numofbits(self._h))
+
+    def mark(self, result, layout=COVERAGE_QUERY, side=COVERAGE_DATABASE,
+             palindromic=False, selfpalindromic=False, complete=False,
+             markleft=1, markright=1, markleftifdifferentsequence=1,
+             markrightifdifferentsequence=1):
+        """markmatches (Vmatch/markmat.c:42) for every record of a Result"""
+        p = CoverageParams(int(layout), int(side), int(bool(palindromic)),
+                           int(bool(selfpalindromic)), int(bool(complete)),
+                           int(markleft), int(markright),
+                           int(markleftifdifferentsequence),
+                           int(markrightifdifferentsequence))
+        _check(lib.vsa_coverage_mark(self._h, result._h, C.byref(p)))
+
+    def merge(self, other):
+        _check(lib.vsa_coverage_merge(self._h, other._h))
+
+    def stats(self):
+        s = CoverageStats()
+        _check(lib.vsa_coverage_getstats(self._h, C.byref(s)))
+        return s
+
+    def bits(self):
+        """-> the table as uint64 words (position p = bit p & 63 of word
+        p >> 6)"""
+        out = np.zeros((self.nbits + 63) // 64, np.uint64)
+        if len(out):
+            _check(lib.vsa_coverage_fetch_bits(self._h, _ptr(out), len(out)))
+        return out
+
+    def device_bits(self):
+        return lib.vsa_coverage_device_bits(self._h)
+
+    def nomatch(self, minlength, first=None, length=None, part=None):
+        """runs of unmarked positions of at least minlength -> array of
+        INTERVAL_DTYPE.  part: None (the whole table or [first, first +
+        length)), "database" or "queries" of an index with queries"""
+        h = C.c_void_p()
+        if part == "database":
+            rc = lib.vsa_coverage_nomatch_database(self._h, int(minlength),
+                                                   C.byref(h))
+        elif part == "queries":
+            rc = lib.vsa_coverage_nomatch_queries(self._h, int(minlength),
+                                                  C.byref(h))
+        elif first is None:
+            rc = lib.vsa_coverage_nomatch_all(self._h, int(minlength),
+                                              C.byref(h))
+        else:
+            rc = lib.vsa_coverage_nomatch(self._h, int(minlength), int(first),
+                                          int(length), C.byref(h))
+        _check(rc)
+        return Result(h).fetch().view(INTERVAL_DTYPE)
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_coverage_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def nomatch_format(intervals, showmode=0, posoffset=0):
+    """the reference's lines for runs of unmarked positions (shownomatch,
+    Vmatch/nomatch.c:36) -> bytes; posoffset != 0: the query part of an
+    index with queries"""
+    iv = np.ascontiguousarray(intervals).view(MATCH_DTYPE)
+    cap = 64 * (len(iv) + 1)
+    buf = np.empty(cap, np.uint8)
+    n = lib.vsa_nomatch_format(_ptr(iv), len(iv), int(showmode),
+                               int(posoffset), _ptr(buf), cap)
+    if n < 0:
+        raise VsaError(int(n), messagespace())
+    return buf[:n].tobytes()
+
+
+def mask_apply(bits, chars, maskchar):
+    """showmaskedseq (Vmatch/showmasked.c:49) on the characters of a
+    Multiseq (separators as SEPARATOR) -> (masked characters, number of
+    masked symbols); maskchar: a character, MASK_TOUPPER or MASK_TOLOWER"""
+    bits = np.ascontiguousarray(bits, np.uint64)
+    out = np.array(np.frombuffer(bytes(chars), np.uint8)
+                   if isinstance(chars, (bytes, bytearray))
+                   else np.asarray(chars, np.uint8), copy=True)
+    assert len(bits) * 64 >= len(out)
+    if not isinstance(maskchar, int):
+        maskchar = ord(maskchar)
+    n = C.c_uint64(0)
+    _check(lib.vsa_mask_apply(_ptr(bits), len(out), _ptr(out), maskchar,
+                              C.byref(n)))
+    return out, int(n.value)
 
 
 # ---- synthetic inputs (SURVEY.md section 8d) ------------------------------
