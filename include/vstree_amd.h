@@ -167,6 +167,9 @@ typedef struct vsa_queries vsa_queries;
   alphabet-mapped symbols -- the layout of a reference Multiseq: sequences
   separated by VSA_SEPARATOR, start[i] = markpos[i-1]+1
   (include/multidef.h:113-133, kurtz-basic/multiseq.c:129-166).
+  Contract: symbols are codes of the index's alphabet or >= 254 (wildcard,
+  separator).  A batch is not bound to an index, so nothing checks this; a
+  code in [numofchars, 253] would give a q-gram code beyond the bucket table.
 */
 int vsa_queries_from_host(const uint8_t *symbols, uint64_t nsymbols,
                           const uint64_t *start, const uint64_t *length,

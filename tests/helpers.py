@@ -462,6 +462,28 @@ def dna_map():
     return m
 
 
+def symbol_map_from_al1(path):
+    """Symbol map of an alphabet file as mkvtree writes it (.al1) and reads it
+    (-smap; kurtz-basic/alphabet.c:189-295): one class of characters per
+    line up to the first blank, comment lines in front; class i -> code i,
+    the last class -> WILDCARD, every other byte -> 253 (not in the
+    alphabet).  dna_map() is symbol_map_from_al1 of the DNA .al1."""
+    m = np.full(256, 253, np.uint8)
+    classes, preamble = [], True
+    with open(path, "rb") as f:
+        for line in f.read().split(b"\n"):
+            if not line or (preamble and line.startswith(b"#")):
+                continue
+            preamble = False
+            classes.append(line.split(b" ")[0])
+    assert 2 <= len(classes) <= 254
+    for code, chars in enumerate(classes):
+        for ch in chars:
+            assert m[ch] == 253, "character mapped twice"
+            m[ch] = WILDCARD if code == len(classes) - 1 else code
+    return m
+
+
 def read_fasta(path):
     """-> list of (description, bytes) records."""
     recs, desc, chunks = [], None, []
@@ -806,6 +828,57 @@ def load_case(case):
         idx.numofdbsequences = idx.numofsequences
     _cases[case] = (idx, queries)
     return _cases[case]
+
+
+_amanifest = None
+_aexpected = None
+
+
+def alphabets_manifest():
+    """tests/golden/alphabets_manifest.json
+    (scripts/make_golden_alphabets.py)"""
+    global _amanifest
+    if _amanifest is None:
+        with open(os.path.join(GOLDEN, "alphabets_manifest.json")) as f:
+            _amanifest = _json.load(f)
+    return _amanifest
+
+
+def alphabets_expected(case, key):
+    global _aexpected
+    if _aexpected is None:
+        _aexpected = np.load(os.path.join(GOLDEN, "alphabets_expected.npz"))
+    return _aexpected["%s__%s" % (case, key)]
+
+
+def load_alphabet_case(case):
+    """load_case for the cases of alphabets_manifest.json: the alphabet size
+    and the symbol map (the .al1 the reference wrote) come from the manifest.
+    -> (Index built by the CPU oracle builder, Queries or None); the tables
+    are asserted equal to the md5 sums of the reference's files."""
+    if ("alphabets", case) in _cases:
+        return _cases[("alphabets", case)]
+    m = alphabets_manifest()[case]
+    nc, pl = m["numofchars"], m["index"]["prj"]["prefixlength"]
+    symmap = symbol_map_from_al1(os.path.join(GOLDEN, m["al1"]))
+    assert int(symmap[symmap < 253].max()) + 1 == nc
+    files = [_golden_fasta(f) for f in m["db"]]
+    qfiles = [_golden_fasta(f) for f in m.get("indexedquery", [])]
+    tis, ssp, perfile = fasta_text(files + qfiles, symmap)
+    assert not (tis == 253).any(), "symbol outside the alphabet"
+    hasq = bool(qfiles)
+    ndb = sum(perfile[:len(files)])
+    qsep = int(ssp[ndb - 1]) if hasq else 0
+    idx = oracle_build_index(tis, nc, pl, ssp=ssp, querysepposition=qsep,
+                             hasqueries=hasq)
+    idx.numofdbsequences = ndb
+    idx.symmap = symmap
+    got = table_md5(idx)
+    assert got == m["index"]["md5"], (case, got, m["index"]["md5"])
+    queries = (fasta_queries(_golden_fasta(m["query"]), symmap)
+               if "query" in m else None)
+    _cases[("alphabets", case)] = (idx, queries)
+    return idx, queries
 
 
 def index_as_rc_queries(index):
