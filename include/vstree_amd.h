@@ -973,6 +973,124 @@ int64_t vsa_nomatch_format(const vsa_match *intervals, uint64_t n,
 int vsa_mask_apply(const uint64_t *bits, uint64_t nbits, uint8_t *chars,
                    int maskchar, uint64_t *masked);
 
+/* ---- match selection: vmatch -best N, -sort mode, -evalue, -identity,
+   -leastscore and the gap bounds of -l L lo [hi] (Vmatch/procfinal.c:196-260,
+   566-636,695-745, Vmatch/mokay.c, kurtz/bestmatch.c:33-119,
+   kurtz-basic/dictmaxsize.c, kurtz/smcontain.c:23-95, kurtz/matsort.c,
+   kurtz/evalues.c:316-420) on match lists that stay in HBM -----------------
+
+   Per match processfinal derives length1, position1, length2, position2
+   (absolute in the query Multiseq: sequence i starts at the sum of
+   length_j + 1 over j < i; relpos2 flipped to seqlength2 - (relpos2 +
+   length2) for a palindromic list), the distance (0, +d for -e, -d for -h),
+   the D/P flag and the E-value: multiplier * T[|d|][lenmatch] for d <= 0,
+   (multiplier * hequot[d]) * T[d][lenmatch] for d > 0, with T the table of
+   incprecomputehammingEvalues, lenmatch = length2 for complete lists or d = 0
+   and the larger length otherwise, and the multiplier of assignEvalue:
+   (double) totallength * (double) length of the query sequence with -q,
+   totallength for complete lists, 0.5 * totallength^2 for self lists
+   (DATABASELENGTH * totalquerylength on an index with queries); 0.0 for
+   every match with VSA_SHOW_NOEVALUE.
+
+   matchokay drops a match if a length is below leastlength; if
+   100 (1 - |d| / max(length1, length2)) < identity; if EVALDISTANCE2SCORE
+   (l1 + l2 - 3d for d >= 0, -(l1 + l2 + 3d) for d < 0) < leastscore; if
+   evalue > maximumevalue; if the gap position2 - (position1 + length1), or
+   -(position1 + length1 - position2) where position1 + length1 - 1 >
+   position2, is below lowergap or above uppergap.
+
+   -best N keeps the N best distinct matches, best first: smaller E-value,
+   larger length1, smaller position1, larger length2, smaller position2,
+   direct before palindromic (cmpBestMatch); two matches equal in all six are
+   one match (the one seen first stays).  -sort takes these N, sorts them
+   stably by (position1, length1, position2), drops every match contained in
+   another (CONTAINSSTOREMATCH; of two with the same four coordinates the
+   earlier stays) and, unless the mode is ia, sorts them stably by the mode's
+   key: length1, position1, position2, E-value, |score|, identity. */
+
+#define VSA_SORT_NONE 12  /* else 0..11 = la ld ia id ja jd ea ed sa sd ida idd (matsort.c:167-180) */
+typedef struct
+{
+  uint64_t bestnumber;   /* -best N; 0: filters only, input order kept      */
+  int sortmode;          /* VSA_SORT_NONE or 0..11; needs bestnumber > 0    */
+  int hasmaxevalue;
+  double maximumevalue;
+  uint32_t identity;     /* 0 = off, 1..100                                 */
+  int hasleastscore;
+  int64_t leastscore;    /* >= 0                                            */
+  int haslowergap, hasuppergap; /* VSA_SINK_SELF only, else error; the upper
+                                   bound needs the lower one                */
+  int64_t lowergap, uppergap;
+} vsa_selectparams;
+
+typedef struct
+{
+  uint64_t seen;       /* records handed to vsa_select_add                  */
+  uint64_t rejected;   /* ... dropped by matchokay                          */
+  uint64_t duplicates; /* ... found equal in all six values to a match kept
+                          at that time (a match worse than the N kept ones
+                          is dropped without being compared)                */
+  uint64_t selected;   /* matches of the selection, after vsa_select_finish
+                          of the list it delivered                          */
+  uint64_t containedremoved; /* "remove %lu contained matches"             */
+} vsa_selectstats;
+
+typedef struct vsa_select vsa_select;
+/* records one workgroup of the selection kernels compacts */
+#define VSA_SELECT_TILE 1024u
+
+/*
+  layout describes the run like it does for the sink: kind, numofchars,
+  showmode & VSA_SHOW_NOEVALUE, leastlength, the index and the query
+  Multiseq; layout->palindromic is ignored in favour of the argument of
+  vsa_select_add.  queries != NULL: the query Multiseq is laid out from the
+  lengths of the batch like vsa_coverage_open_queries does, and the offset of
+  the batch (vsa_queries_set_offset) at the time of the call is subtracted
+  from the queryseq of every match; NULL: layout->querystart / querylength.
+  bestnumber is at most 2^32 - 16.
+*/
+int vsa_select_open(const vsa_sinkparams *layout, const vsa_queries *queries,
+                    const vsa_selectparams *params, int device,
+                    vsa_select **select);
+/* the records of a list through matchokay into the selection; several calls
+   accumulate (-d -p: two calls).  VSA_NOT_COVERED, state untouched: a
+   packed-pair result; selfpalindromic lists (layout->selfpalindromic, or
+   palindromic != 0 with VSA_SINK_SELF).  -2, state untouched: a record that
+   does not fit the layout. */
+int vsa_select_add(vsa_select *select, const vsa_result *result,
+                   int palindromic);
+/* the selection as raw records in output order: the same sink formats them
+   (record by record with the flags of vsa_select_flags where both strands
+   were added), vsa_coverage_mark accepts them.  The selection stays open:
+   more lists may be added and finish called again. */
+int vsa_select_finish(vsa_select *select, vsa_result **selected);
+/* the D/P flag of every record vsa_select_finish delivered last */
+int vsa_select_flags(const vsa_select *select, uint8_t *palindromic,
+                     uint64_t capacity);
+int vsa_select_getstats(const vsa_select *select, vsa_selectstats *stats);
+/* digit-counting passes the radix select of the last vsa_select_add made
+   over its candidates: one per word of the key on which they all agree, a
+   few on a word that tells them apart (scripts/select_probe.py) */
+uint64_t vsa_select_passes(const vsa_select *select);
+/* the E-value of every record of a list, bit for bit the host's */
+int vsa_select_evalues(vsa_select *select, const vsa_result *result,
+                       int palindromic, double *evalues, uint64_t capacity);
+void vsa_select_close(vsa_select *select);
+
+/*
+  The same rules on a list in host memory, no GPU involved: matches[i] with
+  the flag palindromic[i] (NULL: all direct), the query Multiseq from
+  layout->querystart / querylength.  selected / selectedflags / evalues (the
+  latter two may be NULL) take the at most `capacity` records of the
+  selection in output order; -3 if there are more.
+*/
+int vsa_select_host(const vsa_sinkparams *layout,
+                    const vsa_selectparams *params, const vsa_match *matches,
+                    const uint8_t *palindromic, uint64_t n,
+                    vsa_match *selected, uint8_t *selectedflags,
+                    double *evalues, uint64_t capacity, uint64_t *nselected,
+                    vsa_selectstats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,24 @@ class CoverageStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("bestnumber", C.c_uint64), ("sortmode", C.c_int),
+                ("hasmaxevalue", C.c_int), ("maximumevalue", C.c_double),
+                ("identity", C.c_uint32), ("hasleastscore", C.c_int),
+                ("leastscore", C.c_int64), ("haslowergap", C.c_int),
+                ("hasuppergap", C.c_int), ("lowergap", C.c_int64),
+                ("uppergap", C.c_int64)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in
+                ("seen", "rejected", "duplicates", "selected",
+                 "containedremoved")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROCESSMATCH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 
@@ -281,6 +299,19 @@ def _load():
         "vsa_coverage_nomatch_queries": (I, [V, U64, PP]),
         "vsa_nomatch_format": (C.c_int64, [V, U64, U32, U64, V, U64]),
         "vsa_mask_apply": (I, [V, U64, V, I, C.POINTER(U64)]),
+        "vsa_select_open": (I, [C.POINTER(SinkParams), V,
+                                C.POINTER(SelectParams), I, PP]),
+        "vsa_select_add": (I, [V, V, I]),
+        "vsa_select_finish": (I, [V, PP]),
+        "vsa_select_flags": (I, [V, V, U64]),
+        "vsa_select_getstats": (I, [V, C.POINTER(SelectStats)]),
+        "vsa_select_evalues": (I, [V, V, I, V, U64]),
+        "vsa_select_passes": (U64, [V]),
+        "vsa_select_close": (None, [V]),
+        "vsa_select_host": (I, [C.POINTER(SinkParams),
+                                C.POINTER(SelectParams), V, V, U64, V, V, V,
+                                U64, C.POINTER(U64),
+                                C.POINTER(SelectStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -856,32 +887,38 @@ SHOW_ABSOLUTE, SHOW_NODIST, SHOW_NOEVALUE, SHOW_NOSCORE, SHOW_NOIDENTITY = (
     1, 2, 4, 8, 16)
 
 
+def sink_params(kind, totallength, markpos, numofchars=4, querystart=None,
+                querylength=None, querytotallength=0, numofquerysequences=0,
+                totalquerylength=0, leastlength=0, palindromic=False,
+                showmode=0, threads=0, selfpalindromic=False):
+    """the description of a run (vsa_sinkparams) for Sink and Select ->
+    (SinkParams, the arrays it points into)"""
+    keep = [np.ascontiguousarray(markpos, np.uint64)]
+    p = SinkParams()
+    p.kind, p.palindromic = int(kind), int(bool(palindromic))
+    p.selfpalindromic = int(bool(selfpalindromic))
+    p.showmode, p.numofchars = int(showmode), int(numofchars)
+    p.threads = int(threads)
+    p.leastlength, p.totallength = int(leastlength), int(totallength)
+    p.numofsequences = keep[0].shape[0] + 1
+    p.markpos = _ptr(keep[0]) if keep[0].shape[0] else None
+    p.numofquerysequences = int(numofquerysequences)
+    p.totalquerylength = int(totalquerylength)
+    if querystart is not None:
+        qs = np.ascontiguousarray(querystart, np.uint64)
+        ql = np.ascontiguousarray(querylength, np.uint64)
+        keep += [qs, ql]
+        p.numofqueries = qs.shape[0]
+        p.querytotallength = int(querytotallength)
+        p.querystart, p.querylength = _ptr(qs), _ptr(ql)
+    return p, keep
+
+
 class Sink:
     """vmatch's output lines for match records (vsa_sink, host side)."""
 
-    def __init__(self, kind, totallength, markpos, numofchars=4,
-                 querystart=None, querylength=None, querytotallength=0,
-                 numofquerysequences=0, totalquerylength=0, leastlength=0,
-                 palindromic=False, showmode=0, threads=0,
-                 selfpalindromic=False):
-        self._keep = [np.ascontiguousarray(markpos, np.uint64)]
-        p = SinkParams()
-        p.kind, p.palindromic = int(kind), int(bool(palindromic))
-        p.selfpalindromic = int(bool(selfpalindromic))
-        p.showmode, p.numofchars = int(showmode), int(numofchars)
-        p.threads = int(threads)
-        p.leastlength, p.totallength = int(leastlength), int(totallength)
-        p.numofsequences = self._keep[0].shape[0] + 1
-        p.markpos = _ptr(self._keep[0]) if self._keep[0].shape[0] else None
-        p.numofquerysequences = int(numofquerysequences)
-        p.totalquerylength = int(totalquerylength)
-        if querystart is not None:
-            qs = np.ascontiguousarray(querystart, np.uint64)
-            ql = np.ascontiguousarray(querylength, np.uint64)
-            self._keep += [qs, ql]
-            p.numofqueries = qs.shape[0]
-            p.querytotallength = int(querytotallength)
-            p.querystart, p.querylength = _ptr(qs), _ptr(ql)
+    def __init__(self, *args, **kw):
+        p, self._keep = sink_params(*args, **kw)
         self._h = C.c_void_p()
         _check(lib.vsa_sink_open(C.byref(p), C.byref(self._h)))
 
@@ -1053,6 +1090,109 @@ def mask_apply(bits, chars, maskchar):
     _check(lib.vsa_mask_apply(_ptr(bits), len(out), _ptr(out), maskchar,
                               C.byref(n)))
     return out, int(n.value)
+
+
+# ---- match selection (vmatch -best, -sort, -evalue, -identity, -leastscore,
+# the gap bounds of -l L lo [hi]) ------------------------------------------------
+
+SORT_MODES = ("la", "ld", "ia", "id", "ja", "jd", "ea", "ed", "sa", "sd",
+              "ida", "idd")
+SORT_NONE = 12
+SELECT_TILE = 1024
+
+
+def select_params(best=0, sort=None, evalue=None, identity=0,
+                  leastscore=None, gap=None):
+    """-best N, -sort mode (a name of SORT_MODES or its number), -evalue X,
+    -identity I, -leastscore S, gap = (lo,) or (lo, hi) -> SelectParams"""
+    p = SelectParams()
+    p.bestnumber = int(best)
+    p.sortmode = SORT_NONE if sort is None else (
+        SORT_MODES.index(sort) if isinstance(sort, str) else int(sort))
+    if evalue is not None:
+        p.hasmaxevalue, p.maximumevalue = 1, float(evalue)
+    p.identity = int(identity)
+    if leastscore is not None:
+        p.hasleastscore, p.leastscore = 1, int(leastscore)
+    if gap is not None:
+        p.haslowergap, p.lowergap = 1, int(gap[0])
+        if len(gap) > 1:
+            p.hasuppergap, p.uppergap = 1, int(gap[1])
+    return p
+
+
+class Select:
+    """The matches vmatch would print of the lists added (vsa_select): what
+    matchokay lets through, the N best of it, sorted.  layout: what
+    sink_params() returns; queries: the batch the lists refer to (its lengths
+    and offset), or None for the query Multiseq of the layout."""
+
+    def __init__(self, layout, queries=None, device=0, **options):
+        self._layout = layout
+        p = options.pop("params", None) or select_params(**options)
+        self._h = C.c_void_p()
+        _check(lib.vsa_select_open(C.byref(layout[0]),
+                                   queries._h if queries is not None else None,
+                                   C.byref(p), device, C.byref(self._h)))
+
+    def add(self, result, palindromic=False):
+        _check(lib.vsa_select_add(self._h, result._h, int(bool(palindromic))))
+
+    def finish(self):
+        """-> Result: the selection as raw records in output order"""
+        h = C.c_void_p()
+        _check(lib.vsa_select_finish(self._h, C.byref(h)))
+        return Result(h)
+
+    def flags(self, n):
+        """the D/P flags of the n records finish() delivered last"""
+        out = np.zeros(n, np.uint8)
+        _check(lib.vsa_select_flags(self._h, _ptr(out), n))
+        return out
+
+    def stats(self):
+        s = SelectStats()
+        _check(lib.vsa_select_getstats(self._h, C.byref(s)))
+        return s
+
+    @property
+    def passes(self):
+        """digit-counting passes of the radix select of the last add()"""
+        return int(lib.vsa_select_passes(self._h))
+
+    def evalues(self, result, palindromic=False):
+        out = np.zeros(result.count, np.float64)
+        _check(lib.vsa_select_evalues(self._h, result._h,
+                                      int(bool(palindromic)), _ptr(out),
+                                      len(out)))
+        return out
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_select_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def select_host(layout, matches, palindromic=None, **options):
+    """the same selection on a list in host memory, no GPU -> (records,
+    flags, E-values, SelectStats)"""
+    p = options.pop("params", None) or select_params(**options)
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    n = len(matches)
+    pal = None if palindromic is None else \
+        np.ascontiguousarray(palindromic, np.uint8)
+    assert pal is None or len(pal) == n
+    out = np.zeros(n, MATCH_DTYPE)
+    flags, ev = np.zeros(n, np.uint8), np.zeros(n, np.float64)
+    k, st = C.c_uint64(0), SelectStats()
+    _check(lib.vsa_select_host(C.byref(layout[0]), C.byref(p), _ptr(matches),
+                               _ptr(pal), n, _ptr(out), _ptr(flags), _ptr(ev),
+                               n, C.byref(k), C.byref(st)))
+    k = int(k.value)
+    return out[:k], flags[:k], ev[:k], st
 
 
 # ---- synthetic inputs (SURVEY.md section 8d) ------------------------------

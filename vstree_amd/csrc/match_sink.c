@@ -30,6 +30,7 @@
 #include <pthread.h>
 #include <unistd.h>
 #include "vstree_amd.h"
+#include "evalues.h"
 
 char *vsa_errbuf(void);
 #define ERRSIZE 1024
@@ -43,14 +44,7 @@ static const double averagequot[] = {
     8.22e+02, 1.78e+03, 3.91e+03, 8.50e+03, 1.76e+04, 3.78e+04, 7.98e+04,
     1.66e+05, 3.58e+05, 7.44e+05, 1.52e+06, 3.20e+06, 6.40e+06, 1.31e+07};
 
-typedef struct
-{
-  double probmatch, first;
-  int64_t *linestart; /* nextline entries are valid */
-  uint64_t nextline, alloclines;
-  double *table;
-  uint64_t nexttab, alloctab;
-} Evalues;
+typedef vsa_evalues Evalues; /* evalues.h: shared with select_host.c */
 
 /* strings that depend on (distance, length) only, per formatting thread:
    "%.2e" of the E-value with its leading blanks, and "%.2f" of the identity
@@ -85,7 +79,7 @@ struct vsa_sink
 };
 
 /* incprecomputehammingEvalues, kurtz/evalues.c:316-368 */
-static int evalues_extend(Evalues *h, int64_t kmax)
+int vsa_evalues_extend(Evalues *h, int64_t kmax)
 {
   int64_t k, l;
 
@@ -132,7 +126,7 @@ static double evalues_lookup(Evalues *h, int64_t distance, int64_t length)
 
   if (distance + 1 > (int64_t) h->nextline)
   {
-    if (evalues_extend(h, distance) != 0)
+    if (vsa_evalues_extend(h, distance) != 0)
     {
       return 0.0;
     }
@@ -145,6 +139,16 @@ static double evalues_lookup(Evalues *h, int64_t distance, int64_t length)
   return 0.0;
 }
 
+/* the factor incgetEvalue multiplies in for an edit distance */
+double vsa_evalues_hequot(int64_t distance)
+{
+  if (distance > 20)
+  {
+    return 1.31e+07 * pow(2.0, (double) (distance - 20));
+  }
+  return averagequot[distance];
+}
+
 /* incgetEvalue, kurtz/evalues.c:388-426 */
 static double evalues_get(Evalues *h, double multiplier, int64_t distance,
                           uint64_t length)
@@ -153,17 +157,29 @@ static double evalues_get(Evalues *h, double multiplier, int64_t distance,
   {
     return multiplier * evalues_lookup(h, -distance, (int64_t) length);
   }
-  if (distance > 20)
+  if (distance - 20 > MAXEXPONENTOF2)
   {
-    if (distance - 20 > MAXEXPONENTOF2)
-    {
-      return 0.0;
-    }
-    return multiplier * (1.31e+07 * pow(2.0, (double) (distance - 20))) *
-           evalues_lookup(h, distance, (int64_t) length);
+    return 0.0;
   }
-  return multiplier * averagequot[distance] *
+  return multiplier * vsa_evalues_hequot(distance) *
          evalues_lookup(h, distance, (int64_t) length);
+}
+
+/* inithammingEvalues(&evalues, 1.0 / (mapsize - 1)),
+   Vmatch/procmatch.c:545, kurtz/evalues.c:307-314 */
+void vsa_evalues_init(Evalues *h, uint32_t numofchars)
+{
+  memset(h, 0, sizeof *h);
+  h->probmatch = 1.0 / (double) numofchars;
+  h->first = h->probmatch * ((1.0 - h->probmatch) * (1.0 - h->probmatch));
+}
+
+void vsa_evalues_free(Evalues *h)
+{
+  free(h->linestart);
+  free(h->table);
+  h->linestart = NULL;
+  h->table = NULL;
 }
 
 static void cache_free(Fcache *c);
@@ -239,11 +255,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
     s->wpos2 = digitsof(params->querytotallength);
     s->wseq2 = digitsof(params->numofqueries);
   }
-  /* inithammingEvalues(&evalues, 1.0 / (mapsize - 1)),
-     Vmatch/procmatch.c:545, kurtz/evalues.c:307-314 */
-  s->ev.probmatch = 1.0 / (double) params->numofchars;
-  s->ev.first = s->ev.probmatch *
-                ((1.0 - s->ev.probmatch) * (1.0 - s->ev.probmatch));
+  vsa_evalues_init(&s->ev, params->numofchars);
   *sink = s;
   return 0;
 }
@@ -257,8 +269,7 @@ void vsa_sink_close(vsa_sink *s)
     free(s->qlength);
     free(s->line);
     cache_free(&s->cache);
-    free(s->ev.linestart);
-    free(s->ev.table);
+    vsa_evalues_free(&s->ev);
     free(s);
   }
 }
@@ -598,7 +609,7 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
     }
   }
   if (maxd + 1 > s->ev.nextline &&
-      evalues_extend(&s->ev, (int64_t) maxd) != 0)
+      vsa_evalues_extend(&s->ev, (int64_t) maxd) != 0)
   {
     snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
     return -101;

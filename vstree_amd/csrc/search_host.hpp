@@ -180,6 +180,11 @@ VSA_HIDDEN int sortbykey(uint64_t *keys_in, uint64_t *keys_out, vsa_match *in,
                          vsa_match *out, uint64_t n, unsigned int endbit,
                          hipStream_t stream);
 
+// stable sort of (key, index) pairs by the whole key (fewer than 2^32 pairs)
+VSA_HIDDEN int sortpairs(uint64_t *keys_in, uint64_t *keys_out,
+                         uint32_t *vals_in, uint32_t *vals_out, uint64_t n,
+                         hipStream_t stream);
+
 VSA_HIDDEN vsa_result *newresult(int device);
 
 // offsets[sh] = sum of the fill counts of the cursor regions before sh (one
