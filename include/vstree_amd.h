@@ -1091,6 +1091,121 @@ int vsa_select_host(const vsa_sinkparams *layout,
                     double *evalues, uint64_t capacity, uint64_t *nselected,
                     vsa_selectstats *stats);
 
+/* ---- sequence clustering: vmatch -dbcluster percsmall perclarge
+   (Vmatch/vmcluster.c:289-415, kurtz/cluster.c:125-197,436-683) on match
+   lists that stay in HBM ----------------------------------------------------
+
+   Single-linkage clustering of the sequences of the index.  A record of a
+   self list (VSA_SINK_SELF: length, start1, start2 absolute) or of a list of
+   vmatch -p IDX (dbstart absolute, queryseq = the sequence of the index whose
+   reverse complement matched) lies in the sequences seq1 and seq2, found in
+   markpos; a sequence is as long as findboundaries says.  A record with
+   seq1 == seq2 is skipped; of a palindromic list the record with seq1 > seq2
+   is the mirror image of another and dropped (procfinal.c:159-167).  The
+   record is an edge (seq1, seq2) iff, with mlen the length of the match and
+   small <= large the two sequence lengths, mlen >= small * percsmall / 100
+   and mlen >= large * perclarge / 100 in 64-bit unsigned arithmetic.  Edges
+   are numbered in the order of the records over all lists added.
+
+   linkcluster takes the edges in that order: two sequences without a cluster
+   found a new one; a sequence without one is appended to the cluster of the
+   other; two clusters are merged into the larger one, into that of seq2 if
+   they are equally large.  Only an edge between two different clusters
+   changes anything, and these edges are the minimum spanning forest of the
+   list with the edge number as weight: the device finds that forest, the
+   host replays its at most numofsequences - 1 edges.
+
+   Clusters are numbered like vmatch prints them: in the order of their
+   creation, those emptied by a merge left out; the members of a cluster come
+   in the order of its chain.  Fewer than 2^32 sequences and edges. */
+
+typedef struct
+{
+  uint32_t percsmall, perclarge;
+} vsa_clusterparams;
+
+typedef struct
+{
+  uint64_t seen;          /* records handed in                              */
+  uint64_t samesequence;  /* ... with seq1 == seq2                          */
+  uint64_t mirrordropped; /* ... palindromic with seq1 > seq2               */
+  uint64_t rejected;      /* ... with too small an overlap                  */
+  uint64_t edges;         /* ... accepted: linkcluster calls                */
+  uint64_t forestedges;   /* edges that joined two different clusters       */
+  uint64_t rounds;        /* rounds of the forest search (0 on the host)    */
+  uint64_t clusters;      /* after finish: clusters, ...                    */
+  uint64_t inclusters;    /* ... sequences in them, ...                     */
+  uint64_t singlets;      /* ... and sequences in none                      */
+} vsa_clusterstats;
+
+typedef struct vsa_cluster vsa_cluster;
+#define VSA_CLUSTER_SINGLET 0xFFFFFFFFFFFFFFFFull
+#define VSA_CLUSTER_MAXROUNDS 64u /* of the forest search */
+#define VSA_CLUSTER_MAXJUMPS 64u  /* per pointer-jumping pass */
+
+/*
+  layout describes the index like it does for the sink: totallength,
+  numofsequences, markpos, numofquerysequences; kind is VSA_SINK_SELF, or
+  VSA_SINK_QUERY with selfpalindromic set (vmatch -p IDX alone).  -2 with the
+  reference's message: an index of one sequence, an index with queries.
+  VSA_NOT_COVERED: any other kind, 2^32 sequences or more.
+*/
+int vsa_cluster_open(const vsa_sinkparams *layout,
+                     const vsa_clusterparams *params, int device,
+                     vsa_cluster **cluster);
+/* the records of a list (a search result, or what vsa_select_finish
+   delivered) become edges; several calls accumulate (-d -p: two calls, the
+   direct list first).  palindromic != 0: a list of vmatch -p IDX.
+   VSA_NOT_COVERED, state untouched: a packed-pair result; a direct list with
+   a layout that is not VSA_SINK_SELF.  -2, state untouched: a record that
+   does not fit the layout. */
+int vsa_cluster_add(vsa_cluster *cluster, const vsa_result *result,
+                    int palindromic);
+/* forest, replay, numbering; may be called again after more lists */
+int vsa_cluster_finish(vsa_cluster *cluster);
+int vsa_cluster_getstats(const vsa_cluster *cluster, vsa_clusterstats *stats);
+/* after finish: cluster c has the members members[clusterstart[c] ..
+   clusterstart[c + 1]); stats.clusters + 1 and stats.inclusters entries */
+int vsa_cluster_members(const vsa_cluster *cluster, uint64_t *clusterstart,
+                        uint64_t *members);
+/* after finish: the cluster of every sequence or VSA_CLUSTER_SINGLET;
+   numofsequences entries */
+int vsa_cluster_labels(const vsa_cluster *cluster, uint64_t *label);
+/* after finish: the accepted records grouped by cluster, within a cluster in
+   descending edge number -- the order of the lines of PREFIX.size.cnum.match
+   (addClusterEdge, cluster.c:586-614) -- as a result in HBM that the sink
+   formats; palindromic[i] (stats.edges entries, may be NULL) is the D/P flag
+   of record i, the records of cluster c are edgestart[c] ..
+   edgestart[c + 1] (stats.clusters + 1 entries, may be NULL) */
+int vsa_cluster_edges(vsa_cluster *cluster, vsa_result **edges,
+                      uint8_t *palindromic, uint64_t *edgestart);
+/* after finish: what vmatch prints behind its "# args=" line: the lines of
+   clusterSizedistribution and one line "c: m m m" per cluster; returns the
+   bytes written (without the closing 0 byte), -3 if capacity is too small */
+int64_t vsa_cluster_format(const vsa_cluster *cluster, char *buffer,
+                           uint64_t capacity);
+/* HIP-event times of all calls so far, in ms */
+int vsa_cluster_times(const vsa_cluster *cluster, double *add_ms,
+                      double *finish_ms, double *edges_ms);
+void vsa_cluster_close(vsa_cluster *cluster);
+
+/*
+  The same on a list in host memory, no GPU involved: every edge goes through
+  linkcluster.  matches[i] with the flag palindromic[i] (NULL: all direct).
+  Outputs that are NULL are left out: clusterstart and edgestart
+  (numofsequences / 2 + 2 entries are enough), members and label
+  (numofsequences), edgerecord (n: the indices into matches of the accepted
+  records, grouped like vsa_cluster_edges groups them), buffer / capacity /
+  written like vsa_cluster_format.  On an error nothing is written.
+*/
+int vsa_cluster_host(const vsa_sinkparams *layout,
+                     const vsa_clusterparams *params, const vsa_match *matches,
+                     const uint8_t *palindromic, uint64_t n,
+                     vsa_clusterstats *stats, uint64_t *clusterstart,
+                     uint64_t *members, uint64_t *label, uint64_t *edgestart,
+                     uint64_t *edgerecord, char *buffer, uint64_t capacity,
+                     int64_t *written);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,20 @@ class SelectStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [("percsmall", C.c_uint32), ("perclarge", C.c_uint32)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in
+                ("seen", "samesequence", "mirrordropped", "rejected", "edges",
+                 "forestedges", "rounds", "clusters", "inclusters",
+                 "singlets")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROCESSMATCH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 
@@ -312,6 +326,23 @@ def _load():
                                 C.POINTER(SelectParams), V, V, U64, V, V, V,
                                 U64, C.POINTER(U64),
                                 C.POINTER(SelectStats)]),
+        "vsa_cluster_open": (I, [C.POINTER(SinkParams),
+                                 C.POINTER(ClusterParams), I, PP]),
+        "vsa_cluster_add": (I, [V, V, I]),
+        "vsa_cluster_finish": (I, [V]),
+        "vsa_cluster_getstats": (I, [V, C.POINTER(ClusterStats)]),
+        "vsa_cluster_members": (I, [V, V, V]),
+        "vsa_cluster_labels": (I, [V, V]),
+        "vsa_cluster_edges": (I, [V, PP, V, V]),
+        "vsa_cluster_format": (C.c_int64, [V, V, U64]),
+        "vsa_cluster_times": (I, [V, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double)]),
+        "vsa_cluster_close": (None, [V]),
+        "vsa_cluster_host": (I, [C.POINTER(SinkParams),
+                                 C.POINTER(ClusterParams), V, V, U64,
+                                 C.POINTER(ClusterStats), V, V, V, V, V, V,
+                                 U64, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1193,6 +1224,125 @@ def select_host(layout, matches, palindromic=None, **options):
                                n, C.byref(k), C.byref(st)))
     k = int(k.value)
     return out[:k], flags[:k], ev[:k], st
+
+
+# ---- sequence clustering (vmatch -dbcluster percsmall perclarge) ---------------
+
+CLUSTER_SINGLET = 0xFFFFFFFFFFFFFFFF
+CLUSTER_MAXROUNDS, CLUSTER_MAXJUMPS = 64, 64
+
+
+def _format_capacity(numofsequences, inclusters):
+    # three lines, a line per cluster size and per cluster, 21 bytes a member
+    return 512 + 64 * (numofsequences // 2 + 2) + 22 * (inclusters + 1)
+
+
+class Cluster:
+    """Single-linkage clusters of the sequences of an index from the match
+    lists added (vsa_cluster).  layout: what sink_params() returns, kind
+    SINK_SELF (or SINK_QUERY with selfpalindromic for lists of vmatch -p IDX
+    alone)."""
+
+    def __init__(self, layout, percsmall, perclarge, device=0):
+        self._layout = layout
+        self.numofsequences = int(layout[0].numofsequences)
+        p = ClusterParams(int(percsmall), int(perclarge))
+        self._h = C.c_void_p()
+        _check(lib.vsa_cluster_open(C.byref(layout[0]), C.byref(p), device,
+                                    C.byref(self._h)))
+
+    def add(self, result, palindromic=False):
+        _check(lib.vsa_cluster_add(self._h, result._h,
+                                   int(bool(palindromic))))
+
+    def finish(self):
+        _check(lib.vsa_cluster_finish(self._h))
+
+    def stats(self):
+        s = ClusterStats()
+        _check(lib.vsa_cluster_getstats(self._h, C.byref(s)))
+        return s
+
+    def members(self):
+        """-> (clusterstart, members): cluster c is
+        members[clusterstart[c]:clusterstart[c + 1]]"""
+        s = self.stats()
+        start = np.zeros(s.clusters + 1, np.uint64)
+        mem = np.zeros(s.inclusters, np.uint64)
+        _check(lib.vsa_cluster_members(self._h, _ptr(start), _ptr(mem)))
+        return start, mem
+
+    def labels(self):
+        out = np.zeros(self.numofsequences, np.uint64)
+        _check(lib.vsa_cluster_labels(self._h, _ptr(out)))
+        return out
+
+    def edges(self):
+        """-> (Result of the accepted records grouped by cluster, D/P flags,
+        edgestart)"""
+        s = self.stats()
+        flags = np.zeros(s.edges, np.uint8)
+        start = np.zeros(s.clusters + 1, np.uint64)
+        h = C.c_void_p()
+        _check(lib.vsa_cluster_edges(self._h, C.byref(h), _ptr(flags),
+                                     _ptr(start)))
+        return Result(h), flags, start
+
+    def format(self):
+        s = self.stats()
+        cap = _format_capacity(self.numofsequences, s.inclusters)
+        buf = np.empty(cap, np.uint8)
+        n = lib.vsa_cluster_format(self._h, _ptr(buf), cap)
+        if n < 0:
+            raise VsaError(int(n), messagespace())
+        return buf[:n].tobytes()
+
+    def times(self):
+        """HIP-event ms of all add / finish / edges calls so far"""
+        a, f, e = C.c_double(), C.c_double(), C.c_double()
+        _check(lib.vsa_cluster_times(self._h, C.byref(a), C.byref(f),
+                                     C.byref(e)))
+        return a.value, f.value, e.value
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_cluster_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def cluster_host(layout, percsmall, perclarge, matches, palindromic=None,
+                 text=True):
+    """the same clustering of a list in host memory, no GPU -> dict(stats,
+    clusterstart, members, labels, edgestart, edgerecord, text)"""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    n = len(matches)
+    pal = None if palindromic is None else \
+        np.ascontiguousarray(palindromic, np.uint8)
+    assert pal is None or len(pal) == n
+    nseq = int(layout[0].numofsequences)
+    p = ClusterParams(int(percsmall), int(perclarge))
+    st = ClusterStats()
+    cstart = np.zeros(nseq // 2 + 2, np.uint64)
+    estart = np.zeros(nseq // 2 + 2, np.uint64)
+    mem = np.zeros(nseq, np.uint64)
+    lab = np.zeros(nseq, np.uint64)
+    erec = np.zeros(n, np.uint64)
+    cap = _format_capacity(nseq, nseq) if text else 0
+    buf = np.empty(cap, np.uint8) if text else None
+    written = C.c_int64(0)
+    _check(lib.vsa_cluster_host(C.byref(layout[0]), C.byref(p), _ptr(matches),
+                                _ptr(pal), n, C.byref(st), _ptr(cstart),
+                                _ptr(mem), _ptr(lab), _ptr(estart),
+                                _ptr(erec), _ptr(buf), cap,
+                                C.byref(written)))
+    k = int(st.clusters)
+    return dict(stats=st, clusterstart=cstart[:k + 1],
+                members=mem[:int(st.inclusters)], labels=lab,
+                edgestart=estart[:k + 1], edgerecord=erec[:int(st.edges)],
+                text=buf[:written.value].tobytes() if text else None)
 
 
 # ---- synthetic inputs (SURVEY.md section 8d) ------------------------------
