@@ -1206,6 +1206,171 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
                      uint64_t *edgerecord, char *buffer, uint64_t capacity,
                      int64_t *written);
 
+/* ---- match clustering: vmatch -pp matchcluster gapsize G | overlap P
+   (Vmatch/initpost.c:307-333, Vmatch/clpos.c:14-201,
+   Vmatch/matchclust.c:87-128, kurtz/cluster.c:458-614) on match lists that
+   stay in HBM ----------------------------------------------------------------
+
+   Single-linkage clustering of the MATCHES of a list.  Match number m is the
+   index of the record over all add calls (the reference's idnumber when
+   nothing was selected away); length1, position1 and position2 are what
+   processfinal stores (the view vsa_select derives).  Every match gives two
+   references, (position1, index 2m) and (position2, index 2m + 1), both on
+   one axis -- also for lists against queries, where the second one is a
+   query coordinate: the reference mixes them (clpos.c:41-47).  The references
+   are sorted by their start alone, equal starts in the order of their index
+   (clpos.c:48: glibc's merging qsort).  With end_i = start_i + length1 of
+   the match of reference i, for i and every j > i of that order:
+
+     gapsize G  gap = start_j - end_i in unsigned 64-bit arithmetic; the loop
+                over j ends at the first gap > G (clpos.c:87-108).  A
+                successor that starts inside match i wraps to a huge value:
+                reference i then links nothing at all.  Otherwise i links
+                every j with start_j in [end_i, end_i + G].
+     overlap P  the loop over j ends at the first end_i < start_j
+                (clpos.c:145-182); overlap = ((double) (end_i - start_j) *
+                100.0) / (double) max(length1_i, length1_j), an edge iff
+                overlap >= (double) P.  length1 on both sides, also in
+                approximate lists.
+
+   An edge (m_i, m_j), in that orientation, with its gap or overlap is
+   stored where m_i != m_j; edges are numbered in the order (i ascending, j
+   ascending), and the same pair of matches may occur several times.  Every
+   edge goes through linkcluster in that order (matchclust.c:95-104); output
+   numbering, member order and the order of a cluster's edges (descending
+   edge number) are those of showClusterSet and addClusterEdge, as for
+   vsa_cluster above. */
+#define VSA_MATCHCLUSTER_GAP 0     /* gapsize G                             */
+#define VSA_MATCHCLUSTER_OVERLAP 1 /* overlap P                             */
+#define VSA_MATCHCLUSTER_ERATE 2   /* erate: not covered (cluedist.c)       */
+
+typedef struct
+{
+  int mode;
+  uint64_t maxgapsize;        /* VSA_MATCHCLUSTER_GAP, below 2^62           */
+  uint64_t minpercentoverlap; /* VSA_MATCHCLUSTER_OVERLAP                   */
+} vsa_matchclusterparams;
+
+typedef struct
+{
+  uint64_t matches;     /* records of all lists: the nodes                  */
+  uint64_t candidates;  /* pairs (i, j) inside a window                     */
+  uint64_t samematch;   /* ... of the two references of one match           */
+  uint64_t below;       /* ... with an overlap below the threshold          */
+  uint64_t edges;       /* ... stored: linkcluster calls                    */
+  uint64_t forestedges; /* edges that joined two different clusters         */
+  uint64_t rounds;      /* of the forest search (0 on the host)             */
+  uint64_t clusters;    /* after finish: clusters, ...                      */
+  uint64_t inclusters;  /* ... matches in them                              */
+} vsa_matchclusterstats;
+
+typedef struct vsa_matchcluster vsa_matchcluster;
+/* the stages vsa_matchcluster_times reports, in this order */
+#define VSA_MATCHCLUSTER_STAGES 6 /* refs sort window pairs forest group    */
+
+/*
+  layout: what the sink of these lists is opened with (kind, the index, the
+  query Multiseq); markpos, querystart and querylength need not outlive the
+  call.  0 and *cluster (on `device`), or a negative code and the message.
+  VSA_NOT_COVERED: mode VSA_MATCHCLUSTER_ERATE (the edit distance between the
+  match substrings, Vmatch/cluedist.c); a selfpalindromic layout (vmatch -p
+  IDX).
+*/
+int vsa_matchcluster_open(const vsa_sinkparams *layout,
+                          const vsa_matchclusterparams *params, int device,
+                          vsa_matchcluster **cluster);
+/* one more list: its records become the matches count .. count + n - 1 and
+   are copied, the caller may free the list.  palindromic: the list of the
+   reverse-complement pass (vmatch -d -p: two calls).  VSA_NOT_COVERED, state
+   untouched: a packed-pair result; a palindromic list under a self layout;
+   2^31 matches or more on the device (the index 2m + side of a reference is
+   32 bit there; the host code takes fewer than 2^32 - 1).  -2, state
+   untouched: a record that does not fit the layout. */
+int vsa_matchcluster_add(vsa_matchcluster *cluster, const vsa_result *result,
+                         int palindromic);
+/* clusters the matches added so far (more may be added, and finish called
+   again).  VSA_NOT_COVERED, state untouched: 2^32 - 1 edges or more.
+   VSA_MATCHCLUSTER_CHUNK in the environment bounds the candidate pairs
+   looked at per pass (default 2^26): the memory grows with the stored edges,
+   not with the candidates. */
+int vsa_matchcluster_finish(vsa_matchcluster *cluster);
+/* the counts of the last finish, matches included: a list added since then
+   shows only after the next finish (all 0 before the first) */
+int vsa_matchcluster_getstats(const vsa_matchcluster *cluster,
+                              vsa_matchclusterstats *stats);
+/* after finish: cluster c has the matches members[clusterstart[c] ..
+   clusterstart[c + 1]) in the order of its chain; stats.clusters + 1 and
+   stats.inclusters entries */
+int vsa_matchcluster_members(const vsa_matchcluster *cluster,
+                             uint64_t *clusterstart, uint64_t *members);
+/* after finish: the cluster of every match or VSA_CLUSTER_SINGLET;
+   stats.matches entries */
+int vsa_matchcluster_labels(const vsa_matchcluster *cluster, uint64_t *label);
+/* after finish: the edges grouped by cluster, within a cluster in the order
+   showClusterSet shows them (descending edge number): edge t links m0[t] and
+   m1[t] with value[t] (the gap, or the bits of the overlap percentage, a
+   double); the edges of cluster c are edgestart[c] .. edgestart[c + 1].
+   stats.clusters + 1 and stats.edges entries; any may be NULL */
+int vsa_matchcluster_edges(vsa_matchcluster *cluster, uint64_t *edgestart,
+                           uint32_t *m0, uint32_t *m1, uint64_t *value);
+/* after finish: the member matches of all clusters, in the order of
+   vsa_matchcluster_members, as a result in HBM that the sink prints like any
+   list; palindromic[t] (stats.inclusters entries, may be NULL) = the flag of
+   the list record t came from */
+int vsa_matchcluster_records(vsa_matchcluster *cluster, vsa_result **records,
+                             uint8_t *palindromic);
+/* after finish: what vmatch prints behind its "# args=" line -- "# cluster N
+   matches" and one "# create cluster c of size s" per cluster
+   (matchclust.c:10-16,94); returns the bytes written, -3 if the buffer is
+   too small */
+int64_t vsa_matchcluster_format(const vsa_matchcluster *cluster, char *buffer,
+                                uint64_t capacity);
+/* after finish: the bytes of the file PREFIX.size.c.match behind its first
+   line (matchclust.c:31-85): "# id m" and the match line per member, then
+   "# linked a and b with gapsize g" or "... with overlap percentage %.2f"
+   per edge.  The match lines are the sink's; the reference prints them with
+   its fixed default widths (vsa_sink_setdigits(sink, 5, 6, 6, 3, 3)).  Every
+   member is printed with the direction of the sink. */
+int64_t vsa_matchcluster_format_cluster(vsa_matchcluster *cluster,
+                                        vsa_sink *sink, uint64_t c,
+                                        char *buffer, uint64_t capacity);
+/* HIP-event times of all calls so far in ms, VSA_MATCHCLUSTER_STAGES of
+   them */
+int vsa_matchcluster_times(const vsa_matchcluster *cluster, double *ms);
+void vsa_matchcluster_close(vsa_matchcluster *cluster);
+
+/*
+  The same on a list in host memory, no GPU involved: every edge goes through
+  linkcluster.  Outputs that are NULL are left out: clusterstart and
+  edgestart (n / 2 + 2 entries are enough), members and label (n); m0, m1 and
+  value hold edgecapacity entries -- stats is written and -3 returned if
+  there are more edges than that.
+*/
+int vsa_matchcluster_host(const vsa_sinkparams *layout,
+                          const vsa_matchclusterparams *params,
+                          const vsa_match *matches, const uint8_t *palindromic,
+                          uint64_t n, vsa_matchclusterstats *stats,
+                          uint64_t *clusterstart, uint64_t *members,
+                          uint64_t *label, uint64_t *edgestart, uint32_t *m0,
+                          uint32_t *m1, uint64_t *value,
+                          uint64_t edgecapacity, char *buffer,
+                          uint64_t capacity, int64_t *written);
+/* the text of vsa_matchcluster_format_cluster from arrays in host memory:
+   the members of one cluster with their records, its edges */
+int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
+                                     const uint64_t *member,
+                                     const vsa_match *records, uint64_t size,
+                                     const uint32_t *m0, const uint32_t *m1,
+                                     const uint64_t *value, uint64_t nedges,
+                                     char *buffer, uint64_t capacity);
+
+/* the field widths of the sink's lines (length, position1, position2,
+   seqnum1, seqnum2) instead of those of the layout: what the reference's
+   post-processing prints its matches with (ASSIGNDEFAULTDIGITS,
+   Vmatch/outinfo.h:93-98: 5, 6, 6, 3, 3) */
+int vsa_sink_setdigits(vsa_sink *sink, int length, int position1,
+                       int position2, int seqnum1, int seqnum2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,20 @@ class ClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MatchClusterParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("maxgapsize", C.c_uint64),
+                ("minpercentoverlap", C.c_uint64)]
+
+
+class MatchClusterStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in
+                ("matches", "candidates", "samematch", "below", "edges",
+                 "forestedges", "rounds", "clusters", "inclusters")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROCESSMATCH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 
@@ -343,6 +357,27 @@ def _load():
                                  C.POINTER(ClusterParams), V, V, U64,
                                  C.POINTER(ClusterStats), V, V, V, V, V, V,
                                  U64, C.POINTER(C.c_int64)]),
+        "vsa_matchcluster_open": (I, [C.POINTER(SinkParams),
+                                      C.POINTER(MatchClusterParams), I, PP]),
+        "vsa_matchcluster_add": (I, [V, V, I]),
+        "vsa_matchcluster_finish": (I, [V]),
+        "vsa_matchcluster_getstats": (I, [V, C.POINTER(MatchClusterStats)]),
+        "vsa_matchcluster_members": (I, [V, V, V]),
+        "vsa_matchcluster_labels": (I, [V, V]),
+        "vsa_matchcluster_edges": (I, [V, V, V, V, V]),
+        "vsa_matchcluster_records": (I, [V, PP, V]),
+        "vsa_matchcluster_format": (C.c_int64, [V, V, U64]),
+        "vsa_matchcluster_format_cluster": (C.c_int64, [V, V, U64, V, U64]),
+        "vsa_matchcluster_times": (I, [V, V]),
+        "vsa_matchcluster_close": (None, [V]),
+        "vsa_matchcluster_host": (I, [C.POINTER(SinkParams),
+                                      C.POINTER(MatchClusterParams), V, V,
+                                      U64, C.POINTER(MatchClusterStats), V, V,
+                                      V, V, V, V, V, U64, V, U64,
+                                      C.POINTER(C.c_int64)]),
+        "vsa_matchcluster_format_host": (C.c_int64, [V, I, V, V, U64, V, V,
+                                                     V, U64, V, U64]),
+        "vsa_sink_setdigits": (I, [V, I, I, I, I, I]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -964,6 +999,13 @@ class Sink:
             raise VsaError(int(n), messagespace())
         return buf[:n].tobytes()
 
+    def setdigits(self, length=5, position1=6, position2=6, seqnum1=3,
+                  seqnum2=3):
+        """the field widths of the lines; the defaults are those the
+        reference's post-processing prints with (ASSIGNDEFAULTDIGITS)"""
+        _check(lib.vsa_sink_setdigits(self._h, length, position1, position2,
+                                      seqnum1, seqnum2))
+
     def close(self):
         if self._h and lib is not None:
             lib.vsa_sink_close(self._h)
@@ -1342,6 +1384,179 @@ def cluster_host(layout, percsmall, perclarge, matches, palindromic=None,
     return dict(stats=st, clusterstart=cstart[:k + 1],
                 members=mem[:int(st.inclusters)], labels=lab,
                 edgestart=estart[:k + 1], edgerecord=erec[:int(st.edges)],
+                text=buf[:written.value].tobytes() if text else None)
+
+
+# ---- match clustering (vmatch -pp matchcluster gapsize G | overlap P) ---------
+
+MATCHCLUSTER_GAP, MATCHCLUSTER_OVERLAP, MATCHCLUSTER_ERATE = 0, 1, 2
+MATCHCLUSTER_STAGES = ("refs", "sort", "window", "pairs", "forest", "group")
+
+
+def _matchcluster_params(mode, value):
+    return MatchClusterParams(int(mode),
+                              int(value) if mode == MATCHCLUSTER_GAP else 0,
+                              int(value) if mode != MATCHCLUSTER_GAP else 0)
+
+
+def _cluster_text_capacity(size, nedges):
+    # "# id m" and a match line per member, a "# linked" line per edge
+    return 256 + 224 * size + 96 * nedges
+
+
+def matchcluster_format_host(sink, mode, members, records, m0, m1, values):
+    """the bytes of a cluster's match file behind its first line, from the
+    members of one cluster with their records and its edges in host memory"""
+    members = np.ascontiguousarray(members, np.uint64)
+    records = np.ascontiguousarray(records, MATCH_DTYPE)
+    m0 = np.ascontiguousarray(m0, np.uint32)
+    m1 = np.ascontiguousarray(m1, np.uint32)
+    values = np.ascontiguousarray(values, np.uint64)
+    assert len(members) == len(records) and len(m0) == len(m1) == len(values)
+    cap = _cluster_text_capacity(len(members), len(m0))
+    buf = np.empty(cap, np.uint8)
+    n = lib.vsa_matchcluster_format_host(
+        sink._h, int(mode), _ptr(members), _ptr(records), len(members),
+        _ptr(m0), _ptr(m1), _ptr(values), len(m0), _ptr(buf), cap)
+    if n < 0:
+        raise VsaError(int(n), messagespace())
+    return buf[:n].tobytes()
+
+
+class MatchCluster:
+    """Single-linkage clusters of the matches of the lists added, linked by
+    gap or by overlap (vsa_matchcluster).  layout: what sink_params()
+    returns; mode MATCHCLUSTER_GAP with value = the largest gap, or
+    MATCHCLUSTER_OVERLAP with value = the least overlap in percent."""
+
+    def __init__(self, layout, mode, value, device=0):
+        self._layout = layout
+        self.mode = int(mode)
+        p = _matchcluster_params(mode, value)
+        self._h = C.c_void_p()
+        _check(lib.vsa_matchcluster_open(C.byref(layout[0]), C.byref(p),
+                                         device, C.byref(self._h)))
+
+    def add(self, result, palindromic=False):
+        _check(lib.vsa_matchcluster_add(self._h, result._h,
+                                        int(bool(palindromic))))
+
+    def finish(self):
+        _check(lib.vsa_matchcluster_finish(self._h))
+
+    def stats(self):
+        s = MatchClusterStats()
+        _check(lib.vsa_matchcluster_getstats(self._h, C.byref(s)))
+        return s
+
+    def members(self):
+        """-> (clusterstart, members): cluster c is
+        members[clusterstart[c]:clusterstart[c + 1]], match numbers"""
+        s = self.stats()
+        start = np.zeros(s.clusters + 1, np.uint64)
+        mem = np.zeros(s.inclusters, np.uint64)
+        _check(lib.vsa_matchcluster_members(self._h, _ptr(start), _ptr(mem)))
+        return start, mem
+
+    def labels(self):
+        out = np.zeros(self.stats().matches, np.uint64)
+        _check(lib.vsa_matchcluster_labels(self._h, _ptr(out)))
+        return out
+
+    def edges(self):
+        """-> (edgestart, m0, m1, values): the edges grouped by cluster in
+        the reference's order; values are gaps, or the bits of the overlap
+        percentages (values.view(np.float64))"""
+        s = self.stats()
+        start = np.zeros(s.clusters + 1, np.uint64)
+        m0 = np.zeros(s.edges, np.uint32)
+        m1 = np.zeros(s.edges, np.uint32)
+        val = np.zeros(s.edges, np.uint64)
+        _check(lib.vsa_matchcluster_edges(self._h, _ptr(start), _ptr(m0),
+                                          _ptr(m1), _ptr(val)))
+        return start, m0, m1, val
+
+    def records(self):
+        """-> (Result of the member matches of all clusters in member order,
+        D/P flags)"""
+        flags = np.zeros(self.stats().inclusters, np.uint8)
+        h = C.c_void_p()
+        _check(lib.vsa_matchcluster_records(self._h, C.byref(h),
+                                            _ptr(flags)))
+        return Result(h), flags
+
+    def format(self):
+        s = self.stats()
+        cap = 128 + 96 * (s.clusters + 1)
+        buf = np.empty(cap, np.uint8)
+        n = lib.vsa_matchcluster_format(self._h, _ptr(buf), cap)
+        if n < 0:
+            raise VsaError(int(n), messagespace())
+        return buf[:n].tobytes()
+
+    def format_cluster(self, sink, c, size, nedges):
+        """the bytes of PREFIX.size.c.match behind its first line; size and
+        nedges of cluster c bound the text"""
+        cap = _cluster_text_capacity(int(size), int(nedges))
+        buf = np.empty(cap, np.uint8)
+        n = lib.vsa_matchcluster_format_cluster(self._h, sink._h, int(c),
+                                                _ptr(buf), cap)
+        if n < 0:
+            raise VsaError(int(n), messagespace())
+        return buf[:n].tobytes()
+
+    def times(self):
+        """HIP-event ms of all calls so far per stage -> dict"""
+        ms = np.zeros(len(MATCHCLUSTER_STAGES), np.float64)
+        _check(lib.vsa_matchcluster_times(self._h, _ptr(ms)))
+        return dict(zip(MATCHCLUSTER_STAGES, ms.tolist()))
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_matchcluster_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def matchcluster_host(layout, mode, value, matches, palindromic=None,
+                      text=True):
+    """the same clustering of a list in host memory, no GPU -> dict(stats,
+    clusterstart, members, labels, edgestart, m0, m1, values, text)"""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    n = len(matches)
+    pal = None if palindromic is None else \
+        np.ascontiguousarray(palindromic, np.uint8)
+    assert pal is None or len(pal) == n
+    p = _matchcluster_params(mode, value)
+    st = MatchClusterStats()
+    # once for the number of edges, once for the edges
+    _check(lib.vsa_matchcluster_host(C.byref(layout[0]), C.byref(p),
+                                     _ptr(matches), _ptr(pal), n,
+                                     C.byref(st), None, None, None, None,
+                                     None, None, None, 0, None, 0, None))
+    ne = int(st.edges)
+    cstart = np.zeros(n // 2 + 2, np.uint64)
+    estart = np.zeros(n // 2 + 2, np.uint64)
+    mem = np.zeros(n, np.uint64)
+    lab = np.zeros(n, np.uint64)
+    m0 = np.zeros(ne, np.uint32)
+    m1 = np.zeros(ne, np.uint32)
+    val = np.zeros(ne, np.uint64)
+    cap = 128 + 96 * (n // 2 + 2) if text else 0
+    buf = np.empty(cap, np.uint8) if text else None
+    written = C.c_int64(0)
+    _check(lib.vsa_matchcluster_host(C.byref(layout[0]), C.byref(p),
+                                     _ptr(matches), _ptr(pal), n,
+                                     C.byref(st), _ptr(cstart), _ptr(mem),
+                                     _ptr(lab), _ptr(estart), _ptr(m0),
+                                     _ptr(m1), _ptr(val), ne, _ptr(buf), cap,
+                                     C.byref(written)))
+    k = int(st.clusters)
+    return dict(stats=st, clusterstart=cstart[:k + 1],
+                members=mem[:int(st.inclusters)], labels=lab,
+                edgestart=estart[:k + 1], m0=m0, m1=m1, values=val,
                 text=buf[:written.value].tobytes() if text else None)
 
 

@@ -34,13 +34,7 @@
 // positions and record indices 64 bit.
 #include "search_host.hpp"
 #include "cluster_rules.h"
-
-#define CL_BLOCK 256
-#define CL_IPT 4
-#define CL_TILE (CL_BLOCK * CL_IPT)
-#define CL_NONE 0xFFFFFFFFFFFFFFFFull
-
-static_assert(CL_TILE == VSA_SELECT_TILE, "the header names the tile");
+#include "cluster_forest.inc"
 
 struct vsa_cluster
 {
@@ -61,129 +55,6 @@ struct vsa_cluster
 
 namespace
 {
-
-// exclusive sum of one value per thread of a workgroup; sh: CL_BLOCK / 64
-// words of LDS
-__device__ __forceinline__ uint32_t cl_block_exscan(uint32_t v, uint32_t *sh,
-                                                    uint32_t &total)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t o = __shfl_up(incl, d);
-    if (lane >= (uint32_t) d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < CL_BLOCK / 64; w++)
-  {
-    const uint32_t x = sh[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  total = all;
-  return before + incl - v;
-}
-
-// ---- stable compaction of the items of class 0 -----------------------------
-// F::cls(i, payload) names the class of item i; the items of class 0 are
-// written in order through F::put(rank, i, payload), the others only counted
-// (totals[class]).
-
-template <class F>
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_count(F f, uint64_t n, uint64_t *__restrict__ tilecount,
-           unsigned long long *__restrict__ totals)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * CL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[CL_BLOCK / 64];
-  const uint64_t k0 = tile * CL_TILE + (uint64_t) threadIdx.x * CL_IPT;
-  uint32_t c[VSA_CL_CLASSES];
-#pragma unroll
-  for (int q = 0; q < VSA_CL_CLASSES; q++)
-  {
-    c[q] = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    if (k0 + j < n)
-    {
-      typename F::Payload p;
-      const int cls = f.cls(k0 + j, p);
-#pragma unroll
-      for (int q = 0; q < VSA_CL_CLASSES; q++)
-      {
-        c[q] += cls == q ? 1u : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < VSA_CL_CLASSES; q++)
-  {
-    uint32_t total;
-    (void) cl_block_exscan(c[q], sh, total);
-    if (threadIdx.x == 0)
-    {
-      if (q == 0)
-      {
-        tilecount[tile] = total;
-      }
-      else if (total != 0)
-      {
-        atomicAdd(&totals[q], (unsigned long long) total);
-      }
-    }
-  }
-}
-
-template <class F>
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_emit(F f, uint64_t n, const uint64_t *__restrict__ tileoffset)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * CL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[CL_BLOCK / 64];
-  const uint64_t k0 = tile * CL_TILE + (uint64_t) threadIdx.x * CL_IPT;
-  typename F::Payload p[CL_IPT];
-  int cls[CL_IPT];
-  uint32_t c = 0;
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    cls[j] = k0 + j < n ? f.cls(k0 + j, p[j]) : -1;
-    c += cls[j] == 0 ? 1u : 0u;
-  }
-  uint32_t total;
-  uint64_t o = tileoffset[tile] + cl_block_exscan(c, sh, total);
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    if (cls[j] == 0)
-    {
-      f.put(o, k0 + j, p[j]);
-      o++;
-    }
-  }
-}
 
 struct EdgePayload
 {
@@ -220,238 +91,6 @@ struct EdgeF
   }
 };
 
-struct NoPayload
-{
-};
-
-// the edges of the forest, in the order of their numbers
-struct ForestF
-{
-  typedef NoPayload Payload;
-  const uint8_t *inforest;
-  const uint32_t *e1, *e2;
-  uint32_t *f1, *f2;
-
-  __device__ int cls(uint64_t i, Payload &) const
-  {
-    return inforest[i] != 0 ? 0 : 1;
-  }
-  __device__ void put(uint64_t rank, uint64_t i, const Payload &) const
-  {
-    f1[rank] = e1[i];
-    f2[rank] = e2[i];
-  }
-};
-
-// ---- the forest --------------------------------------------------------------
-
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_iota(uint32_t *__restrict__ out, uint64_t n)
-{
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    out[i] = (uint32_t) i;
-  }
-}
-
-// parent[] is flat: parent[x] is the root of x.  Every live edge: dead if its
-// ends share a root, else a candidate of both roots.  *crossing counts the
-// candidates.
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_pick(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
-          uint64_t nedges, const uint32_t *__restrict__ parent,
-          uint8_t *__restrict__ live, unsigned long long *__restrict__ best,
-          unsigned long long *__restrict__ crossing)
-{
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
-  bool cross = false;
-  if (i < nedges && live[i] != 0)
-  {
-    const uint32_t ru = parent[e1[i]], rv = parent[e2[i]];
-    if (ru == rv)
-    {
-      live[i] = 0;
-    }
-    else
-    {
-      cross = true;
-      atomicMin(&best[ru], (unsigned long long) i);
-      atomicMin(&best[rv], (unsigned long long) i);
-    }
-  }
-  const uint64_t b = __ballot(cross);
-  if (b != 0 && (threadIdx.x & 63u) == (uint32_t) (__ffsll((unsigned long long) b) - 1))
-  {
-    atomicAdd(crossing, (unsigned long long) __popcll((unsigned long long) b));
-  }
-}
-
-// next[x] = the parent of x after this round's hooks; parent[] and best[] are
-// only read
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_hook(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
-          const uint32_t *__restrict__ parent,
-          const unsigned long long *__restrict__ best, uint64_t nseq,
-          uint32_t *__restrict__ next, uint8_t *__restrict__ inforest)
-{
-  const uint64_t x = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (x >= nseq)
-  {
-    return;
-  }
-  uint32_t to = parent[x];
-  if (to == (uint32_t) x)
-  {
-    const unsigned long long b = best[x];
-    if (b != CL_NONE)
-    {
-      const uint32_t ru = parent[e1[b]], rv = parent[e2[b]];
-      const uint32_t other = ru == (uint32_t) x ? rv : ru;
-      inforest[b] = 1;
-      // both roots chose b: the smaller one stays a root
-      if (best[other] != b || (uint32_t) x > other)
-      {
-        to = other;
-      }
-    }
-  }
-  next[x] = to;
-}
-
-// one jump; in place: whatever a lane reads is an ancestor
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_jump(uint32_t *__restrict__ parent, uint64_t nseq,
-          unsigned int *__restrict__ changed)
-{
-  const uint64_t x = vsa_bid() * CL_BLOCK + threadIdx.x;
-  bool ch = false;
-  if (x < nseq)
-  {
-    const uint32_t p = parent[x];
-    const uint32_t g = parent[p];
-    if (g != p)
-    {
-      parent[x] = g;
-      ch = true;
-    }
-  }
-  if (__ballot(ch) != 0 && (threadIdx.x & 63u) == 0)
-  {
-    *changed = 1u; // every writer stores the same value
-  }
-}
-
-// ---- grouping ----------------------------------------------------------------
-
-// position j of the reversed list: edge nedges - 1 - j, keyed by its cluster
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_keys(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
-          uint64_t nedges, const uint32_t *__restrict__ label,
-          uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
-          unsigned long long *__restrict__ bad)
-{
-  const uint64_t j = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (j < nedges)
-  {
-    const uint64_t i = nedges - 1 - j;
-    const uint32_t a = label[e1[i]], b = label[e2[i]];
-    if (a != b || a == 0xFFFFFFFFu)
-    {
-      atomicAdd(bad, 1ull);
-    }
-    keys[j] = a;
-    vals[j] = (uint32_t) i;
-  }
-}
-
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_gather(const vsa_match *__restrict__ recs,
-            const uint8_t *__restrict__ flags,
-            const uint32_t *__restrict__ order, uint64_t n,
-            vsa_match *__restrict__ outrecs, uint8_t *__restrict__ outflags)
-{
-  const uint64_t t = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (t < n)
-  {
-    const uint32_t i = order[t];
-    outrecs[t] = recs[i];
-    outflags[t] = flags[i];
-  }
-}
-
-// start[c] = the first position of the sorted keys that is not below c
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_starts(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nclusters,
-            uint64_t *__restrict__ start)
-{
-  const uint64_t c = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (c <= nclusters)
-  {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi)
-    {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (keys[mid] < c)
-      {
-        lo = mid + 1;
-      }
-      else
-      {
-        hi = mid;
-      }
-    }
-    start[c] = lo;
-  }
-}
-
-// ---- host ----------------------------------------------------------------------
-
-uint64_t tilesof(uint64_t n)
-{
-  return (n + CL_TILE - 1) / CL_TILE;
-}
-
-// tile counts of class 0 scanned into offsets (nt + 1 words); totals[q] =
-// items of class q
-template <class F>
-int cl_count(const F &f, uint64_t n, DevBuf &offsets, uint64_t *totals)
-{
-  const uint64_t nt = tilesof(n);
-  DevBuf counts, tot;
-  if (counts.alloc((nt + 1) * 8) != 0 || offsets.alloc((nt + 1) * 8) != 0 ||
-      tot.alloc(VSA_CL_CLASSES * 8) != 0)
-  {
-    return -100;
-  }
-  VSA_HIP(hipMemsetAsync(counts.p, 0, (nt + 1) * 8, nullptr));
-  VSA_HIP(hipMemsetAsync(tot.p, 0, VSA_CL_CLASSES * 8, nullptr));
-  k_cl_count<F><<<vsa_grid(nt), CL_BLOCK, 0, nullptr>>>(
-      f, n, counts.as<uint64_t>(), tot.as<unsigned long long>());
-  VSA_HIP(hipGetLastError());
-  if (exclusive_sum(counts.as<uint64_t>(), offsets.as<uint64_t>(), nt, nullptr,
-                    &totals[0]) != 0)
-  {
-    return -100;
-  }
-  uint64_t t[VSA_CL_CLASSES];
-  VSA_HIP(hipMemcpy(t, tot.p, sizeof t, hipMemcpyDeviceToHost));
-  for (int q = 1; q < VSA_CL_CLASSES; q++)
-  {
-    totals[q] = t[q];
-  }
-  return 0;
-}
-
-template <class F>
-int cl_emit(const F &f, uint64_t n, DevBuf &offsets)
-{
-  k_cl_emit<F><<<vsa_grid(tilesof(n)), CL_BLOCK, 0, nullptr>>>(
-      f, n, offsets.as<uint64_t>());
-  VSA_HIP(hipGetLastError());
-  return 0;
-}
-
 // room for `need` edges; what is there stays
 int reserve(vsa_cluster *c, uint64_t need)
 {
@@ -487,108 +126,6 @@ int reserve(vsa_cluster *c, uint64_t need)
   c->recs = (vsa_match *) recs.release();
   c->flags = (uint8_t *) flags.release();
   c->capacity = cap;
-  return 0;
-}
-
-// the edges of the minimum spanning forest (weight = edge number) in the
-// order of their numbers -> f1 / f2 on the host
-int forest(vsa_cluster *c, std::vector<uint32_t> &f1,
-           std::vector<uint32_t> &f2, uint64_t *rounds)
-{
-  const uint64_t nseq = c->rules.numofsequences, ne = c->nedges;
-  DevBuf parent, next, live, inforest, best, counters;
-  if (parent.alloc(nseq * 4) != 0 || next.alloc(nseq * 4) != 0 ||
-      live.alloc(ne) != 0 || inforest.alloc(ne) != 0 ||
-      best.alloc(nseq * 8) != 0 || counters.alloc(16) != 0)
-  {
-    return -100;
-  }
-  unsigned long long *crossing = counters.as<unsigned long long>();
-  unsigned int *changed = (unsigned int *) (crossing + 1);
-  k_cl_iota<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
-                                                     nseq);
-  VSA_HIP(hipGetLastError());
-  VSA_HIP(hipMemsetAsync(live.p, 1, ne, nullptr));
-  VSA_HIP(hipMemsetAsync(inforest.p, 0, ne, nullptr));
-  *rounds = 0;
-  for (;;)
-  {
-    uint64_t ncross = 0;
-    VSA_HIP(hipMemsetAsync(best.p, 0xFF, nseq * 8, nullptr));
-    VSA_HIP(hipMemsetAsync(counters.p, 0, 16, nullptr));
-    k_cl_pick<<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
-        c->e1, c->e2, ne, parent.as<uint32_t>(), live.as<uint8_t>(),
-        best.as<unsigned long long>(), crossing);
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(hipMemcpy(&ncross, crossing, 8, hipMemcpyDeviceToHost));
-    if (ncross == 0)
-    {
-      break;
-    }
-    if (*rounds == VSA_CLUSTER_MAXROUNDS)
-    {
-      VSA_ERROR("vsa_cluster_finish: %lu edges still join different "
-                "components after %u rounds", (unsigned long) ncross,
-                VSA_CLUSTER_MAXROUNDS);
-      return -101;
-    }
-    (*rounds)++;
-    k_cl_hook<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(
-        c->e1, c->e2, parent.as<uint32_t>(), best.as<unsigned long long>(),
-        nseq, next.as<uint32_t>(), inforest.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    std::swap(parent.p, next.p);
-    unsigned int ch = 1;
-    for (unsigned int jumps = 0; ch != 0; jumps++)
-    {
-      if (jumps == VSA_CLUSTER_MAXJUMPS)
-      {
-        VSA_ERROR("vsa_cluster_finish: the components are not flat after %u "
-                  "jumps", VSA_CLUSTER_MAXJUMPS);
-        return -101;
-      }
-      VSA_HIP(hipMemsetAsync(changed, 0, 4, nullptr));
-      k_cl_jump<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
-                                                         nseq, changed);
-      VSA_HIP(hipGetLastError());
-      VSA_HIP(hipMemcpy(&ch, changed, 4, hipMemcpyDeviceToHost));
-    }
-  }
-  ForestF ff;
-  ff.inforest = inforest.as<uint8_t>();
-  ff.e1 = c->e1;
-  ff.e2 = c->e2;
-  ff.f1 = ff.f2 = nullptr;
-  DevBuf offsets, d1, d2;
-  uint64_t totals[VSA_CL_CLASSES];
-  if (cl_count(ff, ne, offsets, totals) != 0)
-  {
-    return -100;
-  }
-  const uint64_t nf = totals[0];
-  if (nf >= nseq)
-  {
-    VSA_ERROR("vsa_cluster_finish: a forest of %lu edges over %lu sequences",
-              (unsigned long) nf, (unsigned long) nseq);
-    return -101;
-  }
-  f1.resize(nf);
-  f2.resize(nf);
-  if (nf > 0)
-  {
-    if (d1.alloc(nf * 4) != 0 || d2.alloc(nf * 4) != 0)
-    {
-      return -100;
-    }
-    ff.f1 = d1.as<uint32_t>();
-    ff.f2 = d2.as<uint32_t>();
-    if (cl_emit(ff, ne, offsets) != 0)
-    {
-      return -100;
-    }
-    VSA_HIP(hipMemcpy(f1.data(), d1.p, nf * 4, hipMemcpyDeviceToHost));
-    VSA_HIP(hipMemcpy(f2.data(), d2.p, nf * 4, hipMemcpyDeviceToHost));
-  }
   return 0;
 }
 
@@ -774,7 +311,8 @@ extern "C" int vsa_cluster_finish(vsa_cluster *c)
   t.start();
   if (c->nedges > 0)
   {
-    const int rc = forest(c, f1, f2, &rounds);
+    const int rc = cl_forest(c->rules.numofsequences, c->e1, c->e2, c->nedges,
+                             f1, f2, &rounds, "vsa_cluster_finish");
     if (rc != 0)
     {
       return rc;
@@ -953,56 +491,26 @@ extern "C" int vsa_cluster_edges(vsa_cluster *c, vsa_result **edges,
                     ? 0xFFFFFFFFu
                     : (uint32_t) c->res.label[s];
   }
-  DevBuf label, keys, keys2, vals, vals2, bad, starts, oflags;
-  if (label.alloc(nseq * 4) != 0 || keys.alloc(ne * 8) != 0 ||
-      keys2.alloc(ne * 8) != 0 || vals.alloc(ne * 4) != 0 ||
-      vals2.alloc(ne * 4) != 0 || bad.alloc(8) != 0 ||
-      starts.alloc((ncl + 1) * 8) != 0 || oflags.alloc(ne) != 0 ||
+  DevBuf order, oflags;
+  std::vector<uint64_t> hstart;
+  if (oflags.alloc(ne) != 0 ||
       vsa_dev_alloc((void **) &res->matches, ne * sizeof(vsa_match)) != 0)
   {
     return -100;
   }
-  VSA_HIP(hipMemcpyAsync(label.p, hlabel.data(), nseq * 4,
-                         hipMemcpyHostToDevice, nullptr));
-  VSA_HIP(hipMemsetAsync(bad.p, 0, 8, nullptr));
-  k_cl_keys<<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
-      c->e1, c->e2, ne, label.as<uint32_t>(), keys.as<uint64_t>(),
-      vals.as<uint32_t>(), bad.as<unsigned long long>());
-  VSA_HIP(hipGetLastError());
-  if (sortpairs(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
-                vals2.as<uint32_t>(), ne, nullptr) != 0)
+  rc = cl_group(c->e1, c->e2, ne, hlabel.data(), nseq, ncl, order, hstart,
+                "vsa_cluster_edges");
+  if (rc != 0)
   {
-    return -100;
+    return rc;
   }
-  k_cl_gather<<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
-      c->recs, c->flags, vals2.as<uint32_t>(), ne, res->matches,
-      oflags.as<uint8_t>());
-  VSA_HIP(hipGetLastError());
-  k_cl_starts<<<gridfor(ncl + 1), CL_BLOCK, 0, nullptr>>>(
-      keys2.as<uint64_t>(), ne, ncl, starts.as<uint64_t>());
+  const RecGather g = {c->recs, c->flags, res->matches, oflags.as<uint8_t>()};
+  k_cl_gather<RecGather><<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
+      g, order.as<uint32_t>(), ne);
   VSA_HIP(hipGetLastError());
   t.stop();
-  uint64_t nbad = 0;
-  std::vector<uint64_t> hstart(ncl + 1);
-  VSA_HIP(hipMemcpy(&nbad, bad.p, 8, hipMemcpyDeviceToHost));
-  VSA_HIP(hipMemcpy(hstart.data(), starts.p, (ncl + 1) * 8,
-                    hipMemcpyDeviceToHost));
+  VSA_HIP(hipStreamSynchronize(nullptr));
   c->edges_ms += t.ms();
-  // the reference's own consistency checks (cluster.c:605-611,
-  // vmcluster.c:507-513)
-  if (nbad != 0)
-  {
-    VSA_ERROR("vsa_cluster_edges: the two sequences of %lu edges do not "
-              "belong to the same cluster", (unsigned long) nbad);
-    return -101;
-  }
-  if (hstart[0] != 0 || hstart[ncl] != ne)
-  {
-    VSA_ERROR("number %lu of stored matches differs from number %lu of edges "
-              "used for clustering", (unsigned long) hstart[ncl],
-              (unsigned long) ne);
-    return -101;
-  }
   if (palindromic != nullptr)
   {
     VSA_HIP(hipMemcpy(palindromic, oflags.p, ne, hipMemcpyDeviceToHost));

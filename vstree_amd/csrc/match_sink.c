@@ -274,6 +274,27 @@ void vsa_sink_close(vsa_sink *s)
   }
 }
 
+/* ASSIGNDEFAULTDIGITS (Vmatch/outinfo.h:93-98) and its like: the widths the
+   post-processing prints with instead of those of the layout */
+int vsa_sink_setdigits(vsa_sink *s, int length, int position1, int position2,
+                       int seqnum1, int seqnum2)
+{
+  if (s == NULL || length < 1 || position1 < 1 || position2 < 1 ||
+      seqnum1 < 1 || seqnum2 < 1 || length > 12 || position1 > 12 ||
+      position2 > 12 || seqnum1 > 12 || seqnum2 > 12)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_setdigits: a sink and five "
+             "widths between 1 and 12");
+    return -1;
+  }
+  s->wlength = length;
+  s->wpos1 = position1;
+  s->wpos2 = position2;
+  s->wseq1 = seqnum1;
+  s->wseq2 = seqnum2;
+  return 0;
+}
+
 /* getseqinfo on the index (kurtz-basic/multiseq-adv.c:277-284): number of
    separators in front of pos, start and length of that sequence */
 static void seqinfo(const vsa_sink *s, uint64_t pos, uint64_t *seqnum,

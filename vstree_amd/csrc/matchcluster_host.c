@@ -1,0 +1,470 @@
+/*
+  Match clustering, host side: a fresh restatement of mirrorandsortmatches,
+  gapclustermatches and overlapclustermatches (Vmatch/clpos.c:34-201) as the
+  reference writes them -- two nested loops over the sorted references, the
+  inner one left at the first successor out of reach -- and of the lines of
+  domatchclustering (Vmatch/matchclust.c:10-128).  linkcluster, the numbering
+  of showClusterSet and the order of addClusterEdge are those of
+  cluster_host.c (vsa_cl_replay), over the matches as elements.
+  vsa_matchcluster_host sends every edge through linkcluster;
+  matchcluster.hip sends only the edges of the spanning forest it found
+  through the same code.  No GPU involved.
+*/
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <stdint.h>
+#include "vstree_amd.h"
+#include "matchcluster_rules.h"
+
+char *vsa_errbuf(void);
+#define ERRSIZE 1024
+
+int vsa_mc_checklayout(const vsa_sinkparams *layout,
+                       const vsa_matchclusterparams *params, const char *who,
+                       vsa_selrules *rules, vsa_mcrules *mcrules)
+{
+  if (layout == NULL || params == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
+    return -1;
+  }
+  if (params->mode == VSA_MATCHCLUSTER_ERATE)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: matchcluster erate (the edit distance "
+             "between the match substrings) is not covered", who);
+    return VSA_NOT_COVERED;
+  }
+  if (params->mode != VSA_MATCHCLUSTER_GAP &&
+      params->mode != VSA_MATCHCLUSTER_OVERLAP)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: illegal mode %d", who, params->mode);
+    return -2;
+  }
+  if (params->mode == VSA_MATCHCLUSTER_GAP &&
+      params->maxgapsize >= VSA_MC_MAXGAP)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: a gap size of %lu is beyond 2^62", who,
+             (unsigned long) params->maxgapsize);
+    return -2;
+  }
+  if (layout->selfpalindromic)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of vmatch -p IDX "
+             "(selfpalindromic) are not covered", who);
+    return VSA_NOT_COVERED;
+  }
+  if (layout->kind < VSA_SINK_COMPLETE ||
+      layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
+      layout->totalquerylength + 1 > layout->totallength ||
+      (layout->kind != VSA_SINK_SELF && layout->numofqueries > 0 &&
+       (layout->querystart == NULL || layout->querylength == NULL)))
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: incomplete layout", who);
+    return -2;
+  }
+  /* the view of a match (select_rules.h); no E-value is looked at */
+  memset(rules, 0, sizeof *rules);
+  rules->kind = layout->kind;
+  rules->noevalue = 1;
+  rules->totallength = (double) layout->totallength;
+  if (layout->kind == VSA_SINK_SELF)
+  {
+    rules->hasindexedqueries = layout->totalquerylength > 0;
+    rules->dblenplus1 = layout->totallength - layout->totalquerylength;
+  } else
+  {
+    rules->nq = layout->numofqueries;
+    rules->qstart = layout->querystart;
+    rules->qlen = layout->querylength;
+  }
+  mcrules->mode = params->mode;
+  mcrules->maxgapsize = params->maxgapsize;
+  mcrules->minpercentoverlap = params->minpercentoverlap;
+  return 0;
+}
+
+/* bounded text: the bytes that did not fit are counted, not written */
+typedef struct
+{
+  char *p;
+  uint64_t cap, len;
+} textbuf;
+
+static void put(textbuf *t, const char *s, size_t n)
+{
+  if (t->len + n < t->cap)
+  {
+    memcpy(t->p + t->len, s, n);
+  }
+  t->len += n;
+}
+
+static int64_t endtext(textbuf *t, const char *who)
+{
+  if (t->len >= t->cap)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu bytes do not fit a buffer of %lu",
+             who, (unsigned long) t->len + 1, (unsigned long) t->cap);
+    return -3;
+  }
+  t->p[t->len] = '\0';
+  return (int64_t) t->len;
+}
+
+/* domatchclustering and showclnum, matchclust.c:10-16,94 */
+int64_t vsa_mc_format(uint64_t matches, const vsa_clresult *r, char *buffer,
+                      uint64_t capacity)
+{
+  textbuf t = {buffer, capacity, 0};
+  char line[128];
+  uint64_t c;
+  int n;
+
+  n = snprintf(line, sizeof line, "# cluster %lu matches\n",
+               (unsigned long) matches);
+  put(&t, line, (size_t) n);
+  for (c = 0; c < r->clusters; c++)
+  {
+    n = snprintf(line, sizeof line, "# create cluster %lu of size %lu\n",
+                 (unsigned long) c,
+                 (unsigned long) (r->clusterstart[c + 1] - r->clusterstart[c]));
+    put(&t, line, (size_t) n);
+  }
+  return endtext(&t, "vsa_matchcluster_format");
+}
+
+/* showclelem and showedge with the two mcllinkinfo functions,
+   matchclust.c:31-85, clpos.c:53-70 */
+int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
+                                     const uint64_t *member,
+                                     const vsa_match *records, uint64_t size,
+                                     const uint32_t *m0, const uint32_t *m1,
+                                     const uint64_t *value, uint64_t nedges,
+                                     char *buffer, uint64_t capacity)
+{
+  textbuf t = {buffer, capacity, 0};
+  char line[512];
+  uint64_t i;
+  int n;
+
+  if (sink == NULL || buffer == NULL || (size > 0 && (member == NULL ||
+      records == NULL)) || (nedges > 0 && (m0 == NULL || m1 == NULL ||
+      value == NULL)))
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_format_host: NULL "
+             "argument");
+    return -1;
+  }
+  for (i = 0; i < size; i++)
+  {
+    int64_t w;
+    n = snprintf(line, sizeof line, "# id %lu\n", (unsigned long) member[i]);
+    put(&t, line, (size_t) n);
+    w = vsa_sink_format(sink, records + i, 1, line, sizeof line);
+    if (w < 0)
+    {
+      return w;
+    }
+    put(&t, line, (size_t) w);
+  }
+  for (i = 0; i < nedges; i++)
+  {
+    if (mode == VSA_MATCHCLUSTER_GAP)
+    {
+      n = snprintf(line, sizeof line,
+                   "# linked %lu and %lu with gapsize %lu\n",
+                   (unsigned long) m0[i], (unsigned long) m1[i],
+                   (unsigned long) value[i]);
+    } else
+    {
+      double overlap;
+      memcpy(&overlap, value + i, 8);
+      n = snprintf(line, sizeof line,
+                   "# linked %lu and %lu with overlap percentage %.2f\n",
+                   (unsigned long) m0[i], (unsigned long) m1[i], overlap);
+    }
+    put(&t, line, (size_t) n);
+  }
+  return endtext(&t, "vsa_matchcluster_format_cluster");
+}
+
+/* ---- the references, sorted like glibc's qsort sorts them ---------------- */
+
+typedef struct
+{
+  uint64_t start;
+  uint32_t matchnum;
+} Mref;
+
+/* a merge sort that takes the left run on ties: equal starts keep the order
+   of their index */
+static void sortrefs(Mref *a, Mref *tmp, uint64_t n)
+{
+  uint64_t width, lo;
+
+  for (width = 1; width < n; width *= 2)
+  {
+    for (lo = 0; lo < n; lo += 2 * width)
+    {
+      const uint64_t mid = lo + width < n ? lo + width : n,
+                     hi = lo + 2 * width < n ? lo + 2 * width : n;
+      uint64_t i = lo, j = mid, k = lo;
+      while (i < mid && j < hi)
+      {
+        tmp[k++] = a[j].start < a[i].start ? a[j++] : a[i++];
+      }
+      while (i < mid)
+      {
+        tmp[k++] = a[i++];
+      }
+      while (j < hi)
+      {
+        tmp[k++] = a[j++];
+      }
+    }
+    memcpy(a, tmp, (size_t) n * sizeof *a);
+  }
+}
+
+typedef struct
+{
+  uint32_t *m0, *m1;
+  uint64_t *value;
+  uint64_t n, cap;
+} Edges;
+
+static int addedge(Edges *e, uint32_t a, uint32_t b, uint64_t value)
+{
+  if (e->n == e->cap)
+  {
+    const uint64_t cap = e->cap ? 2 * e->cap : 1024;
+    uint32_t *m0 = realloc(e->m0, (size_t) cap * sizeof *m0);
+    uint32_t *m1 = m0 ? realloc(e->m1, (size_t) cap * sizeof *m1) : NULL;
+    uint64_t *v = m1 ? realloc(e->value, (size_t) cap * sizeof *v) : NULL;
+    if (m0 != NULL)
+    {
+      e->m0 = m0;
+    }
+    if (m1 != NULL)
+    {
+      e->m1 = m1;
+    }
+    if (v == NULL)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+      return -1;
+    }
+    e->value = v;
+    e->cap = cap;
+  }
+  e->m0[e->n] = a;
+  e->m1[e->n] = b;
+  e->value[e->n++] = value;
+  return 0;
+}
+
+int vsa_matchcluster_host(const vsa_sinkparams *layout,
+                          const vsa_matchclusterparams *params,
+                          const vsa_match *matches, const uint8_t *palindromic,
+                          uint64_t n, vsa_matchclusterstats *stats,
+                          uint64_t *clusterstart, uint64_t *members,
+                          uint64_t *label, uint64_t *edgestart, uint32_t *m0,
+                          uint32_t *m1, uint64_t *value,
+                          uint64_t edgecapacity, char *buffer,
+                          uint64_t capacity, int64_t *written)
+{
+  vsa_selrules rules;
+  vsa_mcrules mc;
+  vsa_matchclusterstats st;
+  vsa_clresult res;
+  Edges e = {NULL, NULL, NULL, 0, 0};
+  Mref *ref = NULL, *tmp = NULL;
+  uint64_t *length = NULL, *fill = NULL;
+  uint64_t i, j;
+  int64_t bytes = 0;
+  int rc = vsa_mc_checklayout(layout, params, "vsa_matchcluster_host", &rules,
+                              &mc);
+
+  if (rc != 0)
+  {
+    return rc;
+  }
+  if (matches == NULL && n > 0)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: NULL argument");
+    return -1;
+  }
+  if (n >= 0xFFFFFFFFull)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: %lu matches: only "
+             "fewer than 2^32 - 1 are covered", (unsigned long) n);
+    return VSA_NOT_COVERED;
+  }
+  memset(&st, 0, sizeof st);
+  memset(&res, 0, sizeof res);
+  st.matches = n;
+  ref = malloc((size_t) (2 * n + 1) * sizeof *ref);
+  tmp = malloc((size_t) (2 * n + 1) * sizeof *tmp);
+  length = malloc((size_t) (n + 1) * sizeof *length);
+  if (ref == NULL || tmp == NULL || length == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+    rc = -1;
+    goto done;
+  }
+  for (i = 0; i < n; i++)
+  {
+    const int pal = palindromic != NULL && palindromic[i] != 0;
+    vsa_selvalues v;
+    if (pal && layout->kind == VSA_SINK_SELF)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: palindromic "
+               "self matches are the selfpalindromic form");
+      rc = VSA_NOT_COVERED;
+      goto done;
+    }
+    if (vsa_sel_values(&rules, matches + i, pal, &v) != 0)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: record %lu does "
+               "not fit the layout", (unsigned long) i);
+      rc = -2;
+      goto done;
+    }
+    length[i] = v.length1;
+    ref[2 * i].start = v.position1;
+    ref[2 * i].matchnum = (uint32_t) i;
+    ref[2 * i + 1].start = v.position2;
+    ref[2 * i + 1].matchnum = (uint32_t) i;
+  }
+  sortrefs(ref, tmp, 2 * n);
+  for (i = 0; i + 1 < 2 * n; i++)
+  {
+    const uint64_t len_i = length[ref[i].matchnum],
+                   end_i = ref[i].start + len_i;
+    for (j = i + 1; j < 2 * n; j++)
+    {
+      uint64_t val = 0;
+      int cls;
+      if (vsa_mc_stops(&mc, end_i, ref[j].start))
+      {
+        break;
+      }
+      st.candidates++;
+      cls = vsa_mc_classify(&mc, end_i, len_i, ref[i].matchnum, ref[j].start,
+                            length[ref[j].matchnum], ref[j].matchnum, &val);
+      if (cls == VSA_MC_SAME)
+      {
+        st.samematch++;
+      } else if (cls == VSA_MC_BELOW)
+      {
+        st.below++;
+      } else
+      {
+        if (e.n + 1 >= 0xFFFFFFFFull)
+        {
+          snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: only fewer "
+                   "than 2^32 - 1 edges are covered");
+          rc = VSA_NOT_COVERED;
+          goto done;
+        }
+        if (addedge(&e, ref[i].matchnum, ref[j].matchnum, val) != 0)
+        {
+          rc = -1;
+          goto done;
+        }
+      }
+    }
+  }
+  st.edges = e.n;
+  if ((rc = vsa_cl_replay(n, e.m0, e.m1, e.n, &st.forestedges, &res)) != 0)
+  {
+    goto done;
+  }
+  st.clusters = res.clusters;
+  st.inclusters = res.inclusters;
+  if (stats != NULL)
+  {
+    *stats = st;
+  }
+  if ((m0 != NULL || m1 != NULL || value != NULL) && e.n > edgecapacity)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: %lu edges, room "
+             "for %lu", (unsigned long) e.n, (unsigned long) edgecapacity);
+    rc = -3;
+    goto done;
+  }
+  if (buffer != NULL &&
+      (bytes = vsa_mc_format(n, &res, buffer, capacity)) < 0)
+  {
+    rc = (int) bytes;
+    goto done;
+  }
+  if (edgestart != NULL || m0 != NULL || m1 != NULL || value != NULL)
+  {
+    /* addClusterEdge (cluster.c:586-614): each cluster's part is filled
+       from the back in the order of the edges */
+    fill = calloc((size_t) res.clusters + 2, sizeof *fill);
+    if (fill == NULL)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+      rc = -1;
+      goto done;
+    }
+    for (i = 0; i < e.n; i++)
+    {
+      fill[res.label[e.m0[i]] + 1]++;
+    }
+    for (i = 0; i < res.clusters; i++)
+    {
+      fill[i + 1] += fill[i];
+    }
+    if (edgestart != NULL)
+    {
+      memcpy(edgestart, fill, (size_t) (res.clusters + 1) * sizeof *fill);
+    }
+    for (i = 0; i < e.n; i++)
+    {
+      const uint64_t at = --fill[res.label[e.m0[i]] + 1];
+      if (m0 != NULL)
+      {
+        m0[at] = e.m0[i];
+      }
+      if (m1 != NULL)
+      {
+        m1[at] = e.m1[i];
+      }
+      if (value != NULL)
+      {
+        value[at] = e.value[i];
+      }
+    }
+  }
+  if (clusterstart != NULL)
+  {
+    memcpy(clusterstart, res.clusterstart,
+           (size_t) (res.clusters + 1) * sizeof *clusterstart);
+  }
+  if (members != NULL && res.inclusters > 0)
+  {
+    memcpy(members, res.members, (size_t) res.inclusters * sizeof *members);
+  }
+  if (label != NULL && n > 0)
+  {
+    memcpy(label, res.label, (size_t) n * sizeof *label);
+  }
+  if (written != NULL)
+  {
+    *written = bytes;
+  }
+done:
+  vsa_cl_freeresult(&res);
+  free(fill);
+  free(e.m0);
+  free(e.m1);
+  free(e.value);
+  free(ref);
+  free(tmp);
+  free(length);
+  return rc;
+}
