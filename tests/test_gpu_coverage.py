@@ -250,6 +250,58 @@ def test_extraction_across_workgroups(V):
         cov.nomatch(1, 10, nsym)
 
 
+@pytest.mark.parametrize("nruns", [1023, 1024, 1025, 2049])
+def test_run_compaction_at_tile_edges(V, nruns):
+    """exactly nruns maximal clear runs, alternately 1 and 2 positions long
+    with one marked position between two of them: the runs of at least
+    minlength are compacted over tiles of SELECT_TILE = 1024 runs"""
+    assert V.SELECT_TILE == 1024
+    lengths = 1 + np.arange(nruns) % 2
+    starts = np.concatenate(([0], np.cumsum(lengths + 1)[:-1]))
+    nbits = int(starts[-1] + lengths[-1])
+    assert nbits < 10000
+    cov, t = one_sequence(V, nbits)
+    mark_both(V, cov, t, records([(int(p) - 1, 1) for p in starts[1:]]))
+    assert np.array_equal(cov.bits(), t.words())
+    every = cov.nomatch(1)
+    assert len(every) == nruns
+    assert np.array_equal(every["start"], starts)
+    assert np.array_equal(every["length"], lengths)
+    assert np.array_equal(every, M.model_nomatch(t, 1))
+    two = cov.nomatch(2)
+    assert len(two) == nruns // 2 and (two["length"] == 2).all()
+    assert np.array_equal(two["start"], starts[lengths == 2])
+    assert np.array_equal(two, M.model_nomatch(t, 2))
+    assert len(cov.nomatch(3)) == 0 == len(M.model_nomatch(t, 3))
+
+
+def test_more_than_256_extraction_tiles(V):
+    """the tile counts of one extraction are more than one workgroup scans in
+    one step: clear runs in the first tile, across the edge between tiles
+    255 and 256, in tile 256 and at the very end"""
+    tile = V.COVERAGE_EXTRACT_TILE
+    nbits = 257 * tile + 100
+    clear = [(1000, 7), (256 * tile - 3, 7), (256 * tile + 5000, 5),
+             (nbits - 6, 6)]
+    cov, t = one_sequence(V, nbits)
+    inst, pos = [], 0
+    for p, l in clear:
+        inst.append((pos, p - pos))
+        pos = p + l
+    assert pos == nbits
+    mark_both(V, cov, t, records(inst))
+    assert np.array_equal(cov.bits(), t.words())
+    want = M.model_nomatch(t, 1)
+    assert [(int(r["start"]), int(r["length"])) for r in want] == clear
+    assert np.array_equal(cov.nomatch(1), want)
+    first = 255 * tile + 777
+    for length in (nbits - first, nbits - first - 2, tile + 5002 - 777):
+        sub = M.model_nomatch(t, 1, first, length)
+        assert len(sub) in (2, 3)
+        assert np.array_equal(cov.nomatch(1, first, length), sub), length
+    assert np.array_equal(cov.nomatch(6), M.model_nomatch(t, 6))
+
+
 def q_host(lengths):
     lengths = np.asarray(lengths, np.uint64)
     start = np.concatenate(([0], np.cumsum(lengths + np.uint64(1))[:-1]))

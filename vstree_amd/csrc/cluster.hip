@@ -5,10 +5,10 @@
 //
 //   edges    one lane per record, tiles of VSA_SELECT_TILE records: the two
 //            sequences by binary search in markpos, the overlap test.  The
-//            accepted records are compacted stably: count per tile, exclusive
-//            scan of the tile counts, write in order, behind the edges of the
-//            lists added before.  An edge keeps its record and its D/P flag:
-//            the caller may free the list.
+//            accepted records go through the stable compaction of
+//            tile_compact.inc behind the edges of the lists added before.
+//            An edge keeps its record and its D/P flag: the caller may free
+//            the list.
 //   forest   linkcluster is sequential, but an edge changes its state only if
 //            its ends are in different clusters at that moment: those edges
 //            are the minimum spanning forest of the list with weight = edge
@@ -82,7 +82,7 @@ struct EdgeF
     p.s2 = (uint32_t) s2;
     return c;
   }
-  __device__ void put(uint64_t rank, uint64_t i, const Payload &p) const
+  __device__ void put(int, uint64_t rank, uint64_t i, const Payload &p) const
   {
     e1[base + rank] = p.s1;
     e2[base + rank] = p.s2;
@@ -91,7 +91,9 @@ struct EdgeF
   }
 };
 
-// room for `need` edges; what is there stays
+// room for `need` edges; what is there stays.  Array by array (one wait
+// each, the old and the new block of one array at a time): where a later one
+// fails, the earlier ones are larger than `capacity` says, which stays right
 int reserve(vsa_cluster *c, uint64_t need)
 {
   if (need <= c->capacity)
@@ -99,43 +101,14 @@ int reserve(vsa_cluster *c, uint64_t need)
     return 0;
   }
   const uint64_t cap = std::max<uint64_t>(need, 2 * c->capacity);
-  DevBuf e1, e2, recs, flags;
-  if (e1.alloc(cap * 4) != 0 || e2.alloc(cap * 4) != 0 ||
-      recs.alloc(cap * sizeof(vsa_match)) != 0 || flags.alloc(cap) != 0)
+  if (grow((void **) &c->e1, c->nedges, cap, 4) != 0 ||
+      grow((void **) &c->e2, c->nedges, cap, 4) != 0 ||
+      grow((void **) &c->recs, c->nedges, cap, sizeof(vsa_match)) != 0 ||
+      grow((void **) &c->flags, c->nedges, cap, 1) != 0)
   {
     return -100;
   }
-  if (c->nedges > 0)
-  {
-    VSA_HIP(hipMemcpyAsync(e1.p, c->e1, c->nedges * 4, hipMemcpyDeviceToDevice,
-                           nullptr));
-    VSA_HIP(hipMemcpyAsync(e2.p, c->e2, c->nedges * 4, hipMemcpyDeviceToDevice,
-                           nullptr));
-    VSA_HIP(hipMemcpyAsync(recs.p, c->recs, c->nedges * sizeof(vsa_match),
-                           hipMemcpyDeviceToDevice, nullptr));
-    VSA_HIP(hipMemcpyAsync(flags.p, c->flags, c->nedges,
-                           hipMemcpyDeviceToDevice, nullptr));
-    VSA_HIP(hipStreamSynchronize(nullptr));
-  }
-  vsa_dev_free(c->e1);
-  vsa_dev_free(c->e2);
-  vsa_dev_free(c->recs);
-  vsa_dev_free(c->flags);
-  c->e1 = (uint32_t *) e1.release();
-  c->e2 = (uint32_t *) e2.release();
-  c->recs = (vsa_match *) recs.release();
-  c->flags = (uint8_t *) flags.release();
   c->capacity = cap;
-  return 0;
-}
-
-int enter(const vsa_cluster *c)
-{
-  if (vsa_set_device(c->device) != 0)
-  {
-    return -100;
-  }
-  vsa_dev_set_stream(nullptr);
   return 0;
 }
 
@@ -172,11 +145,10 @@ extern "C" int vsa_cluster_open(const vsa_sinkparams *layout,
   {
     return rc;
   }
-  if (vsa_set_device(device) != 0)
+  if (enter(device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   vsa_cluster *c = new vsa_cluster();
   c->device = device;
   c->kind = layout->kind;
@@ -226,7 +198,7 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
               r->device, c->device);
     return -2;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -246,7 +218,7 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
   ef.flags = nullptr;
   DevBuf offsets;
   uint64_t totals[VSA_CL_CLASSES];
-  if (cl_count(ef, r->count, offsets, totals) != 0)
+  if (tc_count<1, VSA_CL_CLASSES>(ef, r->count, offsets, totals) != 0)
   {
     return -100;
   }
@@ -276,7 +248,7 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
     ef.e2 = c->e2;
     ef.recs = c->recs;
     ef.flags = c->flags;
-    if (cl_emit(ef, r->count, offsets) != 0)
+    if (tc_emit<1>(ef, r->count, offsets) != 0)
     {
       return -100;
     }
@@ -301,7 +273,7 @@ extern "C" int vsa_cluster_finish(vsa_cluster *c)
     VSA_ERROR("vsa_cluster_finish: NULL argument");
     return -1;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -454,7 +426,7 @@ extern "C" int vsa_cluster_edges(vsa_cluster *c, vsa_result **edges,
     return -1;
   }
   *edges = nullptr;
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -470,27 +442,9 @@ extern "C" int vsa_cluster_edges(vsa_cluster *c, vsa_result **edges,
     *edges = res;
     return 0;
   }
-  // (the guard owns the list until it is handed over)
-  struct Guard
-  {
-    vsa_result *r;
-    ~Guard()
-    {
-      if (r != nullptr)
-      {
-        vsa_result_free(r);
-      }
-    }
-  } guard = {res};
+  ResultGuard guard = {res};
   Timer t(nullptr);
   t.start();
-  std::vector<uint32_t> hlabel(nseq);
-  for (uint64_t s = 0; s < nseq; s++)
-  {
-    hlabel[s] = c->res.label[s] == VSA_CLUSTER_SINGLET
-                    ? 0xFFFFFFFFu
-                    : (uint32_t) c->res.label[s];
-  }
   DevBuf order, oflags;
   std::vector<uint64_t> hstart;
   if (oflags.alloc(ne) != 0 ||
@@ -498,14 +452,14 @@ extern "C" int vsa_cluster_edges(vsa_cluster *c, vsa_result **edges,
   {
     return -100;
   }
-  rc = cl_group(c->e1, c->e2, ne, hlabel.data(), nseq, ncl, order, hstart,
+  rc = cl_group(c->e1, c->e2, ne, c->res.label, nseq, ncl, order, hstart,
                 "vsa_cluster_edges");
   if (rc != 0)
   {
     return rc;
   }
   const RecGather g = {c->recs, c->flags, res->matches, oflags.as<uint8_t>()};
-  k_cl_gather<RecGather><<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
+  k_cl_gather<RecGather><<<gridfor(ne), TC_BLOCK, 0, nullptr>>>(
       g, order.as<uint32_t>(), ne);
   VSA_HIP(hipGetLastError());
   t.stop();

@@ -1,13 +1,13 @@
 // The part of the clustering that does not care what the nodes are, for the
 // translation units that cluster something: cluster.hip (the sequences of an
 // index, vmatch -dbcluster) and matchcluster.hip (the matches of a list,
-// vmatch -pp matchcluster).  Included inside no namespace; everything here
-// lands in an unnamed one.
+// vmatch -pp matchcluster).  Included inside no namespace, after
+// search_host.hpp and the rules of the including file (VSA_CL_CLASSES,
+// vsa_clresult); everything here lands in an unnamed one.
 //
-//   compaction  F::cls(i, payload) names the class of item i; the items of
-//               class 0 are written in order through F::put(rank, i, payload),
-//               the others only counted: count per tile of VSA_SELECT_TILE
-//               items, exclusive scan of the tile counts, emit.
+//   compaction  tile_compact.inc, which this file includes: the functors
+//               here and in the including files keep class 0 (NE = 1) and
+//               total the VSA_CL_CLASSES - 1 others.
 //   forest      cl_forest: the edges (e1[i], e2[i]) over `nodes` nodes that
 //               change the state of linkcluster -- the minimum spanning forest
 //               with weight = edge number -- by Boruvka rounds, compacted in
@@ -17,142 +17,12 @@
 //               cluster's edges together in descending number, the order
 //               addClusterEdge leaves them in.
 // Node and edge numbers are 32 bit: the callers refuse more.
-#define CL_BLOCK 256
-#define CL_IPT 4
-#define CL_TILE (CL_BLOCK * CL_IPT)
 #define CL_NONE 0xFFFFFFFFFFFFFFFFull
 
-static_assert(CL_TILE == VSA_SELECT_TILE, "the header names the tile");
+#include "tile_compact.inc"
 
 namespace
 {
-
-// exclusive sum of one value per thread of a workgroup; sh: CL_BLOCK / 64
-// words of LDS
-__device__ __forceinline__ uint32_t cl_block_exscan(uint32_t v, uint32_t *sh,
-                                                    uint32_t &total)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t o = __shfl_up(incl, d);
-    if (lane >= (uint32_t) d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < CL_BLOCK / 64; w++)
-  {
-    const uint32_t x = sh[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  total = all;
-  return before + incl - v;
-}
-
-// ---- stable compaction of the items of class 0 -----------------------------
-// F::cls(i, payload) names the class of item i; the items of class 0 are
-// written in order through F::put(rank, i, payload), the others only counted
-// (totals[class]).
-
-template <class F>
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_count(F f, uint64_t n, uint64_t *__restrict__ tilecount,
-           unsigned long long *__restrict__ totals)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * CL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[CL_BLOCK / 64];
-  const uint64_t k0 = tile * CL_TILE + (uint64_t) threadIdx.x * CL_IPT;
-  uint32_t c[VSA_CL_CLASSES];
-#pragma unroll
-  for (int q = 0; q < VSA_CL_CLASSES; q++)
-  {
-    c[q] = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    if (k0 + j < n)
-    {
-      typename F::Payload p;
-      const int cls = f.cls(k0 + j, p);
-#pragma unroll
-      for (int q = 0; q < VSA_CL_CLASSES; q++)
-      {
-        c[q] += cls == q ? 1u : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < VSA_CL_CLASSES; q++)
-  {
-    uint32_t total;
-    (void) cl_block_exscan(c[q], sh, total);
-    if (threadIdx.x == 0)
-    {
-      if (q == 0)
-      {
-        tilecount[tile] = total;
-      }
-      else if (total != 0)
-      {
-        atomicAdd(&totals[q], (unsigned long long) total);
-      }
-    }
-  }
-}
-
-template <class F>
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_emit(F f, uint64_t n, const uint64_t *__restrict__ tileoffset)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * CL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[CL_BLOCK / 64];
-  const uint64_t k0 = tile * CL_TILE + (uint64_t) threadIdx.x * CL_IPT;
-  typename F::Payload p[CL_IPT];
-  int cls[CL_IPT];
-  uint32_t c = 0;
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    cls[j] = k0 + j < n ? f.cls(k0 + j, p[j]) : -1;
-    c += cls[j] == 0 ? 1u : 0u;
-  }
-  uint32_t total;
-  uint64_t o = tileoffset[tile] + cl_block_exscan(c, sh, total);
-#pragma unroll
-  for (int j = 0; j < CL_IPT; j++)
-  {
-    if (cls[j] == 0)
-    {
-      f.put(o, k0 + j, p[j]);
-      o++;
-    }
-  }
-}
-
-struct NoPayload
-{
-};
 
 // the edges of the forest, in the order of their numbers
 struct ForestF
@@ -166,7 +36,7 @@ struct ForestF
   {
     return inforest[i] != 0 ? 0 : 1;
   }
-  __device__ void put(uint64_t rank, uint64_t i, const Payload &) const
+  __device__ void put(int, uint64_t rank, uint64_t i, const Payload &) const
   {
     f1[rank] = e1[i];
     f2[rank] = e2[i];
@@ -175,26 +45,16 @@ struct ForestF
 
 // ---- the forest --------------------------------------------------------------
 
-__global__ void __launch_bounds__(CL_BLOCK)
-k_cl_iota(uint32_t *__restrict__ out, uint64_t n)
-{
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    out[i] = (uint32_t) i;
-  }
-}
-
 // parent[] is flat: parent[x] is the root of x.  Every live edge: dead if its
 // ends share a root, else a candidate of both roots.  *crossing counts the
 // candidates.
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_pick(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
           uint64_t nedges, const uint32_t *__restrict__ parent,
           uint8_t *__restrict__ live, unsigned long long *__restrict__ best,
           unsigned long long *__restrict__ crossing)
 {
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   bool cross = false;
   if (i < nedges && live[i] != 0)
   {
@@ -219,13 +79,13 @@ k_cl_pick(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
 
 // next[x] = the parent of x after this round's hooks; parent[] and best[] are
 // only read
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_hook(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
           const uint32_t *__restrict__ parent,
           const unsigned long long *__restrict__ best, uint64_t nseq,
           uint32_t *__restrict__ next, uint8_t *__restrict__ inforest)
 {
-  const uint64_t x = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t x = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (x >= nseq)
   {
     return;
@@ -250,11 +110,11 @@ k_cl_hook(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
 }
 
 // one jump; in place: whatever a lane reads is an ancestor
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_jump(uint32_t *__restrict__ parent, uint64_t nseq,
           unsigned int *__restrict__ changed)
 {
-  const uint64_t x = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t x = vsa_bid() * TC_BLOCK + threadIdx.x;
   bool ch = false;
   if (x < nseq)
   {
@@ -275,13 +135,13 @@ k_cl_jump(uint32_t *__restrict__ parent, uint64_t nseq,
 // ---- grouping ----------------------------------------------------------------
 
 // position j of the reversed list: edge nedges - 1 - j, keyed by its cluster
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_keys(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
           uint64_t nedges, const uint32_t *__restrict__ label,
           uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
           unsigned long long *__restrict__ bad)
 {
-  const uint64_t j = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t j = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (j < nedges)
   {
     const uint64_t i = nedges - 1 - j;
@@ -297,10 +157,10 @@ k_cl_keys(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
 
 // out[t] = in[order[t]], whatever G::move makes of it
 template <class G>
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_gather(G g, const uint32_t *__restrict__ order, uint64_t n)
 {
-  const uint64_t t = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t t = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (t < n)
   {
     g.move(t, order[t]);
@@ -323,11 +183,11 @@ struct RecGather
 };
 
 // start[c] = the first position of the sorted keys that is not below c
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cl_starts(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nclusters,
             uint64_t *__restrict__ start)
 {
-  const uint64_t c = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t c = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (c <= nclusters)
   {
     uint64_t lo = 0, hi = n;
@@ -349,51 +209,6 @@ k_cl_starts(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nclusters,
 
 // ---- host ----------------------------------------------------------------------
 
-uint64_t tilesof(uint64_t n)
-{
-  return (n + CL_TILE - 1) / CL_TILE;
-}
-
-// tile counts of class 0 scanned into offsets (nt + 1 words); totals[q] =
-// items of class q
-template <class F>
-int cl_count(const F &f, uint64_t n, DevBuf &offsets, uint64_t *totals)
-{
-  const uint64_t nt = tilesof(n);
-  DevBuf counts, tot;
-  if (counts.alloc((nt + 1) * 8) != 0 || offsets.alloc((nt + 1) * 8) != 0 ||
-      tot.alloc(VSA_CL_CLASSES * 8) != 0)
-  {
-    return -100;
-  }
-  VSA_HIP(hipMemsetAsync(counts.p, 0, (nt + 1) * 8, nullptr));
-  VSA_HIP(hipMemsetAsync(tot.p, 0, VSA_CL_CLASSES * 8, nullptr));
-  k_cl_count<F><<<vsa_grid(nt), CL_BLOCK, 0, nullptr>>>(
-      f, n, counts.as<uint64_t>(), tot.as<unsigned long long>());
-  VSA_HIP(hipGetLastError());
-  if (exclusive_sum(counts.as<uint64_t>(), offsets.as<uint64_t>(), nt, nullptr,
-                    &totals[0]) != 0)
-  {
-    return -100;
-  }
-  uint64_t t[VSA_CL_CLASSES];
-  VSA_HIP(hipMemcpy(t, tot.p, sizeof t, hipMemcpyDeviceToHost));
-  for (int q = 1; q < VSA_CL_CLASSES; q++)
-  {
-    totals[q] = t[q];
-  }
-  return 0;
-}
-
-template <class F>
-int cl_emit(const F &f, uint64_t n, DevBuf &offsets)
-{
-  k_cl_emit<F><<<vsa_grid(tilesof(n)), CL_BLOCK, 0, nullptr>>>(
-      f, n, offsets.as<uint64_t>());
-  VSA_HIP(hipGetLastError());
-  return 0;
-}
-
 // the edges of the minimum spanning forest (weight = edge number) in the
 // order of their numbers -> f1 / f2 on the host
 int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
@@ -409,7 +224,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
   }
   unsigned long long *crossing = counters.as<unsigned long long>();
   unsigned int *changed = (unsigned int *) (crossing + 1);
-  k_cl_iota<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
+  k_tc_iota<<<gridfor(nseq), TC_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
                                                      nseq);
   VSA_HIP(hipGetLastError());
   VSA_HIP(hipMemsetAsync(live.p, 1, ne, nullptr));
@@ -420,7 +235,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
     uint64_t ncross = 0;
     VSA_HIP(hipMemsetAsync(best.p, 0xFF, nseq * 8, nullptr));
     VSA_HIP(hipMemsetAsync(counters.p, 0, 16, nullptr));
-    k_cl_pick<<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
+    k_cl_pick<<<gridfor(ne), TC_BLOCK, 0, nullptr>>>(
         e1, e2, ne, parent.as<uint32_t>(), live.as<uint8_t>(),
         best.as<unsigned long long>(), crossing);
     VSA_HIP(hipGetLastError());
@@ -436,7 +251,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
       return -101;
     }
     (*rounds)++;
-    k_cl_hook<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(
+    k_cl_hook<<<gridfor(nseq), TC_BLOCK, 0, nullptr>>>(
         e1, e2, parent.as<uint32_t>(), best.as<unsigned long long>(),
         nseq, next.as<uint32_t>(), inforest.as<uint8_t>());
     VSA_HIP(hipGetLastError());
@@ -451,7 +266,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
         return -101;
       }
       VSA_HIP(hipMemsetAsync(changed, 0, 4, nullptr));
-      k_cl_jump<<<gridfor(nseq), CL_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
+      k_cl_jump<<<gridfor(nseq), TC_BLOCK, 0, nullptr>>>(parent.as<uint32_t>(),
                                                          nseq, changed);
       VSA_HIP(hipGetLastError());
       VSA_HIP(hipMemcpy(&ch, changed, 4, hipMemcpyDeviceToHost));
@@ -464,7 +279,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
   ff.f1 = ff.f2 = nullptr;
   DevBuf offsets, d1, d2;
   uint64_t totals[VSA_CL_CLASSES];
-  if (cl_count(ff, ne, offsets, totals) != 0)
+  if (tc_count<1, VSA_CL_CLASSES>(ff, ne, offsets, totals) != 0)
   {
     return -100;
   }
@@ -485,7 +300,7 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
     }
     ff.f1 = d1.as<uint32_t>();
     ff.f2 = d2.as<uint32_t>();
-    if (cl_emit(ff, ne, offsets) != 0)
+    if (tc_emit<1>(ff, ne, offsets) != 0)
     {
       return -100;
     }
@@ -496,27 +311,33 @@ int cl_forest(uint64_t nseq, const uint32_t *e1, const uint32_t *e2,
 }
 
 // order[t] = the number of the edge at place t when the edges are grouped by
-// the cluster label[] gives their ends (0xFFFFFFFF: in no cluster), each
-// group in descending number; hstart[c] = the first place of cluster c
-// (ncl + 1 entries).  With the reference's own consistency checks
-// (cluster.c:605-611, vmcluster.c:507-513).
+// the cluster label[] gives their ends (VSA_CLUSTER_SINGLET: in no cluster;
+// host memory, as vsa_cl_replay leaves it), each group in descending number;
+// hstart[c] = the first place of cluster c (ncl + 1 entries).  With the
+// reference's own consistency checks (cluster.c:605-611, vmcluster.c:507-513).
 int cl_group(const uint32_t *e1, const uint32_t *e2, uint64_t ne,
-             const uint32_t *hlabel, uint64_t nnodes, uint64_t ncl,
+             const uint64_t *label, uint64_t nnodes, uint64_t ncl,
              DevBuf &order, std::vector<uint64_t> &hstart, const char *who)
 {
-  DevBuf label, keys, keys2, vals, bad, starts;
-  if (label.alloc(nnodes * 4) != 0 || keys.alloc(ne * 8) != 0 ||
+  std::vector<uint32_t> hlabel(nnodes);
+  for (uint64_t x = 0; x < nnodes; x++)
+  {
+    hlabel[x] = label[x] == VSA_CLUSTER_SINGLET ? 0xFFFFFFFFu
+                                                : (uint32_t) label[x];
+  }
+  DevBuf dlabel, keys, keys2, vals, bad, starts;
+  if (dlabel.alloc(nnodes * 4) != 0 || keys.alloc(ne * 8) != 0 ||
       keys2.alloc(ne * 8) != 0 || vals.alloc(ne * 4) != 0 ||
       order.alloc(ne * 4) != 0 || bad.alloc(8) != 0 ||
       starts.alloc((ncl + 1) * 8) != 0)
   {
     return -100;
   }
-  VSA_HIP(hipMemcpyAsync(label.p, hlabel, nnodes * 4, hipMemcpyHostToDevice,
-                         nullptr));
+  VSA_HIP(hipMemcpyAsync(dlabel.p, hlabel.data(), nnodes * 4,
+                         hipMemcpyHostToDevice, nullptr));
   VSA_HIP(hipMemsetAsync(bad.p, 0, 8, nullptr));
-  k_cl_keys<<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
-      e1, e2, ne, label.as<uint32_t>(), keys.as<uint64_t>(),
+  k_cl_keys<<<gridfor(ne), TC_BLOCK, 0, nullptr>>>(
+      e1, e2, ne, dlabel.as<uint32_t>(), keys.as<uint64_t>(),
       vals.as<uint32_t>(), bad.as<unsigned long long>());
   VSA_HIP(hipGetLastError());
   if (sortpairs(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
@@ -524,12 +345,12 @@ int cl_group(const uint32_t *e1, const uint32_t *e2, uint64_t ne,
   {
     return -100;
   }
-  k_cl_starts<<<gridfor(ncl + 1), CL_BLOCK, 0, nullptr>>>(
+  k_cl_starts<<<gridfor(ncl + 1), TC_BLOCK, 0, nullptr>>>(
       keys2.as<uint64_t>(), ne, ncl, starts.as<uint64_t>());
   VSA_HIP(hipGetLastError());
   uint64_t nbad = 0;
   hstart.resize(ncl + 1);
-  // (the copy of the pageable label[] above is over when these return)
+  // (the copy of the pageable hlabel[] above is over when these return)
   VSA_HIP(hipMemcpy(&nbad, bad.p, 8, hipMemcpyDeviceToHost));
   VSA_HIP(hipMemcpy(hstart.data(), starts.p, (ncl + 1) * 8,
                     hipMemcpyDeviceToHost));

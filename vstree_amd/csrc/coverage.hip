@@ -18,21 +18,21 @@
 //            lists put thousands of instances on the same words).
 //   extract  the maximal runs of clear bits inside [first, first + len): per
 //            word the run starts (clear, predecessor set or outside) and the
-//            run ends; both go through the same three steps -- count per tile,
-//            exclusive scan of the tile counts by one workgroup, write in order
-//            -- so the k-th start pairs with the k-th end; the runs of at
-//            least minlength are then compacted in order by the same three
-//            steps, and get their sequence number from a binary search in the
-//            separator positions.
+//            run ends; both go through the three steps of tile_compact.inc
+//            -- count per tile, exclusive_sum() of the tile counts, write in
+//            order -- in kernels of their own (k_cov_tilecount, k_cov_emit:
+//            one word gives 0 to 64 positions, and the counts are 64 bit), so
+//            the k-th start pairs with the k-th end; the runs of at least
+//            minlength then go through the compaction of tile_compact.inc
+//            itself (RunF), and get their sequence number from a binary
+//            search in the separator positions.
 //   count    popcount reduction; separators are set from the start, so marked
 //            positions = set bits - separators.
 //   merge    OR of one table into another.
-#include "vsa_internal.hpp"
-#include <algorithm>
+#include "search_host.hpp"
+#include "tile_compact.inc"
 
-#define COV_BLOCK 256
-#define COV_WPT 4 // words (of the table) or runs per thread of a tile
-#define COV_TILE (COV_BLOCK * COV_WPT)
+#define COV_TILE TC_TILE // words of the table per tile of the extraction
 
 static_assert(COV_TILE * 64 == VSA_COVERAGE_EXTRACT_TILE,
               "the header names the tile of the extraction kernels");
@@ -59,57 +59,16 @@ struct vsa_coverage
 namespace
 {
 
-__device__ __forceinline__ uint64_t cov_shfl64(uint64_t v, int src)
-{
-  const uint32_t lo = __shfl((uint32_t) v, src);
-  const uint32_t hi = __shfl((uint32_t) (v >> 32), src);
-  return ((uint64_t) hi << 32) | lo;
-}
-
-// workgroup-wide exclusive sum of one value per thread (COV_BLOCK threads);
-// sh: COV_BLOCK / 64 words of LDS
-__device__ __forceinline__ uint64_t cov_block_exscan(uint64_t v, uint64_t *sh,
-                                                     uint64_t &total)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint64_t o = cov_shfl64(incl, (int) (lane >= (uint32_t) d ? lane - d : lane));
-    if (lane >= (uint32_t) d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < COV_BLOCK / 64; w++)
-  {
-    const uint64_t x = sh[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  total = all;
-  return before + incl - v;
-}
-
 // ---- initialisation -------------------------------------------------------
 
 // separator bits of a text: one word per wavefront step, the 64 lanes read
 // 64 consecutive symbols
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_sepbits(const uint8_t *__restrict__ tis, uint64_t n,
               uint64_t *__restrict__ bits, uint64_t nwords)
 {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wavesperblock = COV_BLOCK / 64;
+  const uint64_t wavesperblock = TC_BLOCK / 64;
   uint64_t w = vsa_bid() * wavesperblock + (threadIdx.x >> 6);
   const uint64_t stride = vsa_nblocks() * wavesperblock;
   for (; w < nwords; w += stride)
@@ -125,10 +84,10 @@ k_cov_sepbits(const uint8_t *__restrict__ tis, uint64_t n,
 }
 
 // separator positions of a batch of reads of one length m: (i + 1)(m + 1) - 1
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_uniform_seppos(uint64_t *__restrict__ seppos, uint64_t nsep, uint64_t m)
 {
-  const uint64_t i = vsa_bid() * COV_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (i < nsep)
   {
     seppos[i] = (i + 1) * (m + 1) - 1;
@@ -136,11 +95,11 @@ k_cov_uniform_seppos(uint64_t *__restrict__ seppos, uint64_t nsep, uint64_t m)
 }
 
 // sets the bits at the given positions (the separators of a query table)
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_setbits(uint64_t *__restrict__ bits, uint64_t nbits,
               const uint64_t *__restrict__ pos, uint64_t npos)
 {
-  const uint64_t i = vsa_bid() * COV_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (i < npos && pos[i] < nbits)
   {
     atomicOr((unsigned long long *) &bits[pos[i] >> 6], 1ull << (pos[i] & 63));
@@ -250,7 +209,7 @@ __device__ __forceinline__ void cov_set_instances(const CovMark &a, uint64_t p,
   {
     const int src = __ffsll((unsigned long long) todo) - 1;
     todo &= todo - 1;
-    const uint64_t lp = cov_shfl64(p, src), ll = cov_shfl64(len, src);
+    const uint64_t lp = vsa_shfl64(p, src), ll = vsa_shfl64(len, src);
     const uint64_t w1 = (lp + ll - 1) >> 6;
     for (uint64_t w = (lp >> 6) + lane; w <= w1; w += 64)
     {
@@ -260,10 +219,10 @@ __device__ __forceinline__ void cov_set_instances(const CovMark &a, uint64_t p,
 }
 
 // markmatches (Vmatch/markmat.c:42-118) for one record per lane
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_mark(CovMark a, const vsa_match *__restrict__ matches, uint64_t count)
 {
-  const uint64_t i = vsa_bid() * COV_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   // whole wavefronts behind the last record leave together
   if ((i & ~63ull) >= count)
   {
@@ -420,7 +379,7 @@ __device__ __forceinline__ uint64_t cov_derived(const CovRange &r, uint64_t k)
 }
 
 template <int MODE>
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_tilecount(CovRange r, uint64_t *__restrict__ tilecount)
 {
   const uint64_t tile = vsa_bid();
@@ -428,55 +387,30 @@ k_cov_tilecount(CovRange r, uint64_t *__restrict__ tilecount)
   {
     return;
   }
-  __shared__ uint64_t sh[COV_BLOCK / 64];
-  // thread t takes words t, t + COV_BLOCK, ... of the tile: coalesced, and the
+  __shared__ uint64_t sh[TC_BLOCK / 64];
+  // thread t takes words t, t + TC_BLOCK, ... of the tile: coalesced, and the
   // order does not matter for a count
   uint64_t c = 0;
 #pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
+  for (int j = 0; j < TC_IPT; j++)
   {
-    const uint64_t k = tile * COV_TILE + (uint64_t) j * COV_BLOCK + threadIdx.x;
+    const uint64_t k = tile * COV_TILE + (uint64_t) j * TC_BLOCK + threadIdx.x;
     if (k < r.nw)
     {
       c += (uint64_t) __popcll((unsigned long long) cov_derived<MODE>(r, k));
     }
   }
   uint64_t total;
-  (void) cov_block_exscan(c, sh, total);
+  (void) tc_block_exsum(c, sh, total);
   if (threadIdx.x == 0)
   {
     tilecount[tile] = total;
   }
 }
 
-// exclusive scan of the tile counts, in place, by one workgroup; *total = sum
-__global__ void __launch_bounds__(COV_BLOCK)
-k_cov_scan(uint64_t *__restrict__ tilecount, uint64_t ntiles,
-           uint64_t *__restrict__ total)
-{
-  __shared__ uint64_t sh[COV_BLOCK / 64];
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < ntiles; base += COV_BLOCK)
-  {
-    const uint64_t i = base + threadIdx.x;
-    const uint64_t v = i < ntiles ? tilecount[i] : 0;
-    uint64_t sum;
-    const uint64_t ex = cov_block_exscan(v, sh, sum);
-    if (i < ntiles)
-    {
-      tilecount[i] = carry + ex;
-    }
-    carry += sum;
-  }
-  if (threadIdx.x == 0)
-  {
-    *total = carry;
-  }
-}
-
 // positions of the set bits of the derived words, ascending
 template <int MODE>
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_emit(CovRange r, const uint64_t *__restrict__ tileoffset,
            uint64_t *__restrict__ out, uint64_t capacity)
 {
@@ -485,21 +419,21 @@ k_cov_emit(CovRange r, const uint64_t *__restrict__ tileoffset,
   {
     return;
   }
-  __shared__ uint64_t sh[COV_BLOCK / 64];
-  // thread t takes COV_WPT consecutive words: the positions come out in order
-  const uint64_t k0 = tile * COV_TILE + (uint64_t) threadIdx.x * COV_WPT;
-  uint64_t word[COV_WPT];
+  __shared__ uint64_t sh[TC_BLOCK / 64];
+  // thread t takes TC_IPT consecutive words: the positions come out in order
+  const uint64_t k0 = tile * COV_TILE + (uint64_t) threadIdx.x * TC_IPT;
+  uint64_t word[TC_IPT];
   uint64_t c = 0;
 #pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
+  for (int j = 0; j < TC_IPT; j++)
   {
     word[j] = k0 + j < r.nw ? cov_derived<MODE>(r, k0 + j) : 0;
     c += (uint64_t) __popcll((unsigned long long) word[j]);
   }
   uint64_t total;
-  uint64_t o = tileoffset[tile] + cov_block_exscan(c, sh, total);
+  uint64_t o = tileoffset[tile] + tc_block_exsum(c, sh, total);
 #pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
+  for (int j = 0; j < TC_IPT; j++)
   {
     uint64_t v = word[j];
     while (v != 0)
@@ -515,111 +449,65 @@ k_cov_emit(CovRange r, const uint64_t *__restrict__ tileoffset,
   }
 }
 
-// runs [start[k], last[k]] of at least minlength positions, per tile
-__global__ void __launch_bounds__(COV_BLOCK)
-k_cov_runcount(const uint64_t *__restrict__ start,
-               const uint64_t *__restrict__ last, uint64_t nruns,
-               uint64_t minlength, uint64_t *__restrict__ tilecount)
+// the runs [start[k], last[k]] of at least minlength positions, in order, as
+// (length, absolute start, sequence number, relative start)
+struct RunF
 {
-  const uint64_t tile = vsa_bid();
-  if (tile * COV_TILE >= nruns)
-  {
-    return;
-  }
-  __shared__ uint64_t sh[COV_BLOCK / 64];
-  uint64_t c = 0;
-#pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
-  {
-    const uint64_t k = tile * COV_TILE + (uint64_t) j * COV_BLOCK + threadIdx.x;
-    if (k < nruns && last[k] - start[k] + 1 >= minlength)
-    {
-      c++;
-    }
-  }
-  uint64_t total;
-  (void) cov_block_exscan(c, sh, total);
-  if (threadIdx.x == 0)
-  {
-    tilecount[tile] = total;
-  }
-}
+  typedef NoPayload Payload;
+  const uint64_t *start, *last;
+  uint64_t minlength;
+  const uint64_t *seppos;
+  uint64_t nsep;
+  vsa_match *out;
+  uint64_t capacity;
 
-// ... written in order as (length, absolute start, sequence number, relative
-// start)
-__global__ void __launch_bounds__(COV_BLOCK)
-k_cov_runemit(const uint64_t *__restrict__ start,
-              const uint64_t *__restrict__ last, uint64_t nruns,
-              uint64_t minlength, const uint64_t *__restrict__ tileoffset,
-              const uint64_t *__restrict__ seppos, uint64_t nsep,
-              vsa_match *__restrict__ out, uint64_t capacity)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * COV_TILE >= nruns)
+  __device__ int cls(uint64_t k, Payload &) const
   {
-    return;
+    return last[k] - start[k] + 1 >= minlength ? 0 : -1;
   }
-  __shared__ uint64_t sh[COV_BLOCK / 64];
-  const uint64_t k0 = tile * COV_TILE + (uint64_t) threadIdx.x * COV_WPT;
-  uint64_t c = 0;
-#pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
+  __device__ void put(int, uint64_t rank, uint64_t k, const Payload &) const
   {
-    if (k0 + j < nruns && last[k0 + j] - start[k0 + j] + 1 >= minlength)
+    const uint64_t s = start[k];
+    const uint64_t seq = cov_seqnum(seppos, nsep, s);
+    if (rank < capacity)
     {
-      c++;
+      vsa_match m;
+      m.length = last[k] - s + 1;
+      m.dbstart = s;
+      m.queryseq = seq;
+      m.querystart = s - (seq == 0 ? 0 : seppos[seq - 1] + 1);
+      out[rank] = m;
     }
   }
-  uint64_t total;
-  uint64_t o = tileoffset[tile] + cov_block_exscan(c, sh, total);
-#pragma unroll
-  for (int j = 0; j < COV_WPT; j++)
-  {
-    if (k0 + j < nruns && last[k0 + j] - start[k0 + j] + 1 >= minlength)
-    {
-      const uint64_t s = start[k0 + j];
-      const uint64_t seq = cov_seqnum(seppos, nsep, s);
-      if (o < capacity)
-      {
-        vsa_match m;
-        m.length = last[k0 + j] - s + 1;
-        m.dbstart = s;
-        m.queryseq = seq;
-        m.querystart = s - (seq == 0 ? 0 : seppos[seq - 1] + 1);
-        out[o] = m;
-      }
-      o++;
-    }
-  }
-}
+};
 
 // ---- count, merge ---------------------------------------------------------
 
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_popcount(const uint64_t *__restrict__ bits, uint64_t nwords,
                unsigned long long *__restrict__ sum)
 {
-  __shared__ uint64_t sh[COV_BLOCK / 64];
+  __shared__ uint64_t sh[TC_BLOCK / 64];
   uint64_t c = 0;
-  for (uint64_t w = vsa_bid() * COV_BLOCK + threadIdx.x; w < nwords;
-       w += vsa_nblocks() * COV_BLOCK)
+  for (uint64_t w = vsa_bid() * TC_BLOCK + threadIdx.x; w < nwords;
+       w += vsa_nblocks() * TC_BLOCK)
   {
     c += (uint64_t) __popcll((unsigned long long) bits[w]);
   }
   uint64_t total;
-  (void) cov_block_exscan(c, sh, total);
+  (void) tc_block_exsum(c, sh, total);
   if (threadIdx.x == 0 && total != 0)
   {
     atomicAdd(sum, (unsigned long long) total);
   }
 }
 
-__global__ void __launch_bounds__(COV_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_cov_merge(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src,
             uint64_t nwords)
 {
-  for (uint64_t w = vsa_bid() * COV_BLOCK + threadIdx.x; w < nwords;
-       w += vsa_nblocks() * COV_BLOCK)
+  for (uint64_t w = vsa_bid() * TC_BLOCK + threadIdx.x; w < nwords;
+       w += vsa_nblocks() * TC_BLOCK)
   {
     const uint64_t s = src[w];
     if ((dst[w] & s) != s)
@@ -631,61 +519,22 @@ k_cov_merge(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src,
 
 // ---- host -----------------------------------------------------------------
 
-struct Timer
+// the tile counts of the derived words of MODE scanned into offsets (nt + 1
+// words); *total = their sum
+template <int MODE>
+int cov_count(const CovRange &r, uint64_t nt, DevBuf &offsets, uint64_t *total)
 {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool ok = false;
-  Timer()
+  DevBuf counts;
+  if (counts.alloc((nt + 1) * 8) != 0 || offsets.alloc((nt + 1) * 8) != 0)
   {
-    ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess &&
-         hipEventRecord(a, nullptr) == hipSuccess;
+    return -100;
   }
-  double stop()
-  {
-    float ms = 0;
-    if (ok && hipEventRecord(b, nullptr) == hipSuccess &&
-        hipEventSynchronize(b) == hipSuccess)
-    {
-      (void) hipEventElapsedTime(&ms, a, b);
-    }
-    return ms;
-  }
-  ~Timer()
-  {
-    if (a != nullptr)
-    {
-      (void) hipEventDestroy(a);
-    }
-    if (b != nullptr)
-    {
-      (void) hipEventDestroy(b);
-    }
-  }
-};
-
-struct Tmp
-{
-  void *p = nullptr;
-  ~Tmp()
-  {
-    vsa_dev_free(p);
-  }
-  uint64_t *u64()
-  {
-    return (uint64_t *) p;
-  }
-};
-
-uint64_t ntiles_of(uint64_t items)
-{
-  return (items + COV_TILE - 1) / COV_TILE;
-}
-
-// grid of a grid-stride kernel over nwords words
-dim3 stride_grid(uint64_t nwords)
-{
-  const uint64_t blocks = (nwords + COV_BLOCK - 1) / COV_BLOCK;
-  return dim3((unsigned int) std::max<uint64_t>(1, std::min<uint64_t>(blocks, 4096)));
+  VSA_HIP(hipMemsetAsync(counts.as<uint64_t>() + nt, 0, 8, nullptr));
+  k_cov_tilecount<MODE><<<vsa_grid(nt), TC_BLOCK, 0, nullptr>>>(
+      r, counts.as<uint64_t>());
+  VSA_HIP(hipGetLastError());
+  return exclusive_sum(counts.as<uint64_t>(), offsets.as<uint64_t>(), nt,
+                       nullptr, total);
 }
 
 int new_table(vsa_coverage *c)
@@ -707,20 +556,18 @@ int collect_separators(vsa_coverage *c)
     return 0;
   }
   CovRange r = {c->bits, c->nwords, 0, c->nbits, 0, c->nwords};
-  const uint64_t nt = ntiles_of(r.nw);
-  Tmp tiles;
-  if (vsa_dev_alloc(&tiles.p, (nt + 1) * 8) != 0)
+  const uint64_t nt = tilesof(r.nw);
+  DevBuf offsets;
+  if (cov_count<0>(r, nt, offsets, &c->nsep) != 0)
   {
     return -100;
   }
-  k_cov_tilecount<0><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tiles.u64());
-  k_cov_scan<<<1, COV_BLOCK, 0, nullptr>>>(tiles.u64(), nt, tiles.u64() + nt);
-  VSA_HIP(hipMemcpy(&c->nsep, tiles.u64() + nt, 8, hipMemcpyDeviceToHost));
   VSA_HIP(vsa_hip_malloc((void **) &c->seppos, (c->nsep + 1) * 8));
   if (c->nsep > 0)
   {
-    k_cov_emit<0><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tiles.u64(),
-                                                           c->seppos, c->nsep);
+    k_cov_emit<0><<<vsa_grid(nt), TC_BLOCK, 0, nullptr>>>(
+        r, offsets.as<uint64_t>(), c->seppos, c->nsep);
+    VSA_HIP(hipGetLastError());
   }
   VSA_HIP(hipStreamSynchronize(nullptr));
   return 0;
@@ -762,11 +609,10 @@ extern "C" int vsa_coverage_open_index(const vsa_index *index,
     return -1;
   }
   *coverage = nullptr;
-  if (vsa_set_device(index->device) != 0)
+  if (enter(index->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   vsa_coverage *c = new vsa_coverage();
   c->device = index->device;
   c->kind = 0;
@@ -774,7 +620,7 @@ extern "C" int vsa_coverage_open_index(const vsa_index *index,
   int rc = new_table(c);
   if (rc == 0 && c->nwords > 0)
   {
-    k_cov_sepbits<<<stride_grid(c->nwords), COV_BLOCK, 0, nullptr>>>(
+    k_cov_sepbits<<<stride_grid(c->nwords, 4096), TC_BLOCK, 0, nullptr>>>(
         index->tis_alloc + VSA_TIS_FRONTPAD, index->n, c->bits, c->nwords);
   }
   if (rc == 0)
@@ -817,11 +663,10 @@ extern "C" int vsa_coverage_open_queries(const vsa_queries *q,
     return -1;
   }
   *coverage = nullptr;
-  if (vsa_set_device(q->device) != 0)
+  if (enter(q->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   vsa_coverage *c = new vsa_coverage();
   c->device = q->device;
   c->kind = 1;
@@ -865,8 +710,8 @@ extern "C" int vsa_coverage_open_queries(const vsa_queries *q,
   {
     if (uniform)
     {
-      k_cov_uniform_seppos<<<vsa_grid((c->nsep + COV_BLOCK - 1) / COV_BLOCK),
-                             COV_BLOCK, 0, nullptr>>>(c->seppos, c->nsep,
+      k_cov_uniform_seppos<<<gridfor(c->nsep),
+                             TC_BLOCK, 0, nullptr>>>(c->seppos, c->nsep,
                                                       q->maxlength);
     }
     else if (hipMemcpy(c->seppos, sp.data(), c->nsep * 8,
@@ -877,8 +722,8 @@ extern "C" int vsa_coverage_open_queries(const vsa_queries *q,
     }
     if (rc == 0)
     {
-      k_cov_setbits<<<vsa_grid((c->nsep + COV_BLOCK - 1) / COV_BLOCK),
-                      COV_BLOCK, 0, nullptr>>>(c->bits, c->nbits, c->seppos,
+      k_cov_setbits<<<gridfor(c->nsep),
+                      TC_BLOCK, 0, nullptr>>>(c->bits, c->nbits, c->seppos,
                                                c->nsep);
     }
   }
@@ -1010,12 +855,14 @@ extern "C" int vsa_coverage_mark(vsa_coverage *c, const vsa_result *r,
   a.nq = c->nq;
   a.seqoffset = c->seqoffset;
   a.uniformlen = c->uniformlen;
-  Timer t;
-  k_cov_mark<<<vsa_grid((r->count + COV_BLOCK - 1) / COV_BLOCK), COV_BLOCK, 0,
-               nullptr>>>(a, r->matches, r->count);
+  Timer t(nullptr);
+  t.start();
+  k_cov_mark<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(a, r->matches,
+                                                          r->count);
   VSA_HIP(hipGetLastError());
-  c->mark_ms = t.stop();
+  t.stop();
   VSA_HIP(hipStreamSynchronize(nullptr));
+  c->mark_ms = t.ms();
   return 0;
 }
 
@@ -1040,7 +887,7 @@ extern "C" int vsa_coverage_merge(vsa_coverage *dst, const vsa_coverage *src)
   }
   if (dst->nwords > 0 && dst != src)
   {
-    k_cov_merge<<<stride_grid(dst->nwords), COV_BLOCK, 0, nullptr>>>(
+    k_cov_merge<<<stride_grid(dst->nwords, 4096), TC_BLOCK, 0, nullptr>>>(
         dst->bits, src->bits, dst->nwords);
     VSA_HIP(hipStreamSynchronize(nullptr));
   }
@@ -1055,11 +902,10 @@ extern "C" int vsa_coverage_getstats(const vsa_coverage *c,
     VSA_ERROR("vsa_coverage_getstats: NULL argument");
     return -1;
   }
-  if (vsa_set_device(c->device) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   memset(stats, 0, sizeof *stats);
   stats->positions = c->nbits - c->nsep;
   stats->separators = c->nsep;
@@ -1067,18 +913,20 @@ extern "C" int vsa_coverage_getstats(const vsa_coverage *c,
   stats->extract_ms = c->extract_ms;
   if (c->nwords > 0)
   {
-    Tmp sum;
-    if (vsa_dev_alloc(&sum.p, 8) != 0)
+    DevBuf sum;
+    if (sum.alloc(8) != 0)
     {
       return -100;
     }
     VSA_HIP(hipMemsetAsync(sum.p, 0, 8, nullptr));
-    Timer t;
-    k_cov_popcount<<<stride_grid(c->nwords), COV_BLOCK, 0, nullptr>>>(
-        c->bits, c->nwords, (unsigned long long *) sum.p);
-    stats->count_ms = t.stop();
+    Timer t(nullptr);
+    t.start();
+    k_cov_popcount<<<stride_grid(c->nwords, 4096), TC_BLOCK, 0, nullptr>>>(
+        c->bits, c->nwords, sum.as<unsigned long long>());
+    t.stop();
     uint64_t set = 0;
     VSA_HIP(hipMemcpy(&set, sum.p, 8, hipMemcpyDeviceToHost));
+    stats->count_ms = t.ms();
     // the separators are set from the start and stay set
     stats->marked = set - c->nsep;
   }
@@ -1154,18 +1002,11 @@ static int cov_nomatch(vsa_coverage *c, uint64_t minlength, uint64_t first,
               (unsigned long) c->nbits);
     return -2;
   }
-  if (vsa_set_device(c->device) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
-  vsa_result *res = new vsa_result();
-  res->device = c->device;
-  res->count = 0;
-  res->matches = nullptr;
-  res->packbits = 0;
-  res->packvals = nullptr;
-  memset(&res->stats, 0, sizeof res->stats);
+  vsa_result *res = newresult(c->device);
   *intervals = res;
   c->extract_ms = 0;
   if (len == 0)
@@ -1179,21 +1020,16 @@ static int cov_nomatch(vsa_coverage *c, uint64_t minlength, uint64_t first,
   r.end = first + len;
   r.w0 = first >> 6;
   r.nw = ((r.end - 1) >> 6) - r.w0 + 1;
-  const uint64_t nt = ntiles_of(r.nw);
-  Tmp tstart, tlast, starts, lasts, tiles2;
+  const uint64_t nt = tilesof(r.nw);
+  DevBuf ostart, olast, starts, lasts, offsets;
   uint64_t nruns = 0, nlast = 0, nout = 0;
-  if (vsa_dev_alloc(&tstart.p, (nt + 1) * 8) != 0 ||
-      vsa_dev_alloc(&tlast.p, (nt + 1) * 8) != 0)
+  Timer t(nullptr);
+  t.start();
+  if (cov_count<1>(r, nt, ostart, &nruns) != 0 ||
+      cov_count<2>(r, nt, olast, &nlast) != 0)
   {
     return -100;
   }
-  Timer t;
-  k_cov_tilecount<1><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tstart.u64());
-  k_cov_scan<<<1, COV_BLOCK, 0, nullptr>>>(tstart.u64(), nt, tstart.u64() + nt);
-  k_cov_tilecount<2><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tlast.u64());
-  k_cov_scan<<<1, COV_BLOCK, 0, nullptr>>>(tlast.u64(), nt, tlast.u64() + nt);
-  VSA_HIP(hipMemcpy(&nruns, tstart.u64() + nt, 8, hipMemcpyDeviceToHost));
-  VSA_HIP(hipMemcpy(&nlast, tlast.u64() + nt, 8, hipMemcpyDeviceToHost));
   if (nruns != nlast)
   {
     VSA_ERROR("vsa_coverage_nomatch: %lu run starts, %lu run ends",
@@ -1202,36 +1038,38 @@ static int cov_nomatch(vsa_coverage *c, uint64_t minlength, uint64_t first,
   }
   if (nruns > 0)
   {
-    const uint64_t nt2 = ntiles_of(nruns);
-    if (vsa_dev_alloc(&starts.p, nruns * 8) != 0 ||
-        vsa_dev_alloc(&lasts.p, nruns * 8) != 0 ||
-        vsa_dev_alloc(&tiles2.p, (nt2 + 1) * 8) != 0)
+    if (starts.alloc(nruns * 8) != 0 || lasts.alloc(nruns * 8) != 0)
     {
       return -100;
     }
-    k_cov_emit<1><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tstart.u64(),
-                                                           starts.u64(), nruns);
-    k_cov_emit<2><<<vsa_grid(nt), COV_BLOCK, 0, nullptr>>>(r, tlast.u64(),
-                                                           lasts.u64(), nruns);
-    k_cov_runcount<<<vsa_grid(nt2), COV_BLOCK, 0, nullptr>>>(
-        starts.u64(), lasts.u64(), nruns, minlength, tiles2.u64());
-    k_cov_scan<<<1, COV_BLOCK, 0, nullptr>>>(tiles2.u64(), nt2,
-                                             tiles2.u64() + nt2);
-    VSA_HIP(hipMemcpy(&nout, tiles2.u64() + nt2, 8, hipMemcpyDeviceToHost));
+    k_cov_emit<1><<<vsa_grid(nt), TC_BLOCK, 0, nullptr>>>(
+        r, ostart.as<uint64_t>(), starts.as<uint64_t>(), nruns);
+    k_cov_emit<2><<<vsa_grid(nt), TC_BLOCK, 0, nullptr>>>(
+        r, olast.as<uint64_t>(), lasts.as<uint64_t>(), nruns);
+    VSA_HIP(hipGetLastError());
+    RunF rf = {starts.as<uint64_t>(), lasts.as<uint64_t>(), minlength,
+               c->seppos, c->nsep, nullptr, 0};
+    if (tc_count<1, 1>(rf, nruns, offsets, &nout) != 0)
+    {
+      return -100;
+    }
     if (nout > 0)
     {
       if (vsa_dev_alloc((void **) &res->matches, nout * sizeof(vsa_match)) != 0)
       {
         return -100;
       }
-      k_cov_runemit<<<vsa_grid(nt2), COV_BLOCK, 0, nullptr>>>(
-          starts.u64(), lasts.u64(), nruns, minlength, tiles2.u64(), c->seppos,
-          c->nsep, res->matches, nout);
+      rf.out = res->matches;
+      rf.capacity = nout;
+      if (tc_emit<1>(rf, nruns, offsets) != 0)
+      {
+        return -100;
+      }
     }
   }
-  VSA_HIP(hipGetLastError());
-  c->extract_ms = t.stop();
+  t.stop();
   VSA_HIP(hipStreamSynchronize(nullptr));
+  c->extract_ms = t.ms();
   res->count = nout;
   res->stats.count = nout;
   res->stats.total_device_ms = c->extract_ms;
@@ -1305,18 +1143,12 @@ extern "C" int vsa_result_from_host(const vsa_match *matches, uint64_t count,
     return -1;
   }
   *result = nullptr;
-  if (vsa_set_device(device) != 0)
+  if (enter(device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
-  vsa_result *r = new vsa_result();
-  r->device = device;
+  vsa_result *r = newresult(device);
   r->count = count;
-  r->matches = nullptr;
-  r->packbits = 0;
-  r->packvals = nullptr;
-  memset(&r->stats, 0, sizeof r->stats);
   r->stats.count = count;
   if (count > 0)
   {

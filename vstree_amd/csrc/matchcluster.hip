@@ -23,7 +23,7 @@
 //            searches that i once per tile of VSA_SELECT_TILE slots, a lane
 //            then searches only between the answers of its tile's ends.
 //            j = i + 1 + (s - off_i).  The slots that are edges go through
-//            the stable compaction of cluster_forest.inc behind the edges so
+//            the stable compaction of tile_compact.inc behind the edges so
 //            far, as (m_i, m_j, value).  At most VSA_MATCHCLUSTER_CHUNK slots
 //            per pass: the memory grows with the edges, not the candidates.
 //   forest, replay, group
@@ -88,14 +88,14 @@ namespace
 // ---- refs -----------------------------------------------------------------------
 
 // positions from `limit` on would not sort by the bits the sort looks at
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_mc_refs(vsa_selrules view, const vsa_match *__restrict__ in, uint64_t n,
           int palindromic, uint64_t base, uint64_t limit,
           vsa_match *__restrict__ recs, uint8_t *__restrict__ flags,
           uint64_t *__restrict__ start, uint64_t *__restrict__ length,
           unsigned long long *__restrict__ bad)
 {
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   bool isbad = false;
   if (i < n)
   {
@@ -151,13 +151,13 @@ __device__ __forceinline__ uint64_t mc_upper(const uint64_t *__restrict__ sstart
 // match of reference i, count[i] = the references behind i that its loop
 // looks at.  One more lane writes count[nrefs] = 0: exclusive_sum scans
 // nrefs + 1 places, so that off[nrefs] is the total it fetches
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_mc_window(vsa_mcrules r, const uint64_t *__restrict__ sstart,
             const uint32_t *__restrict__ sidx,
             const uint64_t *__restrict__ length, uint64_t nrefs,
             uint64_t *__restrict__ send, uint64_t *__restrict__ count)
 {
-  const uint64_t i = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (i > nrefs)
   {
     return;
@@ -201,14 +201,14 @@ __device__ __forceinline__ uint64_t mc_owner(const uint64_t *__restrict__ off,
 
 // first[t] = the reference of the first slot of tile t of this pass;
 // first[ntiles] = that of its last slot.  off[0] = 0 <= every slot.
-__global__ void __launch_bounds__(CL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_mc_tilefirst(const uint64_t *__restrict__ off, uint64_t nrefs, uint64_t c0,
                uint64_t nslots, uint64_t ntiles, uint64_t *__restrict__ first)
 {
-  const uint64_t t = vsa_bid() * CL_BLOCK + threadIdx.x;
+  const uint64_t t = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (t <= ntiles)
   {
-    const uint64_t k = t * CL_TILE < nslots ? t * CL_TILE : nslots - 1;
+    const uint64_t k = t * TC_TILE < nslots ? t * TC_TILE : nslots - 1;
     first[t] = mc_owner(off, 0, nrefs - 1, c0 + k);
   }
 }
@@ -233,7 +233,7 @@ struct PairF
 
   __device__ int cls(uint64_t k, Payload &p) const
   {
-    const uint64_t s = c0 + k, t = k / CL_TILE;
+    const uint64_t s = c0 + k, t = k / TC_TILE;
     const uint64_t i = mc_owner(off, first[t], first[t + 1], s);
     const uint64_t j = i + 1 + (s - off[i]);
     const uint64_t end_i = send[i], start_j = sstart[j];
@@ -243,7 +243,7 @@ struct PairF
     return vsa_mc_classify(&r, end_i, end_i - sstart[i], p.mi, start_j,
                            send[j] - start_j, p.mj, &p.value);
   }
-  __device__ void put(uint64_t rank, uint64_t, const Payload &p) const
+  __device__ void put(int, uint64_t rank, uint64_t, const Payload &p) const
   {
     e1[base + rank] = p.mi;
     e2[base + rank] = p.mj;
@@ -269,35 +269,6 @@ struct EdgeGather
 };
 
 // ---- host -----------------------------------------------------------------------
-
-int enter(const vsa_matchcluster *c)
-{
-  if (vsa_set_device(c->device) != 0)
-  {
-    return -100;
-  }
-  vsa_dev_set_stream(nullptr);
-  return 0;
-}
-
-// p[0 .. have) moves into a block of `cap` elements of `size` bytes
-int grow(void **p, uint64_t have, uint64_t cap, size_t size)
-{
-  DevBuf b;
-  if (b.alloc(cap * size) != 0)
-  {
-    return -100;
-  }
-  if (have > 0)
-  {
-    VSA_HIP(hipMemcpyAsync(b.p, *p, have * size, hipMemcpyDeviceToDevice,
-                           nullptr));
-    VSA_HIP(hipStreamSynchronize(nullptr));
-  }
-  vsa_dev_free(*p);
-  *p = b.release();
-  return 0;
-}
 
 // room for `need` matches; what is there stays
 int reserve(vsa_matchcluster *c, uint64_t need)
@@ -378,7 +349,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
     return -100;
   }
   tsort.start();
-  k_cl_iota<<<gridfor(nrefs), CL_BLOCK, 0, nullptr>>>(idx.as<uint32_t>(),
+  k_tc_iota<<<gridfor(nrefs), TC_BLOCK, 0, nullptr>>>(idx.as<uint32_t>(),
                                                       nrefs);
   VSA_HIP(hipGetLastError());
   const unsigned int endbit = c->sortbits;
@@ -389,7 +360,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
   }));
   tsort.stop();
   twindow.start();
-  k_mc_window<<<gridfor(nrefs + 1), CL_BLOCK, 0, nullptr>>>(
+  k_mc_window<<<gridfor(nrefs + 1), TC_BLOCK, 0, nullptr>>>(
       c->rules, sstart.as<uint64_t>(), sidx.as<uint32_t>(), c->length, nrefs,
       send.as<uint64_t>(), count.as<uint64_t>());
   VSA_HIP(hipGetLastError());
@@ -419,7 +390,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
     {
       return -100;
     }
-    k_mc_tilefirst<<<gridfor(nt + 1), CL_BLOCK, 0, nullptr>>>(
+    k_mc_tilefirst<<<gridfor(nt + 1), TC_BLOCK, 0, nullptr>>>(
         off.as<uint64_t>(), nrefs, c0, ns, nt, first.as<uint64_t>());
     VSA_HIP(hipGetLastError());
     pf.first = first.as<uint64_t>();
@@ -427,7 +398,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
     pf.base = edges.n;
     pf.e1 = pf.e2 = nullptr;
     pf.value = nullptr;
-    if (cl_count(pf, ns, offsets, totals) != 0)
+    if (tc_count<1, VSA_CL_CLASSES>(pf, ns, offsets, totals) != 0)
     {
       return -100;
     }
@@ -449,7 +420,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
       pf.e1 = edges.e1;
       pf.e2 = edges.e2;
       pf.value = edges.value;
-      if (cl_emit(pf, ns, offsets) != 0)
+      if (tc_emit<1>(pf, ns, offsets) != 0)
       {
         return -100;
       }
@@ -488,7 +459,7 @@ int group(vsa_matchcluster *c, const char *who)
   {
     return 0;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -499,17 +470,12 @@ int group(vsa_matchcluster *c, const char *who)
   c->gvalue.resize(ne);
   if (ne > 0)
   {
-    std::vector<uint32_t> hlabel(c->n);
-    for (uint64_t m = 0; m < c->n; m++)
-    {
-      hlabel[m] = c->res.label[m] == VSA_CLUSTER_SINGLET
-                      ? 0xFFFFFFFFu
-                      : (uint32_t) c->res.label[m];
-    }
     DevBuf order, o1, o2, ov;
+    // (the span of the group stage holds cl_group's conversion of the
+    // labels on the host, as that of vsa_cluster_edges does)
     Timer t(nullptr);
     t.start();
-    const int rc = cl_group(c->e1, c->e2, ne, hlabel.data(), c->n, ncl, order,
+    const int rc = cl_group(c->e1, c->e2, ne, c->res.label, c->n, ncl, order,
                             c->edgestart, who);
     if (rc != 0)
     {
@@ -523,7 +489,7 @@ int group(vsa_matchcluster *c, const char *who)
     const EdgeGather g = {c->e1,           c->e2,           c->value,
                           o1.as<uint32_t>(), o2.as<uint32_t>(),
                           ov.as<uint64_t>()};
-    k_cl_gather<EdgeGather><<<gridfor(ne), CL_BLOCK, 0, nullptr>>>(
+    k_cl_gather<EdgeGather><<<gridfor(ne), TC_BLOCK, 0, nullptr>>>(
         g, order.as<uint32_t>(), ne);
     VSA_HIP(hipGetLastError());
     t.stop();
@@ -552,7 +518,7 @@ int gatherrecords(const vsa_matchcluster *c, const uint64_t *who, uint64_t k,
   }
   VSA_HIP(hipMemcpy(order.p, h.data(), k * 4, hipMemcpyHostToDevice));
   const RecGather g = {c->recs, c->flags, out, outflags};
-  k_cl_gather<RecGather><<<gridfor(k), CL_BLOCK, 0, nullptr>>>(
+  k_cl_gather<RecGather><<<gridfor(k), TC_BLOCK, 0, nullptr>>>(
       g, order.as<uint32_t>(), k);
   VSA_HIP(hipGetLastError());
   VSA_HIP(hipStreamSynchronize(nullptr));
@@ -624,11 +590,10 @@ extern "C" int vsa_matchcluster_open(const vsa_sinkparams *layout,
   {
     return rc;
   }
-  if (vsa_set_device(device) != 0)
+  if (enter(device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   vsa_matchcluster *c = new vsa_matchcluster();
   c->device = device;
   c->view = view;
@@ -639,22 +604,12 @@ extern "C" int vsa_matchcluster_open(const vsa_sinkparams *layout,
                                  layout->kind == VSA_SINK_SELF
                                      ? (uint64_t) 0
                                      : layout->querytotallength));
-  if (view.nq > 0)
+  if (upload_queryview(view.nq, &c->view.qstart, &c->view.qlen, &c->d_qstart,
+                       &c->d_qlen, "vsa_matchcluster_open") != 0)
   {
-    if (vsa_hip_malloc((void **) &c->d_qstart, view.nq * 8) != hipSuccess ||
-        vsa_hip_malloc((void **) &c->d_qlen, view.nq * 8) != hipSuccess ||
-        hipMemcpy(c->d_qstart, view.qstart, view.nq * 8,
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_qlen, view.qlen, view.nq * 8,
-                  hipMemcpyHostToDevice) != hipSuccess)
-    {
-      VSA_ERROR("vsa_matchcluster_open: upload of the query Multiseq failed");
-      vsa_matchcluster_close(c);
-      return -100;
-    }
+    vsa_matchcluster_close(c);
+    return -100;
   }
-  c->view.qstart = c->d_qstart;
-  c->view.qlen = c->d_qlen;
   *cluster = c;
   return 0;
 }
@@ -692,7 +647,7 @@ extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
               "covered", (unsigned long) (c->n + r->count));
     return VSA_NOT_COVERED;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -712,7 +667,7 @@ extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
   Timer t(nullptr);
   t.start();
   VSA_HIP(hipMemsetAsync(bad.p, 0, 8, nullptr));
-  k_mc_refs<<<gridfor(r->count), CL_BLOCK, 0, nullptr>>>(
+  k_mc_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
       c->view, r->matches, r->count, palindromic != 0, c->n,
       c->sortbits < 64 ? (uint64_t) 1 << c->sortbits : ~(uint64_t) 0, c->recs,
       c->flags, c->start, c->length, bad.as<unsigned long long>());
@@ -741,7 +696,7 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
     VSA_ERROR("vsa_matchcluster_finish: NULL argument");
     return -1;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -912,7 +867,7 @@ extern "C" int vsa_matchcluster_records(vsa_matchcluster *c,
     return -1;
   }
   *records = nullptr;
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }
@@ -923,18 +878,7 @@ extern "C" int vsa_matchcluster_records(vsa_matchcluster *c,
     *records = res;
     return 0;
   }
-  // (the guard owns the list until it is handed over)
-  struct Guard
-  {
-    vsa_result *r;
-    ~Guard()
-    {
-      if (r != nullptr)
-      {
-        vsa_result_free(r);
-      }
-    }
-  } guard = {res};
+  ResultGuard guard = {res};
   DevBuf oflags;
   if (oflags.alloc(k) != 0 ||
       vsa_dev_alloc((void **) &res->matches, k * sizeof(vsa_match)) != 0 ||
@@ -999,7 +943,7 @@ extern "C" int64_t vsa_matchcluster_format_cluster(vsa_matchcluster *c,
   {
     return rc;
   }
-  if (enter(c) != 0)
+  if (enter(c->device) != 0)
   {
     return -100;
   }

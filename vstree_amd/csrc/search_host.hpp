@@ -1,9 +1,11 @@
 // Host-side helpers shared by the translation units of the search engine
 // (esa_search.hip, selfmum_search.hip, approx_entry.hip, selfmatch_entry.hip,
-// candidate_partition.hip, index_derive.hip, index_build.hip).  Small things
-// are inline here; what instantiates rocPRIM is defined once, in
-// search_common.hip.  (rocprim_run() is a template over its caller's lambda:
-// it instantiates nothing of rocPRIM by itself.)
+// candidate_partition.hip, index_derive.hip, index_build.hip) and of the
+// handles that post-process match lists (coverage.hip, select.hip,
+// cluster.hip, matchcluster.hip).  Small things are inline here; what
+// instantiates rocPRIM is defined once, in search_common.hip.  (rocprim_run()
+// is a template over its caller's lambda: it instantiates nothing of rocPRIM
+// by itself.)
 #ifndef VSA_SEARCH_HOST_HPP
 #define VSA_SEARCH_HOST_HPP
 #include <cstring>
@@ -44,6 +46,25 @@ struct DevBuf
     return r;
   }
 };
+
+// p[0 .. have) moves into a block of `cap` elements of `size` bytes
+inline int grow(void **p, uint64_t have, uint64_t cap, size_t size)
+{
+  DevBuf b;
+  if (b.alloc(cap * size) != 0)
+  {
+    return -100;
+  }
+  if (have > 0)
+  {
+    VSA_HIP(hipMemcpyAsync(b.p, *p, have * size, hipMemcpyDeviceToDevice,
+                           nullptr));
+    VSA_HIP(hipStreamSynchronize(nullptr));
+  }
+  vsa_dev_free(*p);
+  *p = b.release();
+  return 0;
+}
 
 struct Timer
 {
@@ -186,6 +207,55 @@ VSA_HIDDEN int sortpairs(uint64_t *keys_in, uint64_t *keys_out,
                          hipStream_t stream);
 
 VSA_HIDDEN vsa_result *newresult(int device);
+
+// owns a result until it is handed over (r = nullptr)
+struct ResultGuard
+{
+  vsa_result *r;
+  ~ResultGuard()
+  {
+    if (r != nullptr)
+    {
+      vsa_result_free(r);
+    }
+  }
+};
+
+// the first step of an entry point of a handle: its device, and the default
+// stream for what it allocates
+inline int enter(int device)
+{
+  if (vsa_set_device(device) != 0)
+  {
+    return -100;
+  }
+  vsa_dev_set_stream(nullptr);
+  return 0;
+}
+
+// the query Multiseq of a view of select_rules.h: (*qstart)[] and (*qlen)[],
+// nq words each in host memory (or null: none), go into device memory, which
+// the handle owns through *d_qstart and *d_qlen; *qstart and *qlen then point
+// there
+inline int upload_queryview(uint64_t nq, const uint64_t **qstart,
+                            const uint64_t **qlen, uint64_t **d_qstart,
+                            uint64_t **d_qlen, const char *who)
+{
+  const size_t bytes = (size_t) nq * 8;
+  if (*qstart != nullptr && bytes > 0 &&
+      (vsa_hip_malloc((void **) d_qstart, bytes) != hipSuccess ||
+       vsa_hip_malloc((void **) d_qlen, bytes) != hipSuccess ||
+       hipMemcpy(*d_qstart, *qstart, bytes, hipMemcpyHostToDevice) !=
+           hipSuccess ||
+       hipMemcpy(*d_qlen, *qlen, bytes, hipMemcpyHostToDevice) != hipSuccess))
+  {
+    VSA_ERROR("%s: upload of the query Multiseq failed", who);
+    return -100;
+  }
+  *qstart = *d_qstart;
+  *qlen = *d_qlen;
+  return 0;
+}
 
 // offsets[sh] = sum of the fill counts of the cursor regions before sh (one
 // cursor per VSA_CURSOR_STRIDE words); summary = {total, largest count, 0, 0}

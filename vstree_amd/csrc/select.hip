@@ -8,9 +8,9 @@
 //   key      one lane per record: the record, the length and Multiseq start
 //            of its query sequence, T with its line starts and hequot (made
 //            by the host, select_host.c) -> E-value, matchokay, key.  The
-//            survivors are compacted stably: count per tile, exclusive scan
-//            of the tile counts, write in order.  Filters only (N = 0): the
-//            records themselves are appended to the list.  -best: the five
+//            survivors go through the stable compaction of
+//            tile_compact.inc.  Filters only (N = 0): the records
+//            themselves are appended to the list.  -best: the five
 //            key words go into a pool, word by word (structure of arrays),
 //            behind the keys of the selection so far.
 //   select   the N-th smallest key of the pool by an MSD radix select, word
@@ -21,7 +21,7 @@
 //            word: the bits all candidates share are skipped, so a word on
 //            which they are all equal costs ONE pass, however many there are
 //            (millions of full-length matches of equal-length reads tie on
-//            E-value and length).  Then one three-way stable compaction
+//            E-value and length).  Then one three-class compaction
 //            against the threshold: smaller keys are selected, of the equal
 //            ones the first (they are one match), larger ones wait.
 //   sort     the at most N selected keys: five stable rocPRIM radix sorts of
@@ -34,15 +34,11 @@
 // indices inside the selection (at most N < 2^32) are 32 bit.
 #include "search_host.hpp"
 #include "select_internal.h"
+#include "tile_compact.inc"
 
-#define SEL_BLOCK 256
-#define SEL_IPT 4 // records per thread of a tile
-#define SEL_TILE (SEL_BLOCK * SEL_IPT)
 #define SEL_DIGITBITS 11
 #define SEL_BINS (1 << SEL_DIGITBITS)
 #define SEL_W VSA_SELECT_KEYWORDS
-
-static_assert(SEL_TILE == VSA_SELECT_TILE, "the header names the tile");
 
 struct vsa_select
 {
@@ -70,149 +66,6 @@ struct vsa_select
 
 namespace
 {
-
-// exclusive sum of one value per thread of a workgroup; sh: SEL_BLOCK / 64
-// words of LDS
-__device__ __forceinline__ uint32_t sel_block_exscan(uint32_t v, uint32_t *sh,
-                                                     uint32_t &total)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t o = __shfl_up(incl, d);
-    if (lane >= (uint32_t) d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < SEL_BLOCK / 64; w++)
-  {
-    const uint32_t x = sh[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  total = all;
-  return before + incl - v;
-}
-
-// ---- stable compaction into classes ---------------------------------------
-// F::cls(i, payload) names the class of item i (or -1); the items of the
-// classes below NE are written in order through F::put(class, rank, i,
-// payload), the classes from NE on are only counted.
-
-template <int NE, int NC, class F>
-__global__ void __launch_bounds__(SEL_BLOCK)
-k_sel_count(F f, uint64_t n, uint64_t *__restrict__ tilecount, uint64_t nt,
-            unsigned long long *__restrict__ totals)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * SEL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[SEL_BLOCK / 64];
-  const uint64_t k0 = tile * SEL_TILE + (uint64_t) threadIdx.x * SEL_IPT;
-  uint32_t c[NC];
-#pragma unroll
-  for (int q = 0; q < NC; q++)
-  {
-    c[q] = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < SEL_IPT; j++)
-  {
-    if (k0 + j < n)
-    {
-      typename F::Payload p;
-      const int cls = f.cls(k0 + j, p);
-#pragma unroll
-      for (int q = 0; q < NC; q++)
-      {
-        c[q] += cls == q ? 1u : 0u;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NC; q++)
-  {
-    uint32_t total;
-    (void) sel_block_exscan(c[q], sh, total);
-    if (threadIdx.x == 0)
-    {
-      if (q < NE)
-      {
-        tilecount[(uint64_t) q * (nt + 1) + tile] = total;
-      }
-      else if (total != 0)
-      {
-        atomicAdd(&totals[q], (unsigned long long) total);
-      }
-    }
-  }
-}
-
-template <int NE, class F>
-__global__ void __launch_bounds__(SEL_BLOCK)
-k_sel_emit(F f, uint64_t n, const uint64_t *__restrict__ tileoffset,
-           uint64_t nt)
-{
-  const uint64_t tile = vsa_bid();
-  if (tile * SEL_TILE >= n)
-  {
-    return;
-  }
-  __shared__ uint32_t sh[SEL_BLOCK / 64];
-  const uint64_t k0 = tile * SEL_TILE + (uint64_t) threadIdx.x * SEL_IPT;
-  typename F::Payload p[SEL_IPT];
-  int cls[SEL_IPT];
-  uint32_t c[NE];
-  uint64_t o[NE];
-#pragma unroll
-  for (int q = 0; q < NE; q++)
-  {
-    c[q] = 0;
-  }
-#pragma unroll
-  for (int j = 0; j < SEL_IPT; j++)
-  {
-    cls[j] = k0 + j < n ? f.cls(k0 + j, p[j]) : -1;
-#pragma unroll
-    for (int q = 0; q < NE; q++)
-    {
-      c[q] += cls[j] == q ? 1u : 0u;
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NE; q++)
-  {
-    uint32_t total;
-    const uint32_t ex = sel_block_exscan(c[q], sh, total);
-    o[q] = tileoffset[(uint64_t) q * (nt + 1) + tile] + ex;
-  }
-#pragma unroll
-  for (int j = 0; j < SEL_IPT; j++)
-  {
-#pragma unroll
-    for (int q = 0; q < NE; q++)
-    {
-      if (cls[j] == q)
-      {
-        f.put(q, o[q], k0 + j, p[j]);
-        o[q]++;
-      }
-    }
-  }
-}
 
 struct KeyPayload
 {
@@ -277,10 +130,6 @@ struct KeyF
       lflags[base + rank] = (uint8_t) (palindromic != 0);
     }
   }
-};
-
-struct NoPayload
-{
 };
 
 // entries of the pool (those of `list`, or all) against the threshold:
@@ -383,22 +232,22 @@ struct HistArgs
 // hist[SEL_BINS] += digits of the candidates; andor[0] &= / andor[1] |= their
 // word.  The counts of a workgroup are gathered in LDS; a wavefront whose
 // candidates all show the same digit (the tie groups) adds once.
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_hist(HistArgs a, unsigned long long *__restrict__ hist,
            unsigned long long *__restrict__ andor)
 {
   __shared__ uint32_t lh[SEL_BINS];
-  for (uint32_t b = threadIdx.x; b < SEL_BINS; b += SEL_BLOCK)
+  for (uint32_t b = threadIdx.x; b < SEL_BINS; b += TC_BLOCK)
   {
     lh[b] = 0;
   }
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
   uint64_t wand = ~0ull, wor = 0;
-  const uint64_t stride = vsa_nblocks() * SEL_BLOCK;
+  const uint64_t stride = vsa_nblocks() * TC_BLOCK;
   // whole wavefronts run the same number of rounds
   const uint64_t rounds = (a.n + stride - 1) / stride;
-  uint64_t i = vsa_bid() * SEL_BLOCK + threadIdx.x;
+  uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   for (uint64_t r = 0; r < rounds; r++, i += stride)
   {
     bool cand = i < a.n;
@@ -458,7 +307,7 @@ k_sel_hist(HistArgs a, unsigned long long *__restrict__ hist,
     atomicOr(&andor[1], (unsigned long long) wor);
   }
   __syncthreads();
-  for (uint32_t b = threadIdx.x; b < SEL_BINS; b += SEL_BLOCK)
+  for (uint32_t b = threadIdx.x; b < SEL_BINS; b += TC_BLOCK)
   {
     if (lh[b] != 0)
     {
@@ -469,34 +318,14 @@ k_sel_hist(HistArgs a, unsigned long long *__restrict__ hist,
 
 // ---- small kernels -----------------------------------------------------------
 
-__global__ void __launch_bounds__(SEL_BLOCK)
-k_sel_iota32(uint32_t *__restrict__ out, uint64_t n)
-{
-  const uint64_t i = vsa_bid() * SEL_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    out[i] = (uint32_t) i;
-  }
-}
-
-__global__ void __launch_bounds__(SEL_BLOCK)
-k_sel_iota64(uint64_t *__restrict__ out, uint64_t n)
-{
-  const uint64_t i = vsa_bid() * SEL_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    out[i] = i;
-  }
-}
-
 // out[j] = word of the selected entry perm[j]
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_gatherword(const uint64_t *__restrict__ word,
                  const uint64_t *__restrict__ selected,
                  const uint32_t *__restrict__ perm, uint64_t n,
                  uint64_t *__restrict__ out)
 {
-  const uint64_t j = vsa_bid() * SEL_BLOCK + threadIdx.x;
+  const uint64_t j = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (j < n)
   {
     out[j] = word[selected[perm[j]]];
@@ -505,7 +334,7 @@ k_sel_gatherword(const uint64_t *__restrict__ word,
 
 // the new selection from the pool: entry e < nold is entry e of the old
 // selection, another one the record src[e - nold] of the list
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_commit(const uint64_t *__restrict__ keys, uint64_t stride,
              const uint64_t *__restrict__ selected, uint64_t n,
              const vsa_match *__restrict__ oldrecs, uint64_t nold,
@@ -513,7 +342,7 @@ k_sel_commit(const uint64_t *__restrict__ keys, uint64_t stride,
              const uint64_t *__restrict__ src, uint64_t *__restrict__ newkeys,
              vsa_match *__restrict__ newrecs)
 {
-  const uint64_t j = vsa_bid() * SEL_BLOCK + threadIdx.x;
+  const uint64_t j = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (j < n)
   {
     const uint64_t e = selected[j];
@@ -526,11 +355,11 @@ k_sel_commit(const uint64_t *__restrict__ keys, uint64_t stride,
   }
 }
 
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_flags(const uint64_t *__restrict__ word4, uint64_t n,
             uint8_t *__restrict__ flags)
 {
-  const uint64_t j = vsa_bid() * SEL_BLOCK + threadIdx.x;
+  const uint64_t j = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (j < n)
   {
     flags[j] = (uint8_t) (word4[j] & 1u);
@@ -538,13 +367,13 @@ k_sel_flags(const uint64_t *__restrict__ word4, uint64_t n,
 }
 
 // the largest querystart field (the distance of approximate matches)
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_maxdistance(const vsa_match *__restrict__ matches, uint64_t n,
                   unsigned long long *__restrict__ out)
 {
   uint64_t mx = 0;
-  for (uint64_t i = vsa_bid() * SEL_BLOCK + threadIdx.x; i < n;
-       i += vsa_nblocks() * SEL_BLOCK)
+  for (uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x; i < n;
+       i += vsa_nblocks() * TC_BLOCK)
   {
     const uint64_t d = matches[i].querystart;
     mx = d > mx ? d : mx;
@@ -563,12 +392,12 @@ k_sel_maxdistance(const vsa_match *__restrict__ matches, uint64_t n,
   }
 }
 
-__global__ void __launch_bounds__(SEL_BLOCK)
+__global__ void __launch_bounds__(TC_BLOCK)
 k_sel_evalues(vsa_selrules r, const vsa_match *__restrict__ matches,
               uint64_t n, int palindromic, double *__restrict__ out,
               unsigned long long *__restrict__ bad)
 {
-  const uint64_t i = vsa_bid() * SEL_BLOCK + threadIdx.x;
+  const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (i < n)
   {
     const vsa_match m = matches[i];
@@ -583,65 +412,6 @@ k_sel_evalues(vsa_selrules r, const vsa_match *__restrict__ matches,
 }
 
 // ---- host ----------------------------------------------------------------------
-
-dim3 stride_grid(uint64_t n)
-{
-  const uint64_t blocks = (n + SEL_BLOCK - 1) / SEL_BLOCK;
-  return dim3((unsigned int) std::max<uint64_t>(1, std::min<uint64_t>(blocks, 2048)));
-}
-
-uint64_t tilesof(uint64_t n)
-{
-  return (n + SEL_TILE - 1) / SEL_TILE;
-}
-
-// the tile counts of the classes below NE scanned into offsets (NE arrays of
-// nt + 1 words), totals[q] = items of class q
-template <int NE, int NC, class F>
-int sel_count(const F &f, uint64_t n, DevBuf &offsets, uint64_t *totals)
-{
-  const uint64_t nt = tilesof(n);
-  DevBuf counts, tot;
-  if (counts.alloc(NE * (nt + 1) * 8) != 0 ||
-      offsets.alloc(NE * (nt + 1) * 8) != 0 || tot.alloc(NC * 8) != 0)
-  {
-    return -100;
-  }
-  VSA_HIP(hipMemsetAsync(counts.p, 0, NE * (nt + 1) * 8, nullptr));
-  VSA_HIP(hipMemsetAsync(tot.p, 0, NC * 8, nullptr));
-  k_sel_count<NE, NC, F><<<vsa_grid(nt), SEL_BLOCK, 0, nullptr>>>(
-      f, n, counts.as<uint64_t>(), nt, tot.as<unsigned long long>());
-  VSA_HIP(hipGetLastError());
-  for (int q = 0; q < NE; q++)
-  {
-    if (exclusive_sum(counts.as<uint64_t>() + q * (nt + 1),
-                      offsets.as<uint64_t>() + q * (nt + 1), nt, nullptr,
-                      &totals[q]) != 0)
-    {
-      return -100;
-    }
-  }
-  if (NC > NE)
-  {
-    uint64_t t[NC];
-    VSA_HIP(hipMemcpy(t, tot.p, NC * 8, hipMemcpyDeviceToHost));
-    for (int q = NE; q < NC; q++)
-    {
-      totals[q] = t[q];
-    }
-  }
-  return 0;
-}
-
-template <int NE, class F>
-int sel_emit(const F &f, uint64_t n, DevBuf &offsets)
-{
-  const uint64_t nt = tilesof(n);
-  k_sel_emit<NE, F><<<vsa_grid(nt), SEL_BLOCK, 0, nullptr>>>(
-      f, n, offsets.as<uint64_t>(), nt);
-  VSA_HIP(hipGetLastError());
-  return 0;
-}
 
 void free_tables(vsa_select *s)
 {
@@ -694,7 +464,7 @@ int ensure_tables(vsa_select *s, const vsa_result *r)
     return -100;
   }
   VSA_HIP(hipMemsetAsync(mx.p, 0, 8, nullptr));
-  k_sel_maxdistance<<<stride_grid(r->count), SEL_BLOCK, 0, nullptr>>>(
+  k_sel_maxdistance<<<stride_grid(r->count, 2048), TC_BLOCK, 0, nullptr>>>(
       r->matches, r->count, mx.as<unsigned long long>());
   VSA_HIP(hipGetLastError());
   VSA_HIP(hipMemcpy(&maxd, mx.p, 8, hipMemcpyDeviceToHost));
@@ -768,7 +538,7 @@ int sel_threshold(const uint64_t *keys, uint64_t stride, const uint64_t *list,
       h[SEL_BINS] = ~0ull;
       VSA_HIP(hipMemcpyAsync(dev.p, h.data(), (SEL_BINS + 2) * 8,
                              hipMemcpyHostToDevice, nullptr));
-      k_sel_hist<<<stride_grid(n), SEL_BLOCK, 0, nullptr>>>(
+      k_sel_hist<<<stride_grid(n, 2048), TC_BLOCK, 0, nullptr>>>(
           a, dev.as<unsigned long long>(),
           dev.as<unsigned long long>() + SEL_BINS);
       VSA_HIP(hipGetLastError());
@@ -818,12 +588,12 @@ int sel_sortunique(const uint64_t *keys, uint64_t stride,
   {
     return -100;
   }
-  k_sel_iota32<<<gridfor(n), SEL_BLOCK, 0, nullptr>>>(perm.as<uint32_t>(), n);
+  k_tc_iota<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(perm.as<uint32_t>(), n);
   VSA_HIP(hipGetLastError());
   uint32_t *p = perm.as<uint32_t>(), *p2 = perm2.as<uint32_t>();
   for (int w = SEL_W - 1; w >= 0; w--)
   {
-    k_sel_gatherword<<<gridfor(n), SEL_BLOCK, 0, nullptr>>>(
+    k_sel_gatherword<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(
         keys + (uint64_t) w * stride, selected, p, n, kw.as<uint64_t>());
     VSA_HIP(hipGetLastError());
     if (sortpairs(kw.as<uint64_t>(), kw2.as<uint64_t>(), p, p2, n, nullptr) !=
@@ -840,8 +610,8 @@ int sel_sortunique(const uint64_t *keys, uint64_t stride,
   u.perm = p;
   u.out = out;
   uint64_t totals[2];
-  if (sel_count<1, 2>(u, n, offsets, totals) != 0 ||
-      sel_emit<1>(u, n, offsets) != 0)
+  if (tc_count<1, 2>(u, n, offsets, totals) != 0 ||
+      tc_emit<1>(u, n, offsets) != 0)
   {
     return -100;
   }
@@ -871,7 +641,7 @@ int sel_best(vsa_select *s, const vsa_result *r, KeyF &kf, DevBuf &offsets,
   kf.stride = P;
   kf.base = nold;
   kf.src = src.as<uint64_t>();
-  if (sel_emit<1>(kf, r->count, offsets) != 0)
+  if (tc_emit<1>(kf, r->count, offsets) != 0)
   {
     return -100;
   }
@@ -892,7 +662,7 @@ int sel_best(vsa_select *s, const vsa_result *r, KeyF &kf, DevBuf &offsets,
       // all of them
       if (list == nullptr)
       {
-        k_sel_iota64<<<gridfor(c), SEL_BLOCK, 0, nullptr>>>(
+        k_tc_iota<<<gridfor(c), TC_BLOCK, 0, nullptr>>>(
             sel.as<uint64_t>() + nselected, c);
         VSA_HIP(hipGetLastError());
       }
@@ -919,7 +689,7 @@ int sel_best(vsa_select *s, const vsa_result *r, KeyF &kf, DevBuf &offsets,
       cf.selected = nullptr;
       cf.waiting = nullptr;
       cf.nless = 0;
-      if (sel_count<3, 3>(cf, c, coffsets, totals) != 0)
+      if (tc_count<3, 3>(cf, c, coffsets, totals) != 0)
       {
         return -100;
       }
@@ -937,7 +707,7 @@ int sel_best(vsa_select *s, const vsa_result *r, KeyF &kf, DevBuf &offsets,
       cf.selected = sel.as<uint64_t>() + nselected;
       cf.nless = totals[0];
       cf.waiting = nextwaiting.as<uint64_t>();
-      if (sel_emit<3>(cf, c, coffsets) != 0)
+      if (tc_emit<3>(cf, c, coffsets) != 0)
       {
         return -100;
       }
@@ -967,7 +737,7 @@ int sel_best(vsa_select *s, const vsa_result *r, KeyF &kf, DevBuf &offsets,
   }
   if (distinct > 0)
   {
-    k_sel_commit<<<gridfor(distinct), SEL_BLOCK, 0, nullptr>>>(
+    k_sel_commit<<<gridfor(distinct), TC_BLOCK, 0, nullptr>>>(
         pool.as<uint64_t>(), P, sel.as<uint64_t>(), distinct, s->srecs, nold,
         r->matches, src.as<uint64_t>(), newkeys.as<uint64_t>(),
         newrecs.as<vsa_match>());
@@ -1063,11 +833,10 @@ extern "C" int vsa_select_open(const vsa_sinkparams *layout,
       plen = qlen.data();
     }
   }
-  if (vsa_set_device(device) != 0)
+  if (enter(device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   vsa_select *s = new vsa_select();
   s->device = device;
   s->selfpalindromic = layout->selfpalindromic != 0;
@@ -1081,19 +850,10 @@ extern "C" int vsa_select_open(const vsa_sinkparams *layout,
     delete s;
     return rc;
   }
-  if (s->ctx.qstart != nullptr)
-  {
-    if (vsa_hip_malloc((void **) &s->d_qstart, nq * 8) != hipSuccess ||
-        vsa_hip_malloc((void **) &s->d_qlen, nq * 8) != hipSuccess ||
-        hipMemcpy(s->d_qstart, s->ctx.qstart, nq * 8, hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMemcpy(s->d_qlen, s->ctx.qlen, nq * 8, hipMemcpyHostToDevice) !=
-            hipSuccess)
-    {
-      VSA_ERROR("vsa_select_open: upload of the query Multiseq failed");
-      rc = -100;
-    }
-  }
+  // (upload_tables makes drules of ctx.rules and points it to the copies)
+  const uint64_t *hstart = s->ctx.rules.qstart, *hlen = s->ctx.rules.qlen;
+  rc = upload_queryview(nq, &hstart, &hlen, &s->d_qstart, &s->d_qlen,
+                        "vsa_select_open");
   if (rc == 0)
   {
     rc = upload_tables(s);
@@ -1120,11 +880,10 @@ extern "C" int vsa_select_add(vsa_select *s, const vsa_result *r,
   {
     return rc;
   }
-  if (vsa_set_device(s->device) != 0)
+  if (enter(s->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   s->lastpasses = 0;
   if (r->count == 0)
   {
@@ -1148,7 +907,7 @@ extern "C" int vsa_select_add(vsa_select *s, const vsa_result *r,
   kf.lflags = nullptr;
   DevBuf offsets;
   uint64_t totals[4];
-  if (sel_count<1, 4>(kf, r->count, offsets, totals) != 0)
+  if (tc_count<1, 4>(kf, r->count, offsets, totals) != 0)
   {
     return -100;
   }
@@ -1187,7 +946,7 @@ extern "C" int vsa_select_add(vsa_select *s, const vsa_result *r,
     kf.lrecs = recs.as<vsa_match>();
     kf.lflags = flags.as<uint8_t>();
     kf.base = s->nlist;
-    if (sel_emit<1>(kf, r->count, offsets) != 0)
+    if (tc_emit<1>(kf, r->count, offsets) != 0)
     {
       return -100;
     }
@@ -1212,11 +971,10 @@ extern "C" int vsa_select_finish(vsa_select *s, vsa_result **selected)
     return -1;
   }
   *selected = nullptr;
-  if (vsa_set_device(s->device) != 0)
+  if (enter(s->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   const bool best = s->ctx.params.bestnumber > 0;
   const uint64_t n = best ? s->nsel : s->nlist;
   const vsa_match *recs = best ? s->srecs : s->lrecs;
@@ -1231,7 +989,7 @@ extern "C" int vsa_select_finish(vsa_select *s, vsa_result **selected)
       {
         return -100;
       }
-      k_sel_flags<<<gridfor(n), SEL_BLOCK, 0, nullptr>>>(
+      k_sel_flags<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(
           s->skeys + (uint64_t) (SEL_W - 1) * n, n, flags.as<uint8_t>());
       VSA_HIP(hipGetLastError());
     }
@@ -1328,11 +1086,10 @@ extern "C" int vsa_select_evalues(vsa_select *s, const vsa_result *r,
   {
     return rc;
   }
-  if (vsa_set_device(s->device) != 0)
+  if (enter(s->device) != 0)
   {
     return -100;
   }
-  vsa_dev_set_stream(nullptr);
   const uint64_t n = std::min(capacity, r->count);
   if (n == 0)
   {
@@ -1349,7 +1106,7 @@ extern "C" int vsa_select_evalues(vsa_select *s, const vsa_result *r,
     return -100;
   }
   VSA_HIP(hipMemsetAsync(bad.p, 0, 8, nullptr));
-  k_sel_evalues<<<gridfor(n), SEL_BLOCK, 0, nullptr>>>(
+  k_sel_evalues<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(
       s->drules, r->matches, n, palindromic != 0, out.as<double>(),
       bad.as<unsigned long long>());
   VSA_HIP(hipGetLastError());
