@@ -1364,6 +1364,173 @@ int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
                                      const uint64_t *value, uint64_t nedges,
                                      char *buffer, uint64_t capacity);
 
+/* ---- chaining: vmatch -pp chain [global [gc|ov] | local [K | Kb | Kp]]
+   [wf F] [maxgap W] [withinborders] [silent] (Vmatch/parsepp.c:95-109,
+   Vmatch/chncallparse.c:224-400, Vmatch/initpost.c:307-318,
+   Vmatch/chainvm.c:29-500, kurtz/matsort.c:316-367,
+   kurtz-basic/chain2dim.c:251-1915) on match lists that stay in HBM ---------
+
+   The records of all lists added are the match buffer; record number m is
+   the index over all add calls.  What a record is (lengths, positions,
+   distance) is the view vsa_select derives; seqnum1 is the sequence of the
+   index position1 lies in, seqnum2 that of position2 (self lists) or the
+   query number.
+
+   Problems.  With withinborders, unless every record lies in one (seqnum1,
+   seqnum2) pair, the records are grouped: a stable counting sort by seqnum1,
+   then the reference's quicksort by seqnum2 inside every run of one seqnum1
+   (not stable for runs of more than 10 records), and every run of one pair is
+   a chaining problem of its own.  Otherwise the whole list is one problem.
+   Inside a problem the records are sorted by position2 (stable); the
+   fragment numbers are the places in that order.
+
+   Fragments.  Dimension 0 is [position1, position1 + length1 - 1], dimension
+   1 is [position2, position2 + length2 - 1]; weight = (int64) (weightfactor *
+   (double) |score|).  Every kind but plain global has initialgap = position1
+   + position2 and terminalgap = (largest end0 of the problem - end0) +
+   (largest end1 - end1).
+
+   Scores.  The predecessor of fragment i is, among the fragments j with
+   end1[j] < start1[i] and end0[j] <= start0[i] - 1, the one of greatest
+   priority (score, minus terminalgap unless plain global), ties to the
+   smallest (end1[j], j); if maxgapwidth != 0 and the gap to it is wider in
+   either dimension, i has no predecessor.  global: score = score[j] +
+   weight, or weight.  global gc: score[j] + weight - gap with gap =
+   (start0 - end0[j]) + (start1 - end1[j]), or weight - initialgap.  local:
+   as gc if score[j] > gap, else weight and a new chain.  global ov: every
+   colinear j < i (all four coordinates strictly smaller) within maxgap is a
+   candidate with score[j] - overlap, continued with + weight if positive and
+   else replaced by weight and a new chain; the first maximum wins.
+
+   Retrieval.  Fragment i ends a chain if it is the last one, or fragment
+   i + 1 does not have it as predecessor, or has a smaller score.  The
+   threshold: global -- the greatest score; gc, ov, local -- the greatest end
+   score of the chain ends (gc: score - terminalgap); local K -- K; local Kb
+   -- the K-th largest distinct score of the chain ends, compared as unsigned
+   numbers; local Kp -- (int64) ((double) max * (1.0 - (double) K / 100.0)).
+   Every chain end not below the threshold gives a chain, in the order of the
+   fragments; the local kinds only one per first fragment, the first end that
+   has the greatest score of its class.  A problem of one fragment gives that
+   fragment as a chain whatever the threshold.  Chains are numbered from 0
+   within every problem. */
+#define VSA_CHAIN_GLOBAL 0          /* global                                */
+#define VSA_CHAIN_GLOBAL_GC 1       /* global gc                             */
+#define VSA_CHAIN_GLOBAL_OV 2       /* global ov                             */
+#define VSA_CHAIN_LOCAL_MAX 3       /* local                                 */
+#define VSA_CHAIN_LOCAL_THRESHOLD 4 /* local K                               */
+#define VSA_CHAIN_LOCAL_BEST 5      /* local Kb, K >= 1                      */
+#define VSA_CHAIN_LOCAL_PERCENT 6   /* local Kp                              */
+/* the most fragments of one problem on the device.  It bounds the
+   QUADRATIC WORK of the one workgroup that chains such a problem (every
+   fragment looks at all earlier ones), not memory; vsa_chain_host takes
+   problems of any size. */
+#define VSA_CHAIN_MAXGROUP ((uint64_t) 1 << 15)
+#define VSA_CHAIN_NONE 0xFFFFFFFFu
+#define VSA_CHAIN_SILENT 1 /* format flag: headers only (silent)           */
+
+typedef struct
+{
+  int kind;
+  int64_t value;        /* K of local K, Kb, Kp                             */
+  uint64_t maxgapwidth; /* maxgap W; 0: none                                */
+  double weightfactor;  /* wf F; the default is 1.0                         */
+  int withinborders;
+  int thread; /* thread ...: not covered                                    */
+} vsa_chainparams;
+
+typedef struct
+{
+  uint64_t matches;  /* records of all lists                                */
+  uint64_t problems; /* chaining problems, of which ...                     */
+  uint64_t single;   /* ... with 1 fragment (the boundary case)             */
+  uint64_t small;    /* ... with 2 .. 8: one lane each                      */
+  uint64_t wave;     /* ... with 9 .. 64: one wavefront each                */
+  uint64_t group;    /* ... with more: one workgroup each                   */
+  uint64_t largest;  /* fragments of the largest problem                    */
+  uint64_t tieruns;  /* runs of records that tie on (seqnum1, seqnum2,
+                        position2), or on position2 in one problem          */
+  uint64_t replayed; /* records in runs of one seqnum1 of more than 10
+                        records that hold such a tie: the only ones the
+                        quicksort may leave in another than the stable order
+                        (the device sends these through the host)           */
+  uint64_t chains;   /* after finish: chains, ...                           */
+  uint64_t chained;  /* ... and the records in them                         */
+} vsa_chainstats;
+
+typedef struct vsa_chain vsa_chain;
+/* the stages vsa_chain_times reports, in this order */
+#define VSA_CHAIN_STAGES 5 /* view sort replay score retrieve              */
+
+/*
+  layout: what the sink of these lists is opened with; markpos, querystart
+  and querylength need not outlive the call.  VSA_NOT_COVERED: thread; the
+  selfpalindromic layout.  -2: an unknown kind, a weight factor that is not
+  positive, local Kb with K < 1.
+*/
+int vsa_chain_open(const vsa_sinkparams *layout,
+                   const vsa_chainparams *params, int device,
+                   vsa_chain **chain);
+/* one more list (vmatch -d -p: two calls); the records are copied.
+   VSA_NOT_COVERED, state untouched: a packed-pair result; a palindromic list
+   under a self layout; 2^32 - 1 records or more.  -2, state untouched: a
+   record that does not fit the layout. */
+int vsa_chain_add(vsa_chain *chain, const vsa_result *result,
+                  int palindromic);
+/* chains the records added so far (more may be added, and finish called
+   again).  VSA_NOT_COVERED: a problem of more than VSA_CHAIN_MAXGROUP
+   fragments -- the handle is then as the last finish left it: its chains
+   stay, the lists added since then are dropped, and smaller ones may
+   follow.  VSA_CHAIN_SMALLMAX and VSA_CHAIN_WAVEMAX in the environment move
+   the sizes up to which a problem gets one lane (default 8) and one
+   wavefront (default 64, the most): the A/B of scripts/chain_probe.py. */
+int vsa_chain_finish(vsa_chain *chain);
+/* the counts of the last finish (all 0 before the first) */
+int vsa_chain_getstats(const vsa_chain *chain, vsa_chainstats *stats);
+/* after finish: chain c belongs to problem problem[c] (problems are numbered
+   in the order of (seqnum1, seqnum2)), is chain number[c] of it, has the
+   score score[c] and the members members[start[c] .. start[c + 1]).
+   stats.chains entries each, start one more; any may be NULL */
+int vsa_chain_chains(const vsa_chain *chain, uint64_t *problem,
+                     uint64_t *number, int64_t *score, uint64_t *start);
+/* after finish: the record numbers of the members of all chains,
+   stats.chained entries */
+int vsa_chain_members(vsa_chain *chain, uint64_t *members);
+/* after finish: the members of all chains, in that order, as a result in
+   HBM that the sink prints like any list; palindromic[t] (stats.chained
+   entries, may be NULL) = the flag of the list record t came from */
+int vsa_chain_records(vsa_chain *chain, vsa_result **records,
+                      uint8_t *palindromic);
+/* after finish: what vmatch prints behind its "# args=" line
+   (outvmatchchain, chainvm.c:106-161): "# chain N: length L score S" and,
+   unless flags has VSA_CHAIN_SILENT, the sink's line of every member, all
+   with the direction of the sink.  Returns the bytes written, -3 if the
+   buffer is too small */
+int64_t vsa_chain_format(vsa_chain *chain, vsa_sink *sink, int flags,
+                         char *buffer, uint64_t capacity);
+/* HIP-event times of all calls so far in ms, VSA_CHAIN_STAGES of them */
+int vsa_chain_times(const vsa_chain *chain, double *ms);
+void vsa_chain_close(vsa_chain *chain);
+
+/*
+  The same on a list in host memory, no GPU involved, problems of any size:
+  the reference's sweep with a sorted array as its dictionary.  Outputs that
+  are NULL are left out; problem, number and score hold chaincapacity
+  entries, start one more, members membercapacity: stats is written and -3
+  returned if there are more.
+*/
+int vsa_chain_host(const vsa_sinkparams *layout,
+                   const vsa_chainparams *params, const vsa_match *matches,
+                   const uint8_t *palindromic, uint64_t n,
+                   vsa_chainstats *stats, uint64_t *problem, uint64_t *number,
+                   int64_t *score, uint64_t *start, uint64_t chaincapacity,
+                   uint64_t *members, uint64_t membercapacity);
+/* the text of vsa_chain_format from arrays in host memory: records[t] = the
+   record of member t of all chains */
+int64_t vsa_chain_format_host(vsa_sink *sink, int flags, uint64_t nchains,
+                              const uint64_t *number, const int64_t *score,
+                              const uint64_t *start, const vsa_match *records,
+                              char *buffer, uint64_t capacity);
+
 /* the field widths of the sink's lines (length, position1, position2,
    seqnum1, seqnum2) instead of those of the layout: what the reference's
    post-processing prints its matches with (ASSIGNDEFAULTDIGITS,

@@ -173,6 +173,21 @@ class MatchClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ChainParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("value", C.c_int64),
+                ("maxgapwidth", C.c_uint64), ("weightfactor", C.c_double),
+                ("withinborders", C.c_int), ("thread", C.c_int)]
+
+
+class ChainStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in
+                ("matches", "problems", "single", "small", "wave", "group",
+                 "largest", "tieruns", "replayed", "chains", "chained")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 PROCESSMATCH = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
 
 
@@ -378,6 +393,22 @@ def _load():
         "vsa_matchcluster_format_host": (C.c_int64, [V, I, V, V, U64, V, V,
                                                      V, U64, V, U64]),
         "vsa_sink_setdigits": (I, [V, I, I, I, I, I]),
+        "vsa_chain_open": (I, [C.POINTER(SinkParams), C.POINTER(ChainParams),
+                               I, PP]),
+        "vsa_chain_add": (I, [V, V, I]),
+        "vsa_chain_finish": (I, [V]),
+        "vsa_chain_getstats": (I, [V, C.POINTER(ChainStats)]),
+        "vsa_chain_chains": (I, [V, V, V, V, V]),
+        "vsa_chain_members": (I, [V, V]),
+        "vsa_chain_records": (I, [V, PP, V]),
+        "vsa_chain_format": (C.c_int64, [V, V, I, V, U64]),
+        "vsa_chain_times": (I, [V, V]),
+        "vsa_chain_close": (None, [V]),
+        "vsa_chain_host": (I, [C.POINTER(SinkParams), C.POINTER(ChainParams),
+                               V, V, U64, C.POINTER(ChainStats), V, V, V, V,
+                               U64, V, U64]),
+        "vsa_chain_format_host": (C.c_int64, [V, I, U64, V, V, V, V, V,
+                                              U64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1558,6 +1589,144 @@ def matchcluster_host(layout, mode, value, matches, palindromic=None,
                 members=mem[:int(st.inclusters)], labels=lab,
                 edgestart=estart[:k + 1], m0=m0, m1=m1, values=val,
                 text=buf[:written.value].tobytes() if text else None)
+
+
+# ---- chaining (vmatch -pp chain ...) --------------------------------------------
+
+CHAIN_GLOBAL, CHAIN_GLOBAL_GC, CHAIN_GLOBAL_OV, CHAIN_LOCAL_MAX, \
+    CHAIN_LOCAL_THRESHOLD, CHAIN_LOCAL_BEST, CHAIN_LOCAL_PERCENT = range(7)
+CHAIN_MAXGROUP = 1 << 15
+CHAIN_SILENT = 1
+CHAIN_STAGES = ("view", "sort", "replay", "score", "retrieve")
+
+
+def _chain_params(kind, value, maxgap, wf, withinborders, thread=False):
+    return ChainParams(int(kind), int(value), int(maxgap), float(wf),
+                       int(bool(withinborders)), int(bool(thread)))
+
+
+def _chain_text_capacity(chains, chained):
+    # a header per chain, a match line per member
+    return 256 + 96 * chains + 224 * chained
+
+
+def chain_format_host(sink, number, score, start, records, silent=False):
+    """the reference's text of chains in host memory: records[t] = the
+    record of member t of all chains"""
+    number = np.ascontiguousarray(number, np.uint64)
+    score = np.ascontiguousarray(score, np.int64)
+    start = np.ascontiguousarray(start, np.uint64)
+    records = np.ascontiguousarray(records, MATCH_DTYPE)
+    assert len(number) == len(score) == len(start) - 1
+    cap = _chain_text_capacity(len(number), len(records))
+    buf = np.empty(cap, np.uint8)
+    n = lib.vsa_chain_format_host(sink._h, CHAIN_SILENT if silent else 0,
+                                  len(number), _ptr(number), _ptr(score),
+                                  _ptr(start), _ptr(records), _ptr(buf), cap)
+    if n < 0:
+        raise VsaError(int(n), messagespace())
+    return buf[:n].tobytes()
+
+
+class Chain:
+    """Chains of the matches of the lists added (vsa_chain): global, with
+    gap costs, with overlaps, or local, per sequence pair (withinborders) or
+    over the whole list.  layout: what sink_params() returns."""
+
+    def __init__(self, layout, kind=CHAIN_GLOBAL, value=0, maxgap=0, wf=1.0,
+                 withinborders=False, thread=False, device=0):
+        self._layout = layout
+        p = _chain_params(kind, value, maxgap, wf, withinborders, thread)
+        self._h = C.c_void_p()
+        _check(lib.vsa_chain_open(C.byref(layout[0]), C.byref(p), device,
+                                  C.byref(self._h)))
+
+    def add(self, result, palindromic=False):
+        _check(lib.vsa_chain_add(self._h, result._h, int(bool(palindromic))))
+
+    def finish(self):
+        _check(lib.vsa_chain_finish(self._h))
+
+    def stats(self):
+        s = ChainStats()
+        _check(lib.vsa_chain_getstats(self._h, C.byref(s)))
+        return s
+
+    def chains(self):
+        """-> dict(problem, number, score, start, members): chain c has the
+        members members[start[c]:start[c + 1]], record numbers"""
+        s = self.stats()
+        out = dict(problem=np.zeros(s.chains, np.uint64),
+                   number=np.zeros(s.chains, np.uint64),
+                   score=np.zeros(s.chains, np.int64),
+                   start=np.zeros(s.chains + 1, np.uint64),
+                   members=np.zeros(s.chained, np.uint64))
+        _check(lib.vsa_chain_chains(self._h, _ptr(out["problem"]),
+                                    _ptr(out["number"]), _ptr(out["score"]),
+                                    _ptr(out["start"])))
+        _check(lib.vsa_chain_members(self._h, _ptr(out["members"])))
+        return out
+
+    def records(self):
+        """-> (Result of the members of all chains in member order, D/P
+        flags)"""
+        flags = np.zeros(self.stats().chained, np.uint8)
+        h = C.c_void_p()
+        _check(lib.vsa_chain_records(self._h, C.byref(h), _ptr(flags)))
+        return Result(h), flags
+
+    def format(self, sink, silent=False):
+        s = self.stats()
+        cap = _chain_text_capacity(s.chains, s.chained)
+        buf = np.empty(cap, np.uint8)
+        n = lib.vsa_chain_format(self._h, sink._h,
+                                 CHAIN_SILENT if silent else 0, _ptr(buf),
+                                 cap)
+        if n < 0:
+            raise VsaError(int(n), messagespace())
+        return buf[:n].tobytes()
+
+    def times(self):
+        """HIP-event ms of all calls so far per stage -> dict"""
+        ms = np.zeros(len(CHAIN_STAGES), np.float64)
+        _check(lib.vsa_chain_times(self._h, _ptr(ms)))
+        return dict(zip(CHAIN_STAGES, ms.tolist()))
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_chain_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def chain_host(layout, matches, palindromic=None, kind=CHAIN_GLOBAL, value=0,
+               maxgap=0, wf=1.0, withinborders=False, thread=False):
+    """the same chaining of a list in host memory, no GPU, problems of any
+    size -> dict(stats, problem, number, score, start, members)"""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    n = len(matches)
+    pal = None if palindromic is None else \
+        np.ascontiguousarray(palindromic, np.uint8)
+    assert pal is None or len(pal) == n
+    p = _chain_params(kind, value, maxgap, wf, withinborders, thread)
+    st = ChainStats()
+    # once for the counts, once for the chains
+    _check(lib.vsa_chain_host(C.byref(layout[0]), C.byref(p), _ptr(matches),
+                              _ptr(pal), n, C.byref(st), None, None, None,
+                              None, 0, None, 0))
+    k, m = int(st.chains), int(st.chained)
+    out = dict(problem=np.zeros(k, np.uint64), number=np.zeros(k, np.uint64),
+               score=np.zeros(k, np.int64), start=np.zeros(k + 1, np.uint64),
+               members=np.zeros(m, np.uint64))
+    _check(lib.vsa_chain_host(C.byref(layout[0]), C.byref(p), _ptr(matches),
+                              _ptr(pal), n, C.byref(st),
+                              _ptr(out["problem"]), _ptr(out["number"]),
+                              _ptr(out["score"]), _ptr(out["start"]), k,
+                              _ptr(out["members"]), m))
+    out["stats"] = st
+    return out
 
 
 # ---- synthetic inputs (SURVEY.md section 8d) ------------------------------
