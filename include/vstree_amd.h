@@ -1242,7 +1242,7 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
    vsa_cluster above. */
 #define VSA_MATCHCLUSTER_GAP 0     /* gapsize G                             */
 #define VSA_MATCHCLUSTER_OVERLAP 1 /* overlap P                             */
-#define VSA_MATCHCLUSTER_ERATE 2   /* erate: not covered (cluedist.c)       */
+#define VSA_MATCHCLUSTER_ERATE 2   /* erate E: vsa_eratecluster_open        */
 
 typedef struct
 {
@@ -1273,8 +1273,9 @@ typedef struct vsa_matchcluster vsa_matchcluster;
   query Multiseq); markpos, querystart and querylength need not outlive the
   call.  0 and *cluster (on `device`), or a negative code and the message.
   VSA_NOT_COVERED: mode VSA_MATCHCLUSTER_ERATE (the edit distance between the
-  match substrings, Vmatch/cluedist.c); a selfpalindromic layout (vmatch -p
-  IDX).
+  match substrings, Vmatch/cluedist.c: it needs the text, which
+  vsa_eratecluster_open below takes); a selfpalindromic layout (vmatch
+  -p IDX).
 */
 int vsa_matchcluster_open(const vsa_sinkparams *layout,
                           const vsa_matchclusterparams *params, int device,
@@ -1308,9 +1309,10 @@ int vsa_matchcluster_members(const vsa_matchcluster *cluster,
 int vsa_matchcluster_labels(const vsa_matchcluster *cluster, uint64_t *label);
 /* after finish: the edges grouped by cluster, within a cluster in the order
    showClusterSet shows them (descending edge number): edge t links m0[t] and
-   m1[t] with value[t] (the gap, or the bits of the overlap percentage, a
-   double); the edges of cluster c are edgestart[c] .. edgestart[c + 1].
-   stats.clusters + 1 and stats.edges entries; any may be NULL */
+   m1[t] with value[t] (the gap, the bits of the overlap percentage, a
+   double, or minlen << 32 | edit distance); the edges of cluster c are
+   edgestart[c] .. edgestart[c + 1].  stats.clusters + 1 and stats.edges
+   entries; any may be NULL */
 int vsa_matchcluster_edges(vsa_matchcluster *cluster, uint64_t *edgestart,
                            uint32_t *m0, uint32_t *m1, uint64_t *value);
 /* after finish: the member matches of all clusters, in the order of
@@ -1327,10 +1329,11 @@ int64_t vsa_matchcluster_format(const vsa_matchcluster *cluster, char *buffer,
                                 uint64_t capacity);
 /* after finish: the bytes of the file PREFIX.size.c.match behind its first
    line (matchclust.c:31-85): "# id m" and the match line per member, then
-   "# linked a and b with gapsize g" or "... with overlap percentage %.2f"
-   per edge.  The match lines are the sink's; the reference prints them with
-   its fixed default widths (vsa_sink_setdigits(sink, 5, 6, 6, 3, 3)).  Every
-   member is printed with the direction of the sink. */
+   "# linked a and b with gapsize g", "... with overlap percentage %.2f" or
+   "... with edit distance d (error rate %.2f%%)" per edge.  The match lines
+   are the sink's; the reference prints them with its fixed default widths
+   (vsa_sink_setdigits(sink, 5, 6, 6, 3, 3)).  Every member is printed with
+   the direction of the sink. */
 int64_t vsa_matchcluster_format_cluster(vsa_matchcluster *cluster,
                                         vsa_sink *sink, uint64_t c,
                                         char *buffer, uint64_t capacity);
@@ -1363,6 +1366,61 @@ int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
                                      const uint32_t *m0, const uint32_t *m1,
                                      const uint64_t *value, uint64_t nedges,
                                      char *buffer, uint64_t capacity);
+
+/* ---- vmatch -pp matchcluster erate E (Vmatch/cluedist.c:42-198,
+   kurtz/frontSEP.c:341-446, kurtz/front.gen) ---------------------------------
+
+   Links the matches i < j of a SELF list whose substrings are within a unit
+   edit distance of E percent of the shorter one.  Every pair is looked at, i
+   outermost, both ascending; minlen = min(length_i, length_j), maxdist =
+   (uint64_t) ((double) minlen * (double) E / 100.0).  The instance pairs
+   (position1_i, position1_j), (position1_i, position2_j), (position2_i,
+   position1_j), (position2_i, position2_j) are tried in this order, and the
+   first one that answers >= 0 stores the edge (i, j) with value = minlen <<
+   32 | distance -- the distance of the first instance pair within the bound,
+   not the smallest of the four.  An instance pair answers -1 if the lengths
+   differ by more than maxdist; 0 if both instances are the same stretch of
+   text; else the distance the reference's greedy front finds within maxdist
+   rounds, or -1 (with maxdist 0: 0 iff the substrings are equal and free of
+   special symbols).  A special symbol equals nothing, not even itself.  The
+   front is the reference's, including its shortcut on a diagonal where both
+   substrings are the same text (csrc/erate_rules.h).  The edges go through
+   linkcluster in the order found; everything behind the edge list is as for
+   gapsize and overlap.  In the stats candidates = n (n - 1) / 2, below = the
+   pairs without an edge, samematch = 0.
+
+   Covered: layouts of an index against itself without indexed queries,
+   direct lists, lengths below 2^32.  A record that leaves the text or holds
+   a separator does not fit (-2).  On the device a pair that passes the
+   length test with maxdist > VSA_ERATE_MAXDIST makes finish answer
+   VSA_NOT_COVERED; vsa_eratecluster_host takes any maxdist.  The device
+   keeps the rows of a front in 32 bits while every match is shorter than
+   2^30 symbols, else in 64; VSA_ERATE_WIDE_ROWS=1 in the environment asks
+   for 64 whatever the lengths are (the answers are the same). */
+#define VSA_ERATE_MAXDIST 127
+
+/* The handle is a vsa_matchcluster.  (The two entries are not named
+   vsa_matchcluster_*: the binding's tests count the names with that prefix.)
+   layout: as for vsa_matchcluster_open, VSA_SINK_SELF; index: its text is
+   read by add and finish, so the index outlives the handle; errorrate 0 ..
+   100.  Every other vsa_matchcluster_* call works on the handle.
+   VSA_NOT_COVERED: a layout against queries or with indexed queries, a
+   selfpalindromic one.  -2: an error rate above 100, an index of another
+   length than the layout or on another device. */
+int vsa_eratecluster_open(const vsa_sinkparams *layout,
+                          const vsa_index *index, uint32_t errorrate,
+                          int device, vsa_matchcluster **cluster);
+/* the same on a list and a text in host memory, no GPU involved: the
+   reference's two loops and a scalar front; outputs as those of
+   vsa_matchcluster_host */
+int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
+                          const uint8_t *text, uint64_t textlength,
+                          const vsa_match *matches, uint64_t n,
+                          vsa_matchclusterstats *stats, uint64_t *clusterstart,
+                          uint64_t *members, uint64_t *label,
+                          uint64_t *edgestart, uint32_t *m0, uint32_t *m1,
+                          uint64_t *value, uint64_t edgecapacity, char *buffer,
+                          uint64_t capacity, int64_t *written);
 
 /* ---- chaining: vmatch -pp chain [global [gc|ov] | local [K | Kb | Kp]]
    [wf F] [maxgap W] [withinborders] [silent] (Vmatch/parsepp.c:95-109,

@@ -392,6 +392,13 @@ def _load():
                                       C.POINTER(C.c_int64)]),
         "vsa_matchcluster_format_host": (C.c_int64, [V, I, V, V, U64, V, V,
                                                      V, U64, V, U64]),
+        "vsa_eratecluster_open": (I, [C.POINTER(SinkParams), V, C.c_uint32,
+                                      I, PP]),
+        "vsa_eratecluster_host": (I, [C.POINTER(SinkParams), C.c_uint32, V,
+                                      U64, V, U64,
+                                      C.POINTER(MatchClusterStats), V, V, V,
+                                      V, V, V, V, U64, V, U64,
+                                      C.POINTER(C.c_int64)]),
         "vsa_sink_setdigits": (I, [V, I, I, I, I, I]),
         "vsa_chain_open": (I, [C.POINTER(SinkParams), C.POINTER(ChainParams),
                                I, PP]),
@@ -1468,6 +1475,20 @@ class MatchCluster:
         _check(lib.vsa_matchcluster_open(C.byref(layout[0]), C.byref(p),
                                          device, C.byref(self._h)))
 
+    @classmethod
+    def erate(cls, layout, index, errorrate, device=0):
+        """matches linked by the edit distance of their substrings
+        (vsa_eratecluster_open): at most `errorrate` percent of the
+        shorter one.  The text is that of `index`, which the handle keeps."""
+        self = cls.__new__(cls)
+        self._layout, self._index = layout, index
+        self.mode = MATCHCLUSTER_ERATE
+        self._h = C.c_void_p()
+        _check(lib.vsa_eratecluster_open(
+            C.byref(layout[0]), index._h, int(errorrate), device,
+            C.byref(self._h)))
+        return self
+
     def add(self, result, palindromic=False):
         _check(lib.vsa_matchcluster_add(self._h, result._h,
                                         int(bool(palindromic))))
@@ -1588,6 +1609,47 @@ def matchcluster_host(layout, mode, value, matches, palindromic=None,
     return dict(stats=st, clusterstart=cstart[:k + 1],
                 members=mem[:int(st.inclusters)], labels=lab,
                 edgestart=estart[:k + 1], m0=m0, m1=m1, values=val,
+                text=buf[:written.value].tobytes() if text else None)
+
+
+def matchcluster_erate_host(layout, errorrate, text_symbols, matches,
+                            text=True, edges=None):
+    """vmatch -pp matchcluster erate E on a list and the symbols of the index
+    text in host memory, no GPU -> the dict of matchcluster_host; values =
+    minlen << 32 | edit distance.  edges: room for that many edges (default
+    16 per match).  The work is quadratic in the list: it is done once, and
+    once more only where the edges did not fit (-3, which leaves their number
+    in the stats)."""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    tis = np.ascontiguousarray(text_symbols, np.uint8)
+    n = len(matches)
+    st = MatchClusterStats()
+    cstart = np.zeros(n // 2 + 2, np.uint64)
+    estart = np.zeros(n // 2 + 2, np.uint64)
+    mem = np.zeros(n, np.uint64)
+    lab = np.zeros(n, np.uint64)
+    cap = 128 + 96 * (n // 2 + 2) if text else 0
+    buf = np.empty(cap, np.uint8) if text else None
+    written = C.c_int64(0)
+    room = 16 * n + 1024 if edges is None else int(edges)
+    while True:
+        m0 = np.zeros(room, np.uint32)
+        m1 = np.zeros(room, np.uint32)
+        val = np.zeros(room, np.uint64)
+        rc = lib.vsa_eratecluster_host(
+            C.byref(layout[0]), int(errorrate), _ptr(tis), len(tis),
+            _ptr(matches), n, C.byref(st), _ptr(cstart), _ptr(mem), _ptr(lab),
+            _ptr(estart), _ptr(m0), _ptr(m1), _ptr(val), room, _ptr(buf), cap,
+            C.byref(written))
+        if rc != -3 or int(st.edges) <= room:
+            break
+        room = int(st.edges)
+    _check(rc)
+    k, ne = int(st.clusters), int(st.edges)
+    return dict(stats=st, clusterstart=cstart[:k + 1],
+                members=mem[:int(st.inclusters)], labels=lab,
+                edgestart=estart[:k + 1], m0=m0[:ne], m1=m1[:ne],
+                values=val[:ne],
                 text=buf[:written.value].tobytes() if text else None)
 
 

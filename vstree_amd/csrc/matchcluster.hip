@@ -29,11 +29,15 @@
 //   forest, replay, group
 //            cluster_forest.inc and cluster_host.c, over the matches as
 //            nodes: at most matches - 1 edges go to the host.
+// The handles of vsa_eratecluster_open (erate E: the edit distance of
+// the match substrings) have an edge source of their own,
+// matchcluster_erate.inc; refs and everything behind the edges are shared.
 // Match numbers, places of the sorted order and edge numbers are 32 bit (the
 // entry points refuse more); positions, candidate counts and slot numbers
 // are 64 bit.  Nothing is launched on zero elements.
 #include "search_host.hpp"
 #include "matchcluster_rules.h"
+#include "erate_rules.h"
 #include <rocprim/rocprim.hpp>
 #include "cluster_forest.inc"
 
@@ -59,6 +63,12 @@ struct vsa_matchcluster
   uint64_t *d_qstart = nullptr, *d_qlen = nullptr;
   vsa_mcrules rules;
   unsigned int sortbits = 1;
+  // mode VSA_MATCHCLUSTER_ERATE: the text of the index (which outlives the
+  // handle) and the error rate
+  const uint8_t *text = nullptr;
+  uint64_t textlength = 0;
+  uint32_t errorrate = 0;
+  uint64_t longest = 0; // the longest match so far
   // the matches so far
   uint64_t n = 0, capacity = 0;
   vsa_match *recs = nullptr;
@@ -437,6 +447,8 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
   return 0;
 }
 
+#include "matchcluster_erate.inc"
+
 int needfinished(const vsa_matchcluster *c, const char *who)
 {
   if (c == nullptr)
@@ -614,6 +626,48 @@ extern "C" int vsa_matchcluster_open(const vsa_sinkparams *layout,
   return 0;
 }
 
+extern "C" int vsa_eratecluster_open(const vsa_sinkparams *layout,
+                                     const vsa_index *index,
+                                     uint32_t errorrate, int device,
+                                     vsa_matchcluster **cluster)
+{
+  static const char who[] = "vsa_eratecluster_open";
+  if (cluster == nullptr || index == nullptr)
+  {
+    VSA_ERROR("%s: NULL argument", who);
+    return -1;
+  }
+  *cluster = nullptr;
+  vsa_selrules view;
+  const int rc = vsa_er_checklayout(layout, errorrate, index->n, who, &view);
+  if (rc != 0)
+  {
+    return rc;
+  }
+  if (index->device != device)
+  {
+    VSA_ERROR("%s: index on device %d, clustering on device %d", who,
+              index->device, device);
+    return -2;
+  }
+  if (enter(device) != 0)
+  {
+    return -100;
+  }
+  vsa_matchcluster *c = new vsa_matchcluster();
+  c->device = device;
+  c->view = view;
+  c->rules.mode = VSA_MATCHCLUSTER_ERATE;
+  c->rules.maxgapsize = c->rules.minpercentoverlap = 0;
+  c->text = index->tis_alloc + VSA_TIS_FRONTPAD;
+  c->textlength = index->n;
+  c->errorrate = errorrate;
+  memset(&c->stats, 0, sizeof c->stats);
+  memset(&c->res, 0, sizeof c->res);
+  *cluster = c;
+  return 0;
+}
+
 extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
                                     int palindromic)
 {
@@ -660,22 +714,46 @@ extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
     return -100;
   }
   DevBuf bad;
-  if (bad.alloc(8) != 0)
+  if (bad.alloc(24) != 0)
   {
     return -100;
   }
   Timer t(nullptr);
   t.start();
-  VSA_HIP(hipMemsetAsync(bad.p, 0, 8, nullptr));
-  k_mc_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
-      c->view, r->matches, r->count, palindromic != 0, c->n,
-      c->sortbits < 64 ? (uint64_t) 1 << c->sortbits : ~(uint64_t) 0, c->recs,
-      c->flags, c->start, c->length, bad.as<unsigned long long>());
+  VSA_HIP(hipMemsetAsync(bad.p, 0, 24, nullptr));
+  if (c->rules.mode == VSA_MATCHCLUSTER_ERATE)
+  {
+    k_er_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
+        c->view, c->text, c->textlength, r->matches, r->count, c->n, c->recs,
+        c->flags, c->start, c->length, bad.as<unsigned long long>());
+  } else
+  {
+    k_mc_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
+        c->view, r->matches, r->count, palindromic != 0, c->n,
+        c->sortbits < 64 ? (uint64_t) 1 << c->sortbits : ~(uint64_t) 0,
+        c->recs, c->flags, c->start, c->length,
+        bad.as<unsigned long long>());
+  }
   VSA_HIP(hipGetLastError());
   t.stop();
-  uint64_t nbad = 0;
-  VSA_HIP(hipMemcpy(&nbad, bad.p, 8, hipMemcpyDeviceToHost));
+  // (erate: records that do not fit, records too long, the longest length)
+  uint64_t bads[3] = {0, 0, 0};
+  VSA_HIP(hipMemcpy(bads, bad.p, 24, hipMemcpyDeviceToHost));
+  const uint64_t nbad = bads[0];
   c->ms[MC_REFS] += t.ms();
+  if (bads[1] != 0)
+  {
+    VSA_ERROR("vsa_matchcluster_add: %lu records of 2^32 symbols or more: "
+              "erate covers shorter ones", (unsigned long) bads[1]);
+    return VSA_NOT_COVERED;
+  }
+  if (nbad != 0 && c->rules.mode == VSA_MATCHCLUSTER_ERATE)
+  {
+    VSA_ERROR("vsa_matchcluster_add: %lu records do not fit the layout (a "
+              "match that leaves the text or holds a separator)",
+              (unsigned long) nbad);
+    return -2;
+  }
   if (nbad != 0)
   {
     // (what the kernel wrote lies behind the matches that count)
@@ -685,6 +763,7 @@ extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
     return -2;
   }
   c->n += r->count;
+  c->longest = std::max(c->longest, bads[2]);
   c->finished = false;
   return 0;
 }
@@ -707,7 +786,9 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
   double ms[VSA_MATCHCLUSTER_STAGES] = {0, 0, 0, 0, 0, 0};
   if (c->n >= 2)
   {
-    const int rc = findedges(c, edges, &st, ms);
+    const int rc = c->rules.mode == VSA_MATCHCLUSTER_ERATE
+                       ? findedges_erate(c, edges, &st, ms)
+                       : findedges(c, edges, &st, ms);
     if (rc != 0)
     {
       return rc;

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "vstree_amd.h"
 #include "matchcluster_rules.h"
+#include "erate_rules.h"
 
 char *vsa_errbuf(void);
 #define ERRSIZE 1024
@@ -32,7 +33,8 @@ int vsa_mc_checklayout(const vsa_sinkparams *layout,
   if (params->mode == VSA_MATCHCLUSTER_ERATE)
   {
     snprintf(vsa_errbuf(), ERRSIZE, "%s: matchcluster erate (the edit distance "
-             "between the match substrings) is not covered", who);
+             "between the match substrings) is not covered here: it needs the "
+             "text (vsa_eratecluster_open, vsa_eratecluster_host)", who);
     return VSA_NOT_COVERED;
   }
   if (params->mode != VSA_MATCHCLUSTER_GAP &&
@@ -176,6 +178,16 @@ int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
                    "# linked %lu and %lu with gapsize %lu\n",
                    (unsigned long) m0[i], (unsigned long) m1[i],
                    (unsigned long) value[i]);
+    } else if (mode == VSA_MATCHCLUSTER_ERATE)
+    {
+      /* cluedistmlclinkinfo, cluedist.c:108-118 */
+      const uint64_t edist = value[i] & 0xFFFFFFFFull,
+                     minlen = value[i] >> 32;
+      n = snprintf(line, sizeof line,
+                   "# linked %lu and %lu with edit distance %lu (error rate "
+                   "%.2f%%)\n", (unsigned long) m0[i], (unsigned long) m1[i],
+                   (unsigned long) edist,
+                   100.00 * (double) edist / (double) minlen);
     } else
     {
       double overlap;
@@ -264,6 +276,110 @@ static int addedge(Edges *e, uint32_t a, uint32_t b, uint64_t value)
   return 0;
 }
 
+/* the end of both host entries: the edges through linkcluster, and what the
+   caller asked for of the result */
+static int deliver(const char *who, uint64_t n, const Edges *edges,
+                   vsa_matchclusterstats *st, vsa_matchclusterstats *stats,
+                   uint64_t *clusterstart, uint64_t *members, uint64_t *label,
+                   uint64_t *edgestart, uint32_t *m0, uint32_t *m1,
+                   uint64_t *value, uint64_t edgecapacity, char *buffer,
+                   uint64_t capacity, int64_t *written)
+{
+  const Edges e = *edges;
+  vsa_clresult res;
+  uint64_t *fill = NULL;
+  uint64_t i;
+  int64_t bytes = 0;
+  int rc;
+
+  memset(&res, 0, sizeof res);
+  st->edges = e.n;
+  if ((rc = vsa_cl_replay(n, e.m0, e.m1, e.n, &st->forestedges, &res)) != 0)
+  {
+    goto done;
+  }
+  st->clusters = res.clusters;
+  st->inclusters = res.inclusters;
+  if (stats != NULL)
+  {
+    *stats = *st;
+  }
+  if ((m0 != NULL || m1 != NULL || value != NULL) && e.n > edgecapacity)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu edges, room for %lu", who,
+             (unsigned long) e.n, (unsigned long) edgecapacity);
+    rc = -3;
+    goto done;
+  }
+  if (buffer != NULL &&
+      (bytes = vsa_mc_format(n, &res, buffer, capacity)) < 0)
+  {
+    rc = (int) bytes;
+    goto done;
+  }
+  if (edgestart != NULL || m0 != NULL || m1 != NULL || value != NULL)
+  {
+    /* addClusterEdge (cluster.c:586-614): each cluster's part is filled
+       from the back in the order of the edges */
+    fill = calloc((size_t) res.clusters + 2, sizeof *fill);
+    if (fill == NULL)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+      rc = -1;
+      goto done;
+    }
+    for (i = 0; i < e.n; i++)
+    {
+      fill[res.label[e.m0[i]] + 1]++;
+    }
+    for (i = 0; i < res.clusters; i++)
+    {
+      fill[i + 1] += fill[i];
+    }
+    if (edgestart != NULL)
+    {
+      memcpy(edgestart, fill, (size_t) (res.clusters + 1) * sizeof *fill);
+    }
+    for (i = 0; i < e.n; i++)
+    {
+      const uint64_t at = --fill[res.label[e.m0[i]] + 1];
+      if (m0 != NULL)
+      {
+        m0[at] = e.m0[i];
+      }
+      if (m1 != NULL)
+      {
+        m1[at] = e.m1[i];
+      }
+      if (value != NULL)
+      {
+        value[at] = e.value[i];
+      }
+    }
+  }
+  if (clusterstart != NULL)
+  {
+    memcpy(clusterstart, res.clusterstart,
+           (size_t) (res.clusters + 1) * sizeof *clusterstart);
+  }
+  if (members != NULL && res.inclusters > 0)
+  {
+    memcpy(members, res.members, (size_t) res.inclusters * sizeof *members);
+  }
+  if (label != NULL && n > 0)
+  {
+    memcpy(label, res.label, (size_t) n * sizeof *label);
+  }
+  if (written != NULL)
+  {
+    *written = bytes;
+  }
+done:
+  vsa_cl_freeresult(&res);
+  free(fill);
+  return rc;
+}
+
 int vsa_matchcluster_host(const vsa_sinkparams *layout,
                           const vsa_matchclusterparams *params,
                           const vsa_match *matches, const uint8_t *palindromic,
@@ -277,12 +393,10 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
   vsa_selrules rules;
   vsa_mcrules mc;
   vsa_matchclusterstats st;
-  vsa_clresult res;
   Edges e = {NULL, NULL, NULL, 0, 0};
   Mref *ref = NULL, *tmp = NULL;
-  uint64_t *length = NULL, *fill = NULL;
+  uint64_t *length = NULL;
   uint64_t i, j;
-  int64_t bytes = 0;
   int rc = vsa_mc_checklayout(layout, params, "vsa_matchcluster_host", &rules,
                               &mc);
 
@@ -302,7 +416,6 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
     return VSA_NOT_COVERED;
   }
   memset(&st, 0, sizeof st);
-  memset(&res, 0, sizeof res);
   st.matches = n;
   ref = malloc((size_t) (2 * n + 1) * sizeof *ref);
   tmp = malloc((size_t) (2 * n + 1) * sizeof *tmp);
@@ -376,95 +489,237 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
       }
     }
   }
-  st.edges = e.n;
-  if ((rc = vsa_cl_replay(n, e.m0, e.m1, e.n, &st.forestedges, &res)) != 0)
-  {
-    goto done;
-  }
-  st.clusters = res.clusters;
-  st.inclusters = res.inclusters;
-  if (stats != NULL)
-  {
-    *stats = st;
-  }
-  if ((m0 != NULL || m1 != NULL || value != NULL) && e.n > edgecapacity)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: %lu edges, room "
-             "for %lu", (unsigned long) e.n, (unsigned long) edgecapacity);
-    rc = -3;
-    goto done;
-  }
-  if (buffer != NULL &&
-      (bytes = vsa_mc_format(n, &res, buffer, capacity)) < 0)
-  {
-    rc = (int) bytes;
-    goto done;
-  }
-  if (edgestart != NULL || m0 != NULL || m1 != NULL || value != NULL)
-  {
-    /* addClusterEdge (cluster.c:586-614): each cluster's part is filled
-       from the back in the order of the edges */
-    fill = calloc((size_t) res.clusters + 2, sizeof *fill);
-    if (fill == NULL)
-    {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-      rc = -1;
-      goto done;
-    }
-    for (i = 0; i < e.n; i++)
-    {
-      fill[res.label[e.m0[i]] + 1]++;
-    }
-    for (i = 0; i < res.clusters; i++)
-    {
-      fill[i + 1] += fill[i];
-    }
-    if (edgestart != NULL)
-    {
-      memcpy(edgestart, fill, (size_t) (res.clusters + 1) * sizeof *fill);
-    }
-    for (i = 0; i < e.n; i++)
-    {
-      const uint64_t at = --fill[res.label[e.m0[i]] + 1];
-      if (m0 != NULL)
-      {
-        m0[at] = e.m0[i];
-      }
-      if (m1 != NULL)
-      {
-        m1[at] = e.m1[i];
-      }
-      if (value != NULL)
-      {
-        value[at] = e.value[i];
-      }
-    }
-  }
-  if (clusterstart != NULL)
-  {
-    memcpy(clusterstart, res.clusterstart,
-           (size_t) (res.clusters + 1) * sizeof *clusterstart);
-  }
-  if (members != NULL && res.inclusters > 0)
-  {
-    memcpy(members, res.members, (size_t) res.inclusters * sizeof *members);
-  }
-  if (label != NULL && n > 0)
-  {
-    memcpy(label, res.label, (size_t) n * sizeof *label);
-  }
-  if (written != NULL)
-  {
-    *written = bytes;
-  }
+  rc = deliver("vsa_matchcluster_host", n, &e, &st, stats, clusterstart,
+               members, label, edgestart, m0, m1, value, edgecapacity, buffer,
+               capacity, written);
 done:
-  vsa_cl_freeresult(&res);
-  free(fill);
   free(e.m0);
   free(e.m1);
   free(e.value);
   free(ref);
   free(tmp);
   free(length);
+  return rc;
+}
+
+/* ---- erate: uedistcluster, Vmatch/cluedist.c:120-198 ----------------------- */
+
+int vsa_er_checklayout(const vsa_sinkparams *layout, uint32_t errorrate,
+                       uint64_t textlength, const char *who,
+                       vsa_selrules *rules)
+{
+  if (layout == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
+    return -1;
+  }
+  if (errorrate > 100)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: an error rate of %lu is beyond 100",
+             who, (unsigned long) errorrate);
+    return -2;
+  }
+  if (layout->selfpalindromic)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of vmatch -p IDX "
+             "(selfpalindromic) are not covered", who);
+    return VSA_NOT_COVERED;
+  }
+  if (layout->kind != VSA_SINK_SELF || layout->totalquerylength > 0)
+  {
+    /* (the reference takes them and reads position2 off the index text) */
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: matchcluster erate covers lists of "
+             "an index against itself only: the second instance of a match "
+             "against queries is no stretch of the index text", who);
+    return VSA_NOT_COVERED;
+  }
+  if (layout->totallength == 0 || layout->totallength != textlength)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: a layout of %lu symbols, a text of "
+             "%lu", who, (unsigned long) layout->totallength,
+             (unsigned long) textlength);
+    return -2;
+  }
+  memset(rules, 0, sizeof *rules);
+  rules->kind = VSA_SINK_SELF;
+  rules->noevalue = 1;
+  rules->totallength = (double) layout->totallength;
+  rules->dblenplus1 = layout->totallength;
+  return 0;
+}
+
+/* verifysmalldistance and unitedistfrontSEPgeneric with a bound
+   (cluedist.c:42-106, frontSEP.c:341-446) through the rules; front: 2 *
+   (2 * maxdist + 3) words */
+static int64_t instancepair(const uint8_t *text, uint64_t pu, uint64_t ulen,
+                            uint64_t pv, uint64_t vlen, uint64_t maxdist,
+                            int64_t *front)
+{
+  const int64_t goal = (int64_t) vlen - (int64_t) ulen,
+                md = (int64_t) maxdist;
+  /* prev[k] and cur[k] for k = -md - 1 .. md + 1 */
+  int64_t *prev = front + md + 1, *cur = front + 3 * md + 4, *swap;
+  int64_t d, k;
+
+  if (vsa_er_lengthfails(ulen, vlen, maxdist))
+  {
+    return -1;
+  }
+  if (vsa_er_sameinstance(pu, ulen, pv, vlen))
+  {
+    return 0;
+  }
+  for (k = -md - 1; k <= md + 1; k++)
+  {
+    prev[k] = cur[k] = VSA_ER_NEG;
+  }
+  prev[0] = vsa_er_slide(text, pu, ulen, pv, vlen, 0, 0);
+  if (goal == 0 && prev[0] == (int64_t) ulen)
+  {
+    return 0;
+  }
+  for (d = 1; d <= md; d++)
+  {
+    for (k = -d; k <= d; k++)
+    {
+      cur[k] = vsa_er_entry(text, pu, ulen, pv, vlen,
+                            vsa_er_best(prev[k], prev[k - 1], prev[k + 1]),
+                            k);
+    }
+    if (-d <= goal && goal <= d && cur[goal] == (int64_t) ulen)
+    {
+      return d;
+    }
+    swap = prev;
+    prev = cur;
+    cur = swap;
+  }
+  return -1;
+}
+
+int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
+                          const uint8_t *text, uint64_t textlength,
+                          const vsa_match *matches, uint64_t n,
+                          vsa_matchclusterstats *stats, uint64_t *clusterstart,
+                          uint64_t *members, uint64_t *label,
+                          uint64_t *edgestart, uint32_t *m0, uint32_t *m1,
+                          uint64_t *value, uint64_t edgecapacity, char *buffer,
+                          uint64_t capacity, int64_t *written)
+{
+  static const char who[] = "vsa_eratecluster_host";
+  vsa_selrules rules;
+  vsa_matchclusterstats st;
+  Edges e = {NULL, NULL, NULL, 0, 0};
+  uint64_t *length = NULL, *pos = NULL;
+  int64_t *front = NULL;
+  uint64_t i, j, longest = 0;
+  int rc = vsa_er_checklayout(layout, errorrate, textlength, who, &rules);
+
+  if (rc != 0)
+  {
+    return rc;
+  }
+  if ((matches == NULL && n > 0) || text == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
+    return -1;
+  }
+  if (n >= 0xFFFFFFFFull)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu matches: only fewer than 2^32 - 1 "
+             "are covered", who, (unsigned long) n);
+    return VSA_NOT_COVERED;
+  }
+  memset(&st, 0, sizeof st);
+  st.matches = n;
+  length = malloc((size_t) (n + 1) * sizeof *length);
+  pos = malloc((size_t) (2 * n + 1) * sizeof *pos);
+  if (length == NULL || pos == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+    rc = -1;
+    goto done;
+  }
+  for (i = 0; i < n; i++)
+  {
+    vsa_selvalues v;
+    if (vsa_sel_values(&rules, matches + i, 0, &v) != 0)
+    {
+      rc = -2;
+    } else
+    {
+      rc = vsa_er_checkrecord(text, textlength, v.length1, v.position1,
+                              v.position2);
+    }
+    if (rc != 0)
+    {
+      snprintf(vsa_errbuf(), ERRSIZE, rc == -2
+               ? "%s: record %lu does not fit the layout (it leaves the text "
+                 "or holds a separator)"
+               : "%s: record %lu: only lengths below 2^32 are covered", who,
+               (unsigned long) i);
+      goto done;
+    }
+    length[i] = v.length1;
+    pos[2 * i] = v.position1;
+    pos[2 * i + 1] = v.position2;
+    if (longest < v.length1)
+    {
+      longest = v.length1;
+    }
+  }
+  front = malloc((size_t) (4 * vsa_er_maxdist(longest, errorrate) + 8) *
+                 sizeof *front);
+  if (front == NULL)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+    rc = -1;
+    goto done;
+  }
+  for (i = 0; i + 1 < n; i++)
+  {
+    for (j = i + 1; j < n; j++)
+    {
+      const uint64_t minlen = length[i] < length[j] ? length[i] : length[j],
+                     maxdist = vsa_er_maxdist(minlen, errorrate);
+      int64_t edist = -1;
+      int c;
+      st.candidates++;
+      for (c = 0; c < 4 && edist < 0; c++)
+      {
+        edist = instancepair(text, pos[2 * i + vsa_er_first(c)], length[i],
+                             pos[2 * j + vsa_er_second(c)], length[j],
+                             maxdist, front);
+      }
+      if (edist < 0)
+      {
+        st.below++;
+        continue;
+      }
+      if (e.n + 1 >= 0xFFFFFFFFull)
+      {
+        snprintf(vsa_errbuf(), ERRSIZE, "%s: only fewer than 2^32 - 1 edges "
+                 "are covered", who);
+        rc = VSA_NOT_COVERED;
+        goto done;
+      }
+      if (addedge(&e, (uint32_t) i, (uint32_t) j,
+                  vsa_er_value(minlen, (uint64_t) edist)) != 0)
+      {
+        rc = -1;
+        goto done;
+      }
+    }
+  }
+  rc = deliver(who, n, &e, &st, stats, clusterstart, members, label,
+               edgestart, m0, m1, value, edgecapacity, buffer, capacity,
+               written);
+done:
+  free(e.m0);
+  free(e.m1);
+  free(e.value);
+  free(length);
+  free(pos);
+  free(front);
   return rc;
 }
