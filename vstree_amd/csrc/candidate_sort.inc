@@ -1,10 +1,10 @@
-// K4s: MUM candidates into dbstart order by buckets -- kernels and their host
-// driver; included by esa_search.hip in front of mum_filter.inc's callers.
+// K4s: MUM candidates thrown into dbstart buckets, every bucket sorted AND
+// filtered in LDS -- kernels and their host driver; included by esa_search.hip
+// behind mum_filter.inc, whose rule (k_mumf_flags<false>) and scans it uses.
 //
-// What the filter (k_mumf_* in mum_filter.inc) asks of the sort in front of
-// it: the (key, value) pairs in order of dbstart = key >> lenbits, in ANY
-// order inside a run of equal dbstarts -- k_mumf_flags looks at runs as runs,
-// and the order the candidates arrive in (wavefront atomics on cursor
+// The rule asks for the (key, value) pairs in order of dbstart = key >>
+// lenbits, in ANY order inside a run of equal dbstarts -- runs are looked at as
+// runs, and the order the candidates arrive in (wavefront atomics on cursor
 // regions) differs from call to call anyway, so no stability either.  Four
 // onesweep passes over 8-bit digits deliver more than that, and each pays a
 // look-back chain over ~1 400 workgroups whatever it moves.  Candidates are
@@ -20,14 +20,22 @@
 //                 regions of the search kernel and of the plan, and the first
 //                 pass's arrays, key and value formed as k_append_first forms
 //                 them -- the dense list of compact() is never made here.
-//   k_cs_scan     one workgroup: bucket counts -> bucket starts in the sorted
-//                 list, and "a bucket holds more than VSA_CS_CAP" into the
-//                 flag word the filter's fetch brings to the host anyway.
-//   k_cs_sort     a workgroup per bucket: the bucket's pairs in registers, a
+//                 A candidate whose right end lies in a later bucket leaves
+//                 it there (atomicMax on bcarry[], one candidate in some
+//                 thousands): bcarry[b] is all that bucket b has to know of
+//                 the buckets in front of it, see k_cs_filter.
+//   k_cs_filter   a workgroup per bucket: the bucket's pairs in registers, a
 //                 counting sort in LDS on the top VSA_CS_BINBITS bits of the
 //                 `shift` low dbstart bits (about one pair per bin), ranks
-//                 inside a bin by looking at the bin, and keys / values
-//                 written where the filter reads them.
+//                 inside a bin by looking at the bin, the pairs stored at
+//                 their ranks; then the filter's rule on the sorted bucket
+//                 where it lies, and the survivors written back in order to
+//                 the front of the bucket's own staging region, with their
+//                 number and the sum of their lengths.
+//   k_mumf_scan   (mum_filter.inc) survivors per bucket -> where each
+//                 bucket's records go; a second workgroup sums the lengths.
+//   k_cs_write    a workgroup per bucket: its survivors from staging as
+//                 32-byte records at the bucket's place in the result.
 //
 // Inside a bucket the high dbstart bits are implied by the place, so where
 // shift + lenbits + 32 value bits fit into 64 a staging entry is 8 bytes
@@ -35,21 +43,30 @@
 // store (64-bit values, or a text so long / a list so short that shift +
 // lenbits > 32).
 //
-// When it does not apply: candidates concentrated on a small part of the text
-// (amplicon reads, a repeat family) overflow a bucket (k_cs_scan) or, inside
-// a bucket that fits, a bin: the ranking inside a bin is quadratic, so
-// k_cs_sort gives up on a bin of more than VSA_CS_BINLIMIT pairs.  Then
-// nothing is lost but time: the flag comes back with the filter's counts, and
-// the caller runs compact() and the rocPRIM sort as before.  The filter
-// kernels between the flag and its fetch run over undefined keys in that
-// case: wasted but safe (their loops are bounded by VSA_RUN_LIMIT, every
-// index by the number of candidates), and the caller backs off on an index
-// whose batches keep doing this (vsa_index::cs_skip).
+// Until round 12 the sorted pairs were written out as two arrays and read
+// back by the five launches of mumfilter_tiles (tile maxima, scan, flags,
+// scan, writer: 940 MB for the 11.6 M candidates of the headline batch where
+// this moves 630).
 //
-// Measured on MI355X: profiles/r05/ (probe of the scatter, timeline, resource
-// usage); DESIGN.md section 5 quotes from there.
+// When it does not apply: candidates concentrated on a small part of the text
+// (amplicon reads, a repeat family) overflow a bucket or, inside a bucket
+// that fits, a bin: the ranking inside a bin is quadratic, so k_cs_filter
+// gives up on a bin of more than VSA_CS_BINLIMIT pairs.  Either way the
+// workgroup that sees it raises VSA_CS_OVERFLOW and leaves no survivors; then
+// nothing is lost but time: the flag comes back with the counts, and the
+// caller runs compact() and the rocPRIM sort as before.  The other workgroups
+// and the writer go on in that case: wasted but safe (every per-bucket number
+// is zeroed in front of the scatter, the loops are bounded by VSA_RUN_LIMIT,
+// every index by VSA_CS_CAP, the bucket's count or the number of
+// candidates), and the caller backs off on an index whose batches keep doing
+// this (vsa_index::cs_skip).  A run of more than VSA_RUN_LIMIT equal dbstarts
+// raises bit 0 as k_mumf_flags does, and the caller sorts on all bits.
+//
+// Measured on MI355X: profiles/r05/ (probe of the scatter, the sort alone)
+// and profiles/r12/ (sort and filter in one kernel); DESIGN.md section 5
+// quotes from there.
 
-#define VSA_CS_CAP 4096 // pairs per bucket: 32 KB (64 KB) of LDS in k_cs_sort
+#define VSA_CS_CAP 4096 // pairs per bucket: 32 KB (64 KB) of LDS in k_cs_filter
 #define VSA_CS_ITEMS (VSA_CS_CAP / VSA_BLOCK)
 #define VSA_CS_BINBITS 11
 #define VSA_CS_BINS (1u << VSA_CS_BINBITS)
@@ -201,13 +218,22 @@ vsa_cs_foreach(const CsRegions &r, uint64_t wg, uint32_t group, Fn fn)
 // once, and wait in registers (a workgroup that walked 32 reads per thread
 // one load after the other, twice, took twice as long); the cursor regions
 // are walked twice.
+//
+// bcarry[b] = the largest right end of a candidate of an earlier bucket that
+// reaches into bucket b (0: none).  That is the reference's running `dbright`
+// on entering b as far as it matters there: a candidate of b ends at or
+// behind the start of b, and whatever does not reach b ends in front of it.
+// With shift >= lenbits a candidate reaches one later bucket at most; a long
+// match over narrow buckets (shift < lenbits) marks each one it reaches.
 template <typename VAL, bool SMALL>
 __global__ void __launch_bounds__(VSA_CS_SCATTER_BLOCK)
 k_cs_scatter(CsSources src, CsTiles t, CsGeometry g,
              uint32_t *__restrict__ counts,
+             unsigned long long *__restrict__ bcarry,
              typename CsForm<VAL, SMALL>::Entry *__restrict__ staging)
 {
   extern __shared__ uint32_t cs_hist[]; // nbuckets words
+  const KeyToRightEnd rightend = {g.lenbits};
   const uint32_t nb = (uint32_t) g.nbuckets;
   auto bucket = [&](uint64_t key) {
     const uint64_t b = (key >> g.lenbits) >> g.shift;
@@ -251,10 +277,17 @@ k_cs_scatter(CsSources src, CsTiles t, CsGeometry g,
     {
       rank = atomicAdd(&cs_hist[b], 1u);
     }
-    if (rank < VSA_CS_CAP) // (beyond: counted, and the scan raises the flag)
-    {
+    if (rank < VSA_CS_CAP) // (beyond: counted, and k_cs_filter raises the
+    {                      // flag)
       staging[(uint64_t) b * VSA_CS_CAP + rank] =
           CsForm<VAL, SMALL>::make(key, val, g);
+    }
+    const uint64_t end = rightend(key);
+    uint64_t last = end >> g.shift;
+    last = last < nb ? last : nb - 1;
+    for (uint64_t later = (uint64_t) b + 1; later <= last; later++)
+    {
+      atomicMax(&bcarry[later], (unsigned long long) end);
     }
   };
   // which tile
@@ -336,62 +369,51 @@ k_cs_scatter(CsSources src, CsTiles t, CsGeometry g,
   }
 }
 
-// one workgroup: starts[b] = pairs in the buckets in front of b; a bucket
-// beyond its capacity raises VSA_CS_OVERFLOW
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_cs_scan(const uint32_t *__restrict__ counts, uint64_t nbuckets,
-          uint64_t *__restrict__ starts, unsigned int *__restrict__ flag)
+// inclusive running maximum over the 64 lanes
+__device__ __forceinline__ uint64_t vsa_wave_inclusive_max(uint64_t v)
 {
-  __shared__ uint64_t sh[VSA_BLOCK / 64 + 1];
-  uint64_t run = 0;
-  uint32_t largest = 0;
-  for (uint64_t b = 0; b < nbuckets; b += VSA_BLOCK * VSA_FT_SCANITEMS)
-  {
-    const uint64_t i0 = b + (uint64_t) threadIdx.x * VSA_FT_SCANITEMS;
-    uint32_t v[VSA_FT_SCANITEMS];
-    uint64_t mine = 0;
+  const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
-    for (int k = 0; k < VSA_FT_SCANITEMS; k++)
-    {
-      v[k] = i0 + k < nbuckets ? counts[i0 + k] : 0;
-      mine += v[k];
-      largest = v[k] > largest ? v[k] : largest;
-    }
-    uint64_t total;
-    uint64_t ex = run + vsa_block_exscan<0>(mine, sh, total);
-#pragma unroll
-    for (int k = 0; k < VSA_FT_SCANITEMS; k++)
-    {
-      if (i0 + k < nbuckets)
-      {
-        starts[i0 + k] = ex;
-      }
-      ex += v[k];
-    }
-    run += total;
-  }
-  if (largest > VSA_CS_CAP)
+  for (int d = 1; d < 64; d <<= 1)
   {
-    atomicOr(flag, VSA_CS_OVERFLOW);
+    const uint64_t o =
+        vsa_shfl64(v, (int) (lane >= (uint32_t) d ? lane - d : lane));
+    v = lane >= (uint32_t) d && o > v ? o : v;
   }
+  return v;
 }
 
-// a workgroup per bucket: its pairs sorted on the `shift` low dbstart bits,
-// written as keys and values at the bucket's place in the list
+// A workgroup per bucket: its pairs sorted on the `shift` low dbstart bits in
+// LDS, filtered there by the rule of k_mumf_flags<false>, and the survivors
+// written back in order to the front of the bucket's staging region --
+// staging[b * VSA_CS_CAP + i], i < bsurv[b]; blen[b] = the sum of their
+// lengths.  (The workgroup owns the region and has read all of it into
+// registers long before it writes.)  carry: see mumfilter_tiles.
+//
+// The sorted bucket is walked in rows of VSA_BLOCK, one pair per thread, so
+// that LDS is read without bank conflicts.  A row of a wavefront is a
+// segment: the running maximum of the right ends is scanned inside segments
+// by shuffles, the (at most 64) segment maxima by the first wavefront, and
+// the same two levels -- a ballot inside the segment -- place the survivors.
+// The segments' words and the scans' lie in `bins`, which the sort needs no
+// longer by then: 40 960 bytes of LDS in the 8-byte form are four workgroups
+// per CU, one word more would be three.
 template <typename VAL, bool SMALL>
 __global__ void __launch_bounds__(VSA_BLOCK)
-k_cs_sort(const typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
-          const uint32_t *__restrict__ counts,
-          const uint64_t *__restrict__ starts,
-          unsigned int *__restrict__ flag, CsGeometry g, uint64_t ncand,
-          uint64_t *__restrict__ k2, VAL *__restrict__ v2)
+k_cs_filter(typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
+            const uint32_t *__restrict__ counts,
+            const unsigned long long *__restrict__ bcarry,
+            unsigned int *__restrict__ flag, CsGeometry g, uint64_t carry,
+            uint64_t *__restrict__ bsurv, uint64_t *__restrict__ blen)
 {
   using F = CsForm<VAL, SMALL>;
   using Entry = typename F::Entry;
+  constexpr uint32_t SEGS = VSA_CS_ITEMS * (VSA_BLOCK / 64);
+  static_assert(SEGS <= 64, "the first wavefront scans the segments");
   __shared__ Entry buf[VSA_CS_CAP];
-  __shared__ uint32_t bins[VSA_CS_BINS];
-  // (the scan's few words lie in buf, which is filled behind the scan: 40 960
-  // bytes of LDS are four workgroups per CU, 41 000 are three)
+  __shared__ uint64_t binwords[VSA_CS_BINS / 2];
+  uint32_t *bins = reinterpret_cast<uint32_t *>(binwords);
+  // (the first scan's few words lie in buf, which is filled behind that scan)
   uint64_t *sh = reinterpret_cast<uint64_t *>(buf);
   // ("a bin is too large", in buf as well, behind the scan's words)
   uint32_t *toobig = reinterpret_cast<uint32_t *>(buf) + 32;
@@ -401,16 +423,23 @@ k_cs_sort(const typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
     return;
   }
   const uint32_t c = counts[b];
-  const uint64_t start = starts[b];
-  if (c == 0 || c > VSA_CS_CAP || start + c > ncand)
+  if (c == 0)
   {
     return;
   }
+  if (c > VSA_CS_CAP) // (the scatter kept VSA_CS_CAP of them)
+  {
+    if (threadIdx.x == 0)
+    {
+      atomicOr(flag, VSA_CS_OVERFLOW);
+    }
+    return;
+  }
   // An overflow: the list is sorted again by the caller, nothing to do here.
-  // Workgroups of this very launch raise the flag as well (a bin too large,
-  // below), so the wavefronts of a workgroup could read different values:
-  // one thread reads it, and all decide on that word behind the barrier --
-  // a workgroup goes on whole or not at all.
+  // Workgroups of this very launch raise the flag, so the wavefronts of a
+  // workgroup could read different values: one thread reads it, and all
+  // decide on that word behind the barrier -- a workgroup goes on whole or
+  // not at all.
   if (threadIdx.x == 0)
   {
     *toobig = (*flag & VSA_CS_OVERFLOW) != 0 ? 1u : 0u;
@@ -426,43 +455,48 @@ k_cs_sort(const typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
   {
     return;
   }
-  // the pairs of the bucket in registers; pairs per bin
-  Entry e[VSA_CS_ITEMS];
+  // the pairs of the bucket in registers; pairs per bin.  (A pair with
+  // dbstart bits beyond the bucket -- none comes from the scatter -- counts
+  // for the last bin: every index into bins stays below VSA_CS_BINS.)
+  auto binof = [&](const Entry &x) {
+    const uint64_t bin = F::sub(x, g) >> binshift;
+    return (uint32_t) (bin < VSA_CS_BINS ? bin : VSA_CS_BINS - 1);
+  };
+  {
+    Entry e[VSA_CS_ITEMS];
 #pragma unroll
-  for (int k = 0; k < VSA_CS_ITEMS; k++)
-  {
-    const uint32_t i = k * VSA_BLOCK + threadIdx.x;
-    if (i < c)
+    for (int k = 0; k < VSA_CS_ITEMS; k++)
     {
-      e[k] = staging[b * VSA_CS_CAP + i];
-      atomicAdd(&bins[F::sub(e[k], g) >> binshift], 1u);
+      const uint32_t i = k * VSA_BLOCK + threadIdx.x;
+      if (i < c)
+      {
+        e[k] = staging[b * VSA_CS_CAP + i];
+        atomicAdd(&bins[binof(e[k])], 1u);
+      }
     }
-  }
-  __syncthreads();
-  // bins[x] = pairs in the bins in front of x (a thread takes 8 bins)
-  {
+    __syncthreads();
+    // bins[x] = pairs in the bins in front of x (a thread takes 8 bins)
     constexpr int PER = VSA_CS_BINS / VSA_BLOCK;
-    uint32_t v[PER];
-    uint64_t mine = 0;
-#pragma unroll
-    for (int j = 0; j < PER; j++)
     {
-      v[j] = bins[threadIdx.x * PER + j];
-      mine += v[j];
-    }
-    uint64_t total;
-    uint32_t ex = (uint32_t) vsa_block_exscan<0>(mine, sh, total);
+      uint32_t v[PER];
+      uint64_t mine = 0;
 #pragma unroll
-    for (int j = 0; j < PER; j++)
-    {
-      bins[threadIdx.x * PER + j] = ex;
-      ex += v[j];
+      for (int j = 0; j < PER; j++)
+      {
+        v[j] = bins[threadIdx.x * PER + j];
+        mine += v[j];
+      }
+      uint64_t total;
+      uint32_t ex = (uint32_t) vsa_block_exscan<0>(mine, sh, total);
+#pragma unroll
+      for (int j = 0; j < PER; j++)
+      {
+        bins[threadIdx.x * PER + j] = ex;
+        ex += v[j];
+      }
     }
-  }
-  __syncthreads();
-  // a bin too large for the quadratic ranking below: the caller sorts again
-  {
-    constexpr int PER = VSA_CS_BINS / VSA_BLOCK;
+    __syncthreads();
+    // a bin too large for the quadratic ranking below: the caller sorts again
     uint32_t big = 0;
 #pragma unroll
     for (int j = 0; j < PER; j++)
@@ -485,36 +519,236 @@ k_cs_sort(const typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
       return;
     }
     __syncthreads(); // (buf is written from here on)
-  }
-  // into LDS bin by bin; afterwards bins[x] = the END of bin x
+    // into LDS bin by bin; afterwards bins[x] = the END of bin x
 #pragma unroll
-  for (int k = 0; k < VSA_CS_ITEMS; k++)
-  {
-    const uint32_t i = k * VSA_BLOCK + threadIdx.x;
-    if (i < c)
+    for (int k = 0; k < VSA_CS_ITEMS; k++)
     {
-      buf[atomicAdd(&bins[F::sub(e[k], g) >> binshift], 1u)] = e[k];
+      const uint32_t i = k * VSA_BLOCK + threadIdx.x;
+      if (i < c)
+      {
+        const uint32_t at = atomicAdd(&bins[binof(e[k])], 1u);
+        if (at < c) // (always)
+        {
+          buf[at] = e[k];
+        }
+      }
     }
   }
   __syncthreads();
   // the place of a pair inside its bin: the pairs of the bin with a smaller
-  // dbstart, and those with the same one that lie in front of it
-  for (uint32_t p = threadIdx.x; p < c; p += VSA_BLOCK)
+  // dbstart, and those with the same one that lie in front of it.  Pairs and
+  // places wait in registers until every thread has looked at its bins; then
+  // buf is in dbstart order without a second buffer.
   {
-    const Entry m = buf[p];
-    const uint64_t sm = F::sub(m, g);
-    const uint32_t x = (uint32_t) (sm >> binshift);
-    const uint32_t first = x > 0 ? bins[x - 1] : 0, end = bins[x];
-    uint32_t r = first;
-    for (uint32_t j = first; j < end; j++)
+    Entry m[VSA_CS_ITEMS];
+    uint32_t place[VSA_CS_ITEMS];
+#pragma unroll
+    for (int k = 0; k < VSA_CS_ITEMS; k++)
     {
-      const uint64_t sj = F::sub(buf[j], g);
-      r += (sj < sm || (sj == sm && j < p)) ? 1u : 0u;
+      const uint32_t p = k * VSA_BLOCK + threadIdx.x;
+      place[k] = VSA_CS_CAP;
+      if (p < c)
+      {
+        m[k] = buf[p];
+        const uint64_t sm = F::sub(m[k], g);
+        const uint32_t x = binof(m[k]);
+        uint32_t first = x > 0 ? bins[x - 1] : 0, end = bins[x];
+        end = end < c ? end : c; // (already so)
+        uint32_t r = first;
+        for (uint32_t j = first; j < end; j++)
+        {
+          const uint64_t sj = F::sub(buf[j], g);
+          r += (sj < sm || (sj == sm && j < p)) ? 1u : 0u;
+        }
+        place[k] = r;
+      }
     }
-    if (r < c) // (always; keeps the stores inside the bucket's part of the
-    {          // list whatever LDS held)
-      k2[start + r] = F::key(m, b, g);
-      v2[start + r] = F::val(m);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < VSA_CS_ITEMS; k++)
+    {
+      if (place[k] < c) // (always for a pair there is; keeps the stores
+      {                 // inside the bucket whatever LDS held)
+        buf[place[k]] = m[k];
+      }
+    }
+  }
+  __syncthreads();
+  // ---- the filter (bins is free from here on)
+  uint64_t *segmax = binwords;       // SEGS words
+  uint32_t *segcount = bins + 128;   // SEGS + 1 words
+  uint64_t *sh2 = binwords + 128;    // a scan's few words
+  const KeyToRightEnd rightend = {g.lenbits};
+  const uint64_t lenmask = (1ull << g.lenbits) - 1;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t nsegs = (c + VSA_BLOCK - 1) / VSA_BLOCK * (VSA_BLOCK / 64);
+  auto keyat = [&](uint32_t i) { return F::key(buf[i], b, g); };
+  // the largest right end in front of each pair inside its segment
+  uint64_t before[VSA_CS_ITEMS];
+#pragma unroll
+  for (int r = 0; r < VSA_CS_ITEMS; r++)
+  {
+    before[r] = 0;
+    if ((uint32_t) r * VSA_BLOCK < c) // (the same for the whole workgroup)
+    {
+      const uint32_t i = r * VSA_BLOCK + threadIdx.x;
+      const uint64_t incl =
+          vsa_wave_inclusive_max(i < c ? rightend(keyat(i)) : 0);
+      const uint64_t prev = vsa_shfl64(incl, (int) (lane > 0 ? lane - 1 : 0));
+      before[r] = lane > 0 ? prev : 0;
+      if (lane == 63)
+      {
+        segmax[r * (VSA_BLOCK / 64) + wave] = incl;
+      }
+    }
+  }
+  __syncthreads();
+  // ... and in front of each segment: the caller's carry, what reaches in
+  // from the buckets in front, the segments in front
+  if (threadIdx.x < 64)
+  {
+    const uint64_t incl =
+        vsa_wave_inclusive_max(lane < nsegs ? segmax[lane] : 0);
+    const uint64_t prev = vsa_shfl64(incl, (int) (lane > 0 ? lane - 1 : 0));
+    uint64_t start = bcarry[b];
+    start = carry > start ? carry : start;
+    const uint64_t mine = lane > 0 ? prev : 0;
+    segmax[lane] = mine > start ? mine : start;
+  }
+  __syncthreads();
+  // who survives: k_mumf_flags<false>, word for word, on LDS
+  uint32_t okbits = 0;
+  uint64_t len = 0;
+#pragma unroll
+  for (int r = 0; r < VSA_CS_ITEMS; r++)
+  {
+    if ((uint32_t) r * VSA_BLOCK < c)
+    {
+      const uint32_t i = r * VSA_BLOCK + threadIdx.x;
+      bool ok = false;
+      uint64_t kk = 0;
+      if (i < c)
+      {
+        kk = keyat(i);
+        const uint64_t e = rightend(kk);
+        const uint64_t seg = segmax[r * (VSA_BLOCK / 64) + wave];
+        const uint64_t run = seg > before[r] ? seg : before[r];
+        ok = run < e;
+        if (ok)
+        {
+          const uint64_t d = kk >> g.lenbits;
+          uint32_t steps = 0;
+          for (uint32_t j = i; j > 0 && (keyat(j - 1) >> g.lenbits) == d; j--)
+          {
+            if (rightend(keyat(j - 1)) >= e || ++steps > VSA_RUN_LIMIT)
+            {
+              ok = false;
+              break;
+            }
+          }
+          if (steps > VSA_RUN_LIMIT)
+          {
+            atomicOr(flag, 1u);
+          }
+          steps = 0;
+          for (uint32_t j = i + 1;
+               ok && j < c && (keyat(j) >> g.lenbits) == d; j++)
+          {
+            if (rightend(keyat(j)) >= e || ++steps > VSA_RUN_LIMIT)
+            {
+              ok = false;
+            }
+          }
+          if (steps > VSA_RUN_LIMIT)
+          {
+            atomicOr(flag, 1u);
+          }
+        }
+      }
+      const uint64_t mask = __ballot(ok);
+      if (lane == 0)
+      {
+        segcount[r * (VSA_BLOCK / 64) + wave] = (uint32_t) __popcll(mask);
+      }
+      okbits |= ok ? 1u << r : 0u;
+      len += ok ? lenmask - (kk & lenmask) : 0;
+    }
+  }
+  __syncthreads();
+  // segcount[s] = survivors in the segments in front of s; [SEGS]: all
+  if (threadIdx.x < 64)
+  {
+    const uint32_t v = lane < nsegs ? segcount[lane] : 0;
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint32_t o = __shfl_up(incl, d, 64);
+      incl += lane >= (uint32_t) d ? o : 0;
+    }
+    segcount[lane] = incl - v;
+    if (lane == 63)
+    {
+      segcount[SEGS] = incl;
+    }
+  }
+  __syncthreads();
+  // the survivors back into the bucket's region, in order: a survivor goes
+  // to a place at or in front of the one it had in the sorted bucket
+#pragma unroll
+  for (int r = 0; r < VSA_CS_ITEMS; r++)
+  {
+    if ((uint32_t) r * VSA_BLOCK < c)
+    {
+      const bool ok = ((okbits >> r) & 1u) != 0;
+      const uint64_t mask = __ballot(ok);
+      const uint32_t at = segcount[r * (VSA_BLOCK / 64) + wave] +
+                          (uint32_t) __popcll(mask & ((1ull << lane) - 1));
+      if (ok && at < c) // (always)
+      {
+        staging[b * VSA_CS_CAP + at] = buf[r * VSA_BLOCK + threadIdx.x];
+      }
+    }
+  }
+  uint64_t alllen;
+  (void) vsa_block_exscan<0>(len, sh2, alllen);
+  if (threadIdx.x == 0)
+  {
+    const uint32_t kept = segcount[SEGS];
+    bsurv[b] = kept < c ? kept : c; // (already so)
+    blen[b] = alllen;
+  }
+}
+
+// A workgroup per bucket: the bucket's survivors, which k_cs_filter left at
+// the front of its staging region, as records at off[b] + i.  Walked in rows
+// of VSA_BLOCK, one survivor per thread, so that the records of neighbouring
+// lanes lie next to each other (see k_mumf_write).
+template <typename VAL, bool SMALL>
+__global__ void __launch_bounds__(VSA_BLOCK)
+k_cs_write(const typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
+           const uint64_t *__restrict__ bsurv, const uint64_t *__restrict__ off,
+           CsGeometry g, uint64_t ncand, PairRecord<VAL> write,
+           vsa_match *__restrict__ out)
+{
+  using F = CsForm<VAL, SMALL>;
+  const uint64_t b = vsa_bid();
+  if (b >= g.nbuckets)
+  {
+    return;
+  }
+  uint64_t n = bsurv[b];
+  n = n < VSA_CS_CAP ? n : VSA_CS_CAP;
+  const uint64_t at = off[b];
+  // (at + n <= ncand, the records `out` has room for, unless the scatter met
+  // more candidates than the caller knew of)
+#pragma unroll 4
+  for (uint64_t i = threadIdx.x; i < n; i += VSA_BLOCK)
+  {
+    if (at + i < ncand)
+    {
+      const typename F::Entry e = staging[b * VSA_CS_CAP + i];
+      write(F::key(e, b, g), (uint64_t) F::val(e), out + at + i);
     }
   }
 }
@@ -540,18 +774,20 @@ inline CsGeometry cs_geometry(uint64_t textlen, uint64_t ncand,
   return g;
 }
 
-// The candidates of `src` (ncand of them, positions in a text of textlen
-// symbols) as keys k2 / values v2 in dbstart order, what
-// rocprim::radix_sort_pairs(keys, k2, vals, v2, ncand, lenbits, lenbits +
-// dbbits) delivers up to the order inside runs of equal dbstarts -- or
-// VSA_CS_OVERFLOW in *flag (device; zeroed by the caller) and k2 / v2
-// undefined.  *used: the geometry it chose.
+// The MUMs of the candidates of `src` (ncand of them, positions in a text of
+// textlen symbols), as records in dbstart order in `out` (room for ncand):
+// what rocprim::radix_sort_pairs(keys, k2, vals, v2, ncand, lenbits, lenbits
+// + dbbits) and mumfilter_tiles<false>(..., carry, write, ...) deliver.
+// got[] = their number, the sum of their lengths and the flag word (bit 0: a
+// run was too long for the filter by runs, VSA_CS_OVERFLOW: a bucket or a bin
+// did not fit); with a flag up the first two and `out` are not to be used.
+// *used: the geometry it chose.
 template <typename VAL>
-int candidate_bucketsort(const CsSources &src, uint64_t ncand,
-                         uint64_t textlen, unsigned int lenbits,
-                         unsigned int dbbits, uint64_t *k2, VAL *v2,
-                         unsigned int *flag, hipStream_t stream,
-                         CsGeometry *used)
+int candidate_bucketfilter(const CsSources &src, uint64_t ncand,
+                           uint64_t textlen, unsigned int lenbits,
+                           unsigned int dbbits, uint64_t carry,
+                           PairRecord<VAL> write, hipStream_t stream,
+                           vsa_match *out, uint64_t got[3], CsGeometry *used)
 {
   const CsGeometry g = cs_geometry(textlen, ncand, lenbits, dbbits);
   if (g.nbuckets > VSA_CS_MAXBUCKETS) // (the caller asks cs_geometry first)
@@ -559,13 +795,26 @@ int candidate_bucketsort(const CsSources &src, uint64_t ncand,
     return -100;
   }
   const bool small = sizeof(VAL) == 4 && g.shift + lenbits <= 32;
-  DevBuf counts, starts, staging;
-  if (counts.alloc(g.nbuckets * 4) || starts.alloc(g.nbuckets * 8) ||
-      staging.alloc(g.nbuckets * VSA_CS_CAP * (small ? 8 : 16)))
+  // One allocation of 8-byte words.  What has to be zero lies in front and is
+  // zeroed by one fill: the flag word (with a word of padding), bcarry,
+  // survivors and their lengths per bucket, the buckets' counters (4 bytes
+  // each), in whole 16 bytes.  Behind it what the scan writes: offsets and running lengths, one
+  // more than buckets each.
+  const uint64_t nb = g.nbuckets;
+  const uint64_t zeroed = (2 + 3 * nb + (nb + 1) / 2 + 1) & ~1ull;
+  DevBuf words, staging;
+  if (words.alloc((zeroed + 2 * (nb + 1)) * 8) ||
+      staging.alloc(nb * VSA_CS_CAP * (small ? 8 : 16)))
   {
     return -100;
   }
-  VSA_HIP(hipMemsetAsync(counts.p, 0, g.nbuckets * 4, stream));
+  uint64_t *w = words.as<uint64_t>();
+  unsigned int *flag = reinterpret_cast<unsigned int *>(w);
+  unsigned long long *bcarry = reinterpret_cast<unsigned long long *>(w + 2);
+  uint64_t *bsurv = w + 2 + nb, *blen = w + 2 + 2 * nb;
+  uint32_t *counts = reinterpret_cast<uint32_t *>(w + 2 + 3 * nb);
+  uint64_t *off = w + zeroed, *lenscan = off + nb + 1;
+  VSA_HIP(hipMemsetAsync(w, 0, zeroed * 8, stream));
   // cursor regions in groups of about a tile's worth of candidates
   CsTiles t = CsTiles();
   uint64_t nwg = 0;
@@ -584,18 +833,21 @@ int candidate_bucketsort(const CsSources &src, uint64_t ncand,
   {
     nwg += (src.first.nq + VSA_CS_TILE - 1) / VSA_CS_TILE;
   }
-  const dim3 sg = vsa_grid(nwg), bg = vsa_grid(g.nbuckets);
+  const dim3 sg = vsa_grid(nwg), bg = vsa_grid(nb);
   auto run = [&](auto sm) {
     using F = CsForm<VAL, decltype(sm)::value>;
     using Entry = typename F::Entry;
     k_cs_scatter<VAL, decltype(sm)::value>
-        <<<sg, VSA_CS_SCATTER_BLOCK, g.nbuckets * 4, stream>>>(
-            src, t, g, counts.as<uint32_t>(), staging.as<Entry>());
-    k_cs_scan<<<1, VSA_BLOCK, 0, stream>>>(counts.as<uint32_t>(), g.nbuckets,
-                                           starts.as<uint64_t>(), flag);
-    k_cs_sort<VAL, decltype(sm)::value><<<bg, VSA_BLOCK, 0, stream>>>(
-        staging.as<Entry>(), counts.as<uint32_t>(), starts.as<uint64_t>(),
-        flag, g, ncand, k2, v2);
+        <<<sg, VSA_CS_SCATTER_BLOCK, nb * 4, stream>>>(
+            src, t, g, counts, bcarry, staging.as<Entry>());
+    k_cs_filter<VAL, decltype(sm)::value><<<bg, VSA_BLOCK, 0, stream>>>(
+        staging.as<Entry>(), counts, bcarry, flag, g, carry, bsurv, blen);
+    // (offsets of the buckets and, in a second workgroup, the sum of the
+    // lengths)
+    k_mumf_scan<0><<<2, VSA_BLOCK, 0, stream>>>(bsurv, nb, 0, off, blen,
+                                                lenscan);
+    k_cs_write<VAL, decltype(sm)::value><<<bg, VSA_BLOCK, 0, stream>>>(
+        staging.as<Entry>(), bsurv, off, g, ncand, write, out);
   };
   if constexpr (sizeof(VAL) == 4)
   {
@@ -611,6 +863,11 @@ int candidate_bucketsort(const CsSources &src, uint64_t ncand,
     run(std::false_type());
   }
   VSA_HIP(hipGetLastError());
+  const Fetch f[3] = {{off + nb, 8}, {lenscan + nb, 8}, {flag, 8}};
+  if (fetchwords(stream, f, 3, got))
+  {
+    return -100;
+  }
   *used = g;
   return 0;
 }

@@ -19,17 +19,18 @@
 //   candidate_sort.inc   K4s candidates as (sort key, value) pairs thrown
 //                            into buckets by the high bits of dbstart from
 //                            where they were produced, every bucket sorted
-//                            in LDS (short or concentrated lists: compaction
-//                            and rocPRIM's radix sort)
+//                            and filtered in LDS by K4's rule, the survivors
+//                            written as records in order (short or
+//                            concentrated lists: compaction, rocPRIM's radix
+//                            sort and K4)
 //   mum_filter.inc       K4  one filter on sorted (key, value) pairs, in
 //                            tiles: running maximum of the right ends, flags
 //                            from the keys, survivors written as records in
-//                            order (kurtz/cleanMUMcand.c:55-118).  Three
-//                            sorters in front of it: the bucket sort and
-//                            rocPRIM on dbstart alone (runs of equal dbstarts
-//                            looked at as runs), rocPRIM on all bits (a run
-//                            too long for that; candidate records, as
-//                            composite key + index)
+//                            order (kurtz/cleanMUMcand.c:55-118).  Two
+//                            sorts in front of it: rocPRIM on dbstart alone
+//                            (runs of equal dbstarts looked at as runs),
+//                            rocPRIM on all bits (a run too long for that;
+//                            candidate records, as composite key + index)
 // The other families have translation units of their own since round 4:
 //   selfmum_search.hip       K3, the scan over an index that holds its queries
 //   approx_entry.hip         -complete -e/-h (approx_search.inc, approx_tree.inc)
@@ -278,11 +279,11 @@ k_mum_compositekeys(const vsa_match *__restrict__ cand, uint64_t n,
   }
 }
 
-// ---- K4: three sorters, one filter (mum_filter.inc) ----
+// ---- K4: rocPRIM's sort, one filter (mum_filter.inc) ----
 
-// What a sorter fills and the filter reads: the pairs in dbstart order, the
-// flag word both may raise (device; bit 0: a run was too long for the filter
-// by runs, VSA_CS_OVERFLOW: the bucket sort gave up), the filter's tiles
+// What the sorter fills and the filter reads: the pairs in dbstart order, the
+// flag word (device; bit 0: a run was too long for the filter by runs), the
+// filter's tiles
 struct SortedPairs
 {
   DevBuf k2, v2, flag, keep, tmax, tcarry, tcount, toff, tsum, tsumscan;
@@ -1160,8 +1161,8 @@ bool feedsbuckets(const QueryRun &st)
   return true;
 }
 
-// MUMs of a packed run through the bucket sort and the filter by runs;
-// c->flags != 0: the list has to go through compact() and rocPRIM
+// MUMs of a packed run through the buckets, sorted and filtered by runs
+// there; c->flags != 0: the list has to go through compact() and rocPRIM
 template <typename VAL>
 int mumfilter_buckets(QueryRun &st, DevBuf &mums, MumCounts *c)
 {
@@ -1183,26 +1184,27 @@ int mumfilter_buckets(QueryRun &st, DevBuf &mums, MumCounts *c)
     src.first = {st.wfmlen.as<uint32_t>(), st.wfmdb.as<uint64_t>(),
                  st.queries->nq, st.qs.seqoffset, rec.packbits, rec.valbits};
   }
-  SortedPairs s;
   CsGeometry g;
-  if (s.alloc(total, sizeof(VAL), mums))
+  if (mums.alloc(total * sizeof(vsa_match)))
   {
     return -100;
   }
-  VSA_HIP(hipMemsetAsync(s.flag.p, 0, 8, st.stream));
-  if (candidate_bucketsort<VAL>(src, total, st.index->n, rec.lenbits,
-                                rec.dbbits, s.k2.as<uint64_t>(),
-                                s.v2.as<VAL>(), s.flag.as<unsigned int>(),
-                                st.stream, &g))
+  const PairRecord<VAL> pr = {rec.lenbits, rec.valbits,
+                              sizeof(VAL) == 4 ? st.qs.seqoffset : 0};
+  uint64_t got[3];
+  if (candidate_bucketfilter<VAL>(src, total, st.index->n, rec.lenbits,
+                                  rec.dbbits, 0, pr, st.stream,
+                                  mums.as<vsa_match>(), got, &g))
   {
     return -100;
   }
   g_cs_runs++;
   g_cs_shift = g.shift;
   g_cs_buckets = g.nbuckets;
-  const PairRecord<VAL> pr = {rec.lenbits, rec.valbits,
-                              sizeof(VAL) == 4 ? st.qs.seqoffset : 0};
-  return mumfilter_tiles<false>(s, rec.lenbits, 0, pr, st.stream, mums, c);
+  c->nmums = got[0];
+  c->sumlength = got[1];
+  c->flags = got[2];
+  return 0;
 }
 
 // the dense list into the result: the pairs themselves, the MUMs behind the

@@ -9,7 +9,7 @@
 // right end in front of a candidate (carry = its value in front of the list),
 // candidate i survives iff it is not covered (dbright < its right end) and no
 // other candidate with its dbstart is at least as long.  The keys arrive
-//   sorted by dbstart ALONE (the bucket sort, or one radix pass saved): the
+//   sorted by dbstart ALONE (one radix pass saved): the
 //     reference's order inside a run of equal dbstarts is "longest first", and
 //     of such a run only the longest can survive, and only if no other member
 //     is as long (the others find dbright at or beyond their right end).  That
@@ -31,6 +31,14 @@
 // are touched only there.  (Until round 3: rocPRIM max-scan, flags, rocPRIM
 // sum-scan, writer, reduce -- 0.3 ms for 11.6 M candidates, each pass paying
 // its launch and a look-back chain over thousands of workgroups.)
+//
+// The bucket path (candidate_sort.inc) does not come through these tiles
+// since round 12: k_cs_filter applies the rule of k_mumf_flags<false> to a
+// bucket where its sort left it in LDS -- the running maximum in front of a
+// bucket is what the scatter found reaching into it -- and k_mumf_scan<0>
+// turns its survivors per bucket into offsets as it does for tiles.  Whoever
+// changes the rule changes it there as well; tests/test_gpu_bucket_filter.py
+// and test_gpu_candidate_sort.py hold both to the oracle's list.
 //
 // At the end of the file: the three kernels of the wide form, for records
 // whose dbstart and length do not fit into one key.
