@@ -523,6 +523,7 @@ extern "C" int vsa_index_clone(const vsa_index *src, int device,
   ix->device_bytes = src->device_bytes;
   ix->D = src->D;
   ix->tune = src->tune;
+  ix->walkshift = src->walkshift;
   ix->qspeedup = src->qspeedup;
   ix->slotwords = src->slotwords;
   ix->firstspecial = src->firstspecial;

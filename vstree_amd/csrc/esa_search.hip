@@ -57,7 +57,13 @@
 //   VSA_TUNE=8        ... by the bucket sort whatever their number (tests on
 //                     small texts; by default lists below VSA_CS_MINPAIRS
 //                     take rocPRIM)
-//                     (a bit mask: 2, 4 and 8 combine)
+//   VSA_TUNE=16       no walk in the planned MUM search: every planned offset
+//                     is located, one per work-item (A/B and cross-check of
+//                     the walk, mum_workplan.inc)
+//                     (a bit mask: 2, 4, 8 and 16 combine)
+//   VSA_WALK_CHUNK=N  offsets of a plan range that one lane walks (a power of
+//                     two, else the next one below; default 32; 1 is
+//                     VSA_TUNE=16)
 //   VSA_NO_ESA8=1     no deep tables: the reference walk, probe for probe
 //   VSA_DEEP_PREFIX=D their depth (default ceil(log4 n), at most 16)
 //   VSA_FORCE_WIDE=1  64-bit device tables whatever the size of the text
@@ -641,6 +647,7 @@ struct QueryRun
   // the search kernel's cursor regions, and the dense list behind them
   DevBuf cursor, doff, summary, blocksum, rtemp, rawout, rawkeys, out, keys;
   uint64_t shardcap = 0, needed = 0, nplan = 0, nfirst = 0, plannedwork = 0;
+  uint64_t plannedlocates = 0; // of plannedwork offsets: located by the walk
   double searchms = 0;
 
   QueryRun(const vsa_index *ix, const vsa_queries *q, bool mum, bool cand,
@@ -968,7 +975,8 @@ void launch_search(QueryRun &st, const DevIndex<IDX> &ix,
               st.rawout.as<vsa_match>(), st.rawkeys.as<uint64_t>(),
               st.shardcap, VSA_CURSOR_SHARDS - 1,
               st.cursor.as<unsigned long long>(), st.rec.packbits,
-              st.rec.valbits, st.blocksum.as<unsigned long long>());
+              st.rec.valbits, st.blocksum.as<PlannedWork>(),
+              st.index->walkshift);
     };
     auto unplanned = [&](auto mum) {
       k_query_search<IDX, mum, deep, 256>
@@ -1007,28 +1015,32 @@ template <typename IDX>
 int search(QueryRun &st, const DevIndex<IDX> &ix)
 {
   const uint32_t nshards = VSA_CURSOR_SHARDS;
-  const uint64_t nplanblocks = (st.queries->nq + 255) / 256;
+  // (reads per workgroup of k_query_search_planned<IDX, 256>)
+  const uint64_t perblock = 256 * (st.domum ? VSA_WALK_READS : 1);
+  const uint64_t nplanblocks = (st.queries->nq + perblock - 1) / perblock;
   size_t rbytes = 0;
   if (st.fromplan)
   {
-    // the work-items of the planned search: summed per workgroup by the
-    // kernel, reduced behind it into the fifth word of the shard summary
-    if (st.blocksum.alloc((vsa_grid_blocks(nplanblocks) + 1) * 8))
+    // the work of the planned search (the locates it really makes -- the
+    // walk leaves planned offsets out -- and the offsets planned): summed per
+    // workgroup by the kernel, reduced behind it into the fifth and sixth
+    // word of the shard summary
+    if (st.blocksum.alloc((vsa_grid_blocks(nplanblocks) + 1) *
+                          sizeof(PlannedWork)))
     {
       return -100;
     }
-    VSA_HIP(rocprim::reduce(nullptr, rbytes,
-                            st.blocksum.as<unsigned long long>(),
-                            (unsigned long long *) nullptr, 0ull,
-                            (size_t) nplanblocks,
-                            rocprim::plus<unsigned long long>(), st.stream));
+    VSA_HIP(rocprim::reduce(nullptr, rbytes, st.blocksum.as<PlannedWork>(),
+                            (PlannedWork *) nullptr, PlannedWork{0, 0},
+                            (size_t) nplanblocks, PlannedWorkPlus(),
+                            st.stream));
     if (st.rtemp.alloc(rbytes))
     {
       return -100;
     }
   }
   if (st.cursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
-      st.doff.alloc(nshards * 8) || st.summary.alloc(5 * 8))
+      st.doff.alloc(nshards * 8) || st.summary.alloc(6 * 8))
   {
     return -100;
   }
@@ -1051,22 +1063,24 @@ int search(QueryRun &st, const DevIndex<IDX> &ix)
     VSA_HIP(hipGetLastError());
     if (st.fromplan)
     {
-      VSA_HIP(rocprim::reduce(st.rtemp.p, rbytes,
-                              st.blocksum.as<unsigned long long>(),
-                              st.summary.as<unsigned long long>() + 4, 0ull,
-                              (size_t) nplanblocks,
-                              rocprim::plus<unsigned long long>(), st.stream));
+      // (words 4 and 5 of the summary: 16-byte aligned)
+      VSA_HIP(rocprim::reduce(
+          st.rtemp.p, rbytes, st.blocksum.as<PlannedWork>(),
+          reinterpret_cast<PlannedWork *>(st.summary.as<uint64_t>() + 4),
+          PlannedWork{0, 0}, (size_t) nplanblocks, PlannedWorkPlus(),
+          st.stream));
     }
     // where each region goes in the dense list, how much there is
     const uint64_t *sm = st.summary.as<uint64_t>();
     VSA_HIP(shard_summary(st.cursor.as<unsigned long long>(), nshards,
                           st.doff.as<uint64_t>(), st.summary.as<uint64_t>(),
                           st.stream));
-    const Fetch f[7] = {{sm, 8}, {sm + 1, 8}, {sm + 2, 8}, {sm + 3, 8},
+    const Fetch f[8] = {{sm, 8}, {sm + 1, 8}, {sm + 2, 8}, {sm + 3, 8},
                         {sm + 4, 8}, {st.planemit ? st.psummary.p : sm, 8},
-                        {st.nlistword != nullptr ? st.nlistword : sm, 8}};
-    uint64_t got[7];
-    if (fetchwords(st.stream, f, 7, got))
+                        {st.nlistword != nullptr ? st.nlistword : sm, 8},
+                        {sm + 5, 8}};
+    uint64_t got[8];
+    if (fetchwords(st.stream, f, 8, got))
     {
       return -100;
     }
@@ -1078,7 +1092,8 @@ int search(QueryRun &st, const DevIndex<IDX> &ix)
     st.nplan = st.planemit ? got[5] : 0;
     st.needed = got[0];
     maxshard = got[1];
-    st.plannedwork = st.fromplan ? got[4] : 0;
+    st.plannedlocates = st.fromplan ? got[4] : 0;
+    st.plannedwork = st.fromplan ? got[7] : 0;
     st.searchms += st.tsearch.ms();
     if (maxshard <= st.shardcap)
     {
@@ -1359,7 +1374,9 @@ int run_query(const vsa_index *index, const vsa_queries *queries, bool domum,
   res->stats.search_kernel_ms = st.searchms;
   res->stats.anchor_ms = 0; // (the anchor pass of round 1 is gone)
   res->stats.first_kernel_ms = st.tfirst.ms();
-  res->stats.kernel_searches = st.fromplan ? st.plannedwork : st.nitems;
+  // (searches: the offsets the plans hold, whatever the walk leaves out of
+  // them; kernel_searches: the locates the search kernel really made)
+  res->stats.kernel_searches = st.fromplan ? st.plannedlocates : st.nitems;
   if (st.fromplan)
   {
     res->stats.searches = st.plannedwork + queries->nq + st.plansearches;

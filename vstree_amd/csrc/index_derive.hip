@@ -125,6 +125,29 @@ k_make_slots(const IDX *__restrict__ bck2, const uint64_t *__restrict__ esa8,
 int vsa_index_make_esa8(vsa_index *ix)
 {
   const char *off = getenv("VSA_NO_ESA8");
+  {
+    // the switches (they hold with and without deep tables, so they are read
+    // in front of everything that can return), and the walk of the planned
+    // MUM search: log2 of the offsets per chunk; VSA_TUNE & 16: no walk, one
+    // offset per work-item
+    const char *tn = getenv("VSA_TUNE"), *wc = getenv("VSA_WALK_CHUNK");
+    const int asked = wc != nullptr ? atoi(wc) : 0;
+    ix->tune = tn != nullptr ? (uint32_t) atoi(tn) : 0;
+    uint32_t chunk = VSA_WALK_CHUNK;
+    if (asked >= 1 && asked <= 0x8000)
+    {
+      chunk = (uint32_t) asked;
+    }
+    if ((ix->tune & 16u) != 0)
+    {
+      chunk = 1;
+    }
+    ix->walkshift = 0;
+    while ((2u << ix->walkshift) <= chunk) // (rounded down to a power of two)
+    {
+      ix->walkshift++;
+    }
+  }
   if (ix->esa8 != nullptr)
   {
     (void) hipFree(ix->esa8);
@@ -208,8 +231,6 @@ int vsa_index_make_esa8(vsa_index *ix)
   }
   static_assert(VSA_TIS_BACKPAD >= 16 + VSA_KEYSYMS + 8, "text pad too small");
   ix->D = D;
-  const char *tune = getenv("VSA_TUNE");
-  ix->tune = tune != nullptr ? (uint32_t) atoi(tune) : 0;
   const uint64_t count = ix->n + 1, ncodes = 1ull << (2 * D);
   // The slot table is the one every search starts in, at a random place: it is
   // allocated FIRST, with the temporaries of the builder handed back to the

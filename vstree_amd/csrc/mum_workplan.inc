@@ -380,10 +380,45 @@ k_mum_plan(const DevIndex<IDX> ix, const DevQueries qs,
 }
 
 
+#include "mum_walk.inc"
+
+// what a workgroup of k_query_search_planned did: the locates it made
+// (stats.kernel_searches) and the offsets of its plans (the planned term of
+// stats.searches, which counts the work the plan asked for and does not
+// depend on how the search kernel goes through it)
+struct PlannedWork
+{
+  unsigned long long locates, offsets;
+};
+struct PlannedWorkPlus
+{
+  __host__ __device__ PlannedWork operator()(const PlannedWork &a,
+                                             const PlannedWork &b) const
+  {
+    return PlannedWork{a.locates + b.locates, a.offsets + b.offsets};
+  }
+};
+
 // 8 wavefronts per SIMD (64 VGPRs, no scratch; the compiler takes 75 when
 // left alone: 1.50-1.55 against 1.57 ms)
 #ifndef VSA_P1_WAVES
 #define VSA_P1_WAVES 8
+#endif
+// The MUM forms carry the walk's state (chunk, offset, read) around the
+// locate and, on packed batches, a second copy of the walk for the reads with
+// a special symbol: 74 to 76 VGPRs.  Held to 64 they spill 10 to 13 VGPRs to
+// scratch (40 to 56 bytes per lane), at 7 wavefronts (72 VGPRs) the packed
+// form still spills 20 bytes: 6 wavefronts per SIMD, no scratch.
+#ifndef VSA_WALK_WAVES
+#define VSA_WALK_WAVES 6
+#endif
+// Reads per lane of a workgroup of the MUM forms.  A quarter of the headline's
+// reads has a plan, of one range that is one chunk: with BLK reads per
+// workgroup one wavefront of four walked and the others waited for it at the
+// barrier (3.70 ms per step against the parent's 2.90, profiles/r13).  Four
+// reads per lane fill the workgroup.
+#ifndef VSA_WALK_READS
+#define VSA_WALK_READS 4
 #endif
 // K2 for a planned MUM batch, straight from the plans: a workgroup takes BLK
 // consecutive queries, lays their planned offsets out in LDS (a scan of the
@@ -392,15 +427,38 @@ k_mum_plan(const DevIndex<IDX> ix, const DevQueries qs,
 // read back in round 1), no scan over all queries, no host round trip before
 // the launch.  Per work-item exactly what k_query_search<IDX, MUM, DEEP> does
 // (same device functions, same output form, same sort key).
-// blocksum[workgroup] = its work-items.  DEEP = false: indexes without the
-// deep tables (other alphabets, VSA_NO_ESA8): the reference walk per item.
+// blocksum[workgroup] = the locates it made and the offsets its plans hold
+// (PlannedWork).  DEEP = false: indexes without the deep tables (other
+// alphabets, VSA_NO_ESA8): the reference walk per item.
+//
+// The walk (MUM = true).  A work-item is a chunk of a plan range, at most
+// 1 << chunkshift offsets, walked by one lane from its last offset down.
+// e(j) never decreases with j (above), so once offset h is located every
+// j < h has a longest match of at most e(h) - j, and a candidate needs
+// searchlength symbols: the offsets j with e(h) - searchlength < j < h are no
+// candidates and are not located.  The lane goes on at
+// min(h - 1, h + U - searchlength), U an UPPER bound of the longest match at h:
+//   VSA_LOC_FOUND              maxlcp (exact), or no bound at all where the
+//                              locate was cut short (hit.notleftmax: maxlcp
+//                              is a lower bound, only h itself is done)
+//   VSA_LOC_NONE               D - 1: nothing shares D symbols
+//   the reference walk         maxlcp (exact), or prefixlength - 1 without a
+//                              bucket
+// A random 20-mer matches log4 n symbols, 15 to 17 in a 3 Gbp text: a locate
+// disposes of about five offsets of a range behind a substitution.  Every
+// located offset takes the candidate test and the output form of the
+// one-offset-per-work-item kernel, so the lists do not change; a chunk makes at
+// most as many locates as it has offsets.  chunkshift = 0 (VSA_TUNE=16) is
+// that kernel: every planned offset located.
+// The deep locate wants all lanes of a wavefront: the walk is a loop with a
+// wavefront-uniform exit, finished lanes pass active = false.
 // ROWS (DEEP, packed batches): a work-item takes its read from the row (two
 // 16-byte loads, the neighbouring offsets of a read share them).
 // MUM = false (byte batches): the planned offsets of a MEM batch
 // (mem_workplan.inc), each through vsa_query_item<MEM>.
 template <typename IDX, int BLK, bool DEEP = true, bool ROWS = false,
           bool MUM = true>
-__global__ void __launch_bounds__(BLK, VSA_P1_WAVES)
+__global__ void __launch_bounds__(BLK, MUM ? VSA_WALK_WAVES : VSA_P1_WAVES)
 k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
                        const uint64_t *__restrict__ base, uint32_t perquery,
                        const PlanRanges *__restrict__ plan,
@@ -410,12 +468,21 @@ k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
                        uint32_t shardmask,
                        unsigned long long *__restrict__ cursors,
                        uint32_t packbits, uint32_t valbits,
-                       unsigned long long *__restrict__ blocksum)
+                       PlannedWork *__restrict__ blocksum,
+                       uint32_t chunkshift = 0)
 {
-  __shared__ uint32_t rel[BLK + 1];
-  __shared__ PlanRanges pr[BLK];
-  const uint64_t q0 = vsa_bid() * BLK;
+  // reads per lane and per workgroup (see VSA_WALK_READS)
+  constexpr int RPT = MUM ? VSA_WALK_READS : 1, RPB = BLK * RPT;
+  __shared__ uint32_t rel[RPB + 1];
+  __shared__ PlanRanges pr[RPB];
+  // (the MUM forms only)
+  __shared__ uint64_t lanesum[MUM ? BLK + 1 : 1];
+  __shared__ uint32_t wavelocates[MUM ? BLK / 64 : 1];
+  const uint64_t q0 = vsa_bid() * RPB;
   const uint32_t tid = threadIdx.x;
+  // (the MEM plan: one offset per work-item)
+  const uint32_t cshift = MUM ? chunkshift : 0, chunk = 1u << cshift;
+  if constexpr (!MUM)
   {
     const bool in = q0 + tid < qs.nq;
     const uint32_t mine = in ? plancount[q0 + tid] : 0;
@@ -437,26 +504,85 @@ k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
       rel[tid + 1] += v;
       __syncthreads();
     }
+  } else
+  {
+    // the counts of RPT consecutive reads per lane, chunks instead of
+    // offsets, summed up as they come; the planned offsets ride along in the
+    // upper half of the lanes' sums (a workgroup plans fewer than 2^32, no
+    // carry) -- summed in registers and by shuffles they cost the packed form
+    // 24 bytes of scratch per lane
+    uint32_t mine[RPT], sum = 0, offsets = 0;
+#pragma unroll
+    for (int k = 0; k < RPT; k++)
+    {
+      const uint64_t q = q0 + tid * RPT + k;
+      uint32_t c = q < qs.nq ? plancount[q] : 0;
+      offsets += c;
+      if (q < qs.nq)
+      {
+        const PlanRanges p = plan[q];
+        pr[tid * RPT + k] = p;
+        if (c > 0)
+        {
+          c = 0;
+#pragma unroll
+          for (int g = 0; g < VSA_PLAN_RANGES; g++)
+          {
+            c += ((p.r[g] >> 16) + chunk - 1) >> cshift;
+          }
+        }
+      }
+      sum += c;
+      mine[k] = sum;
+    }
+    // exclusive scan of the lanes' sums
+    lanesum[tid + 1] = sum | ((uint64_t) offsets << 32);
+    if (tid == 0)
+    {
+      lanesum[0] = 0;
+      rel[0] = 0;
+    }
+    __syncthreads();
+    for (uint32_t d = 1; d < BLK; d <<= 1)
+    {
+      const uint64_t v = (tid + 1 > d) ? lanesum[tid + 1 - d] : 0;
+      __syncthreads();
+      lanesum[tid + 1] += v;
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < RPT; k++)
+    {
+      rel[tid * RPT + k + 1] = (uint32_t) lanesum[tid] + mine[k];
+    }
+    __syncthreads();
   }
-  const uint32_t total = rel[BLK];
+  const uint32_t total = rel[RPB];
   if (tid == 0)
   {
-    blocksum[vsa_bid()] = total;
+    // (MUM: the locates follow at the end)
+    if constexpr (MUM)
+    {
+      blocksum[vsa_bid()].offsets = lanesum[BLK] >> 32;
+    } else
+    {
+      blocksum[vsa_bid()] = PlannedWork{total, total};
+    }
   }
   const uint32_t shard = vsa_bid() & shardmask;
+  uint32_t locates = 0; // of this lane
   for (uint32_t i0 = 0; i0 < total; i0 += BLK)
   {
     const uint32_t i = i0 + tid;
-    const bool active = i < total;
-    uint32_t c = 0, maxlcp = 0, off = 0, remaining = 0;
-    uint64_t witness = 0, q = 0, t = 0;
-    uint8_t leftchar = (uint8_t) VSA_SEPARATOR;
-    const uint8_t *qptr = qs.symbols;
-    bool have = false, fast = false;
+    bool active = i < total;
+    // MUM: the chunk is [first, off], off comes down as the walk goes
+    uint32_t off = 0, first = 0, qlen = qs.uniformlen;
+    uint64_t q = 0, t0 = 0;
+    const uint8_t *qstart = qs.symbols;
     if (active)
     {
       // the query whose stretch holds item i: last k with rel[k] <= i
-      uint32_t lo = 0, hi = BLK;
+      uint32_t lo = 0, hi = RPB;
       while (hi - lo > 1)
       {
         const uint32_t mid = (lo + hi) >> 1;
@@ -468,60 +594,57 @@ k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
           hi = mid;
         }
       }
+      // its chunk: the r-th of the read's ranges, each cut from its first
+      // offset on
       uint32_t r = i - rel[lo];
 #pragma unroll
       for (int k = 0; k < VSA_PLAN_RANGES; k++)
       {
-        const uint32_t first = pr[lo].r[k] & 0xFFFFu, len = pr[lo].r[k] >> 16;
-        if (r < len)
+        const uint32_t rf = pr[lo].r[k] & 0xFFFFu, len = pr[lo].r[k] >> 16,
+                       nchunks = (len + chunk - 1) >> cshift;
+        if (r < nchunks)
         {
-          off = first + r;
+          const uint32_t at = r << cshift,
+                         n = len - at < chunk ? len - at : chunk;
+          first = rf + at;
+          off = first + n - 1;
           r = 0xFFFFFFFFu; // found: no later range takes it
         } else if (r != 0xFFFFFFFFu)
         {
-          r -= len;
+          r -= nchunks;
         }
       }
       q = q0 + lo;
-      t = ((base != nullptr) ? base[q] : q * perquery) + off;
       if constexpr (!MUM)
       {
-        // (vsa_query_item finds the symbols itself)
-      } else if constexpr (ROWS)
-      {
-        remaining = qs.uniformlen - off;
-      } else
+        t0 = (base != nullptr) ? base[q] : q * perquery;
+      }
+      if constexpr (MUM && !ROWS)
       {
         if (qs.dense)
         {
-          qptr = qs.symbols + q * qs.uniformlen + off;
-          remaining = qs.uniformlen - off;
+          qstart = qs.symbols + q * qs.uniformlen;
         } else
         {
-          qptr = qs.symbols + qs.start[q] + off;
-          remaining = (uint32_t) qs.length[q] - off;
-        }
-        if (off > 0)
-        {
-          leftchar = qptr[-1];
+          qstart = qs.symbols + qs.start[q];
+          qlen = (uint32_t) qs.length[q];
         }
       }
     }
     if constexpr (!MUM)
     {
-      vsa_query_item<IDX, false, DEEP>(ix, qs, active, q, off, t,
+      // (vsa_query_item finds the symbols itself)
+      vsa_query_item<IDX, false, DEEP>(ix, qs, active, q, off, t0 + off,
                                        searchlength, out, outkey, shardcap,
                                        shard, cursors, 0, 0);
       continue;
     }
-    DeepHit hit;
-    int st = VSA_LOC_SLOW;
-    RowQuery rq;
-    QSrc src;
     if constexpr (DEEP && ROWS)
     {
-      // windows of the row (one 16-byte load each); a read with a special
-      // symbol takes the reference walk on its bytes
+      // windows of the row; a read with a special symbol (rare) is walked on
+      // its bytes behind the others, as the byte form walks it
+      RowQuery rq;
+      QSrc src;
       bool flagged = false;
       rq.row = qs.rows;
       rq.valid = 0;
@@ -531,76 +654,48 @@ k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
       if (active)
       {
         flagged = vsa_row_of(qs, q, qs.uniformlen, rq, src);
-        if (off > 0)
-        {
-          leftchar = flagged ? src.bytes[off - 1]
-                             : (uint8_t) (vsa_pq_window(rq, off - 1) >> 62);
-        }
-        src.pos = (int32_t) off;
       }
-      const uint32_t qleft = off > 0 ? (uint32_t) leftchar : 0x100u;
-      st = vsa_locate_deep<1, true>(ix, active && !flagged, src, remaining,
-                                    maxlcp, witness, hit, searchlength, qleft,
-                                    &rq, off);
-      if (active && flagged)
+      locates += vsa_walk_chunk<IDX, true, true>(
+          ix, qs, active && !flagged, src, &rq, qlen, first, off, q, base,
+          perquery, searchlength, out, outkey, shardcap, shard, cursors,
+          packbits, valbits);
+      if (__any(active && flagged))
       {
-        st = VSA_LOC_SLOW; // (rare: the reference walk on the read's bytes)
-      }
-    } else if constexpr (DEEP)
-    {
-      st = vsa_locate_deep(ix, active, qptr, remaining, maxlcp, witness, hit,
-                           searchlength,
-                           off > 0 ? (uint32_t) leftchar : 0x100u);
-    }
-    if (st == VSA_LOC_SLOW)
-    {
-      if constexpr (DEEP && ROWS)
-      {
-        have = active &&
-               vsa_locate_reference(ix, src, remaining, maxlcp, witness);
-      } else
-      {
-        have = active &&
-               vsa_locate_reference(ix, qptr, remaining, maxlcp, witness);
+        locates += vsa_walk_chunk<IDX, true, false>(
+            ix, qs, active && flagged, src, nullptr, qlen, first, off, q, base,
+            perquery, searchlength, out, outkey, shardcap, shard, cursors,
+            packbits, valbits);
       }
     } else
     {
-      have = st == VSA_LOC_FOUND;
-      fast = have && maxlcp < 255;
+      locates += vsa_walk_chunk<IDX, DEEP, false>(
+          ix, qs, active, qstart, nullptr, qlen, first, off, q, base, perquery,
+          searchlength, out, outkey, shardcap, shard, cursors, packbits,
+          valbits);
     }
-    // (a work-item none of whose matches can be left maximal was cut short
-    // by the locate: hit.notleftmax, maxlcp is only a lower bound then)
-    if (have && maxlcp >= searchlength &&
-        !(st != VSA_LOC_SLOW && hit.notleftmax))
+  }
+  if constexpr (MUM)
+  {
+    // blocksum[workgroup] = the locates of its lanes, its planned offsets
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
     {
-      if (fast)
+      locates += __shfl_xor(locates, d, 64);
+    }
+    if ((tid & 63u) == 0)
+    {
+      wavelocates[tid >> 6] = locates;
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+      uint32_t s = 0;
+#pragma unroll
+      for (int w = 0; w < BLK / 64; w++)
       {
-        // leftrightmaximaluniquematch (fquery.c:297-386) and PROCESSSUFFIX
-        // (fquery.c:54-81) on values already in registers
-        // (suffix 0 has the separator of the front pad as hit.leftsym)
-        const uint32_t lcpw = (uint32_t) (hit.ew >> 32) & 0xFFu;
-        const bool unique = (witness == 0 || lcpw < maxlcp) &&
-                            (witness + 1 > ix.n - 1 || hit.lcpnext < maxlcp);
-        c = (unique && (VSA_ISSPECIAL(leftchar) || leftchar != hit.leftsym))
-                ? 1u
-                : 0u;
-      } else
-      {
-        c = (vsa_mum_candidate<IDX, DEEP>(ix, maxlcp, witness) &&
-             vsa_leftmaximal(ix, vsa_sufstart<IDX, DEEP>(ix, witness),
-                             leftchar))
-                ? 1u
-                : 0u;
+        s += wavelocates[w];
       }
-    }
-    const uint64_t inshard = vsa_wave_reserve01(
-        cursors + (uint64_t) shard * VSA_CURSOR_STRIDE, c != 0);
-    if (c != 0 && inshard < shardcap)
-    {
-      const uint64_t dbstart = fast ? vsa_entrystart(ix, hit.ew, witness)
-                                    : vsa_sufstart<IDX, DEEP>(ix, witness);
-      vsa_write_candidate(qs, out, outkey, (uint64_t) shard * shardcap + inshard,
-                          q, off, t, dbstart, maxlcp, packbits, valbits);
+      blocksum[vsa_bid()].locates = s;
     }
   }
 }

@@ -93,6 +93,18 @@ struct DevIndex
 #define VSA_KEYFLAG (1ull << 62)
 #define VSA_LEFTSPECIAL (1ull << 63) // ... is not a regular one / does not exist
 
+// offsets of a plan range that one lane of the planned MUM search walks (a
+// power of two; mum_workplan.inc).  Headline, ms per step, one run each: 2.66 /
+// 2.50 / 2.57 / 2.72 / 2.60 at 2 / 4 / 8 / 16 / 32 against the parent's 2.88 to
+// 2.91.  Chunks of 4 are the fastest there,
+// but on reads from repeats, where a lane can skip nothing and a wavefront
+// goes round once per offset of its longest chunk, they are 11 % SLOWER than
+// no walk at all (7.12 against 6.39-6.43 ms per call); whole ranges in one
+// chunk are faster than no walk on both inputs (6.00 there): 32.
+#ifndef VSA_WALK_CHUNK
+#define VSA_WALK_CHUNK 32
+#endif
+
 struct vsa_index
 {
   int device;
@@ -110,6 +122,9 @@ struct vsa_index
   uint8_t *tis2, *spec64; // see DevIndex (may be nullptr)
   uint64_t firstspecial;
   uint32_t D, tune;
+  // log2 of the offsets one lane of the planned MUM search walks
+  // (VSA_WALK_CHUNK, VSA_TUNE & 16: esa_search.hip, mum_workplan.inc)
+  uint32_t walkshift;
   uint32_t qspeedup; // vsa_index_set_queryspeedup: 0 or 2 (default)
   uint64_t querysepposition;
   int hasindexedqueries;
