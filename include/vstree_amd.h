@@ -758,6 +758,23 @@ int vsa_measure_table_read(const vsa_index *ix, int table, int inflight,
 #define VSA_SINK_SELF           2 /* vsa_findmaximaluniquematches         */
 #define VSA_SINK_APPROX_EDIST   3 /* vsa_findapproxcompletematches, -e    */
 #define VSA_SINK_APPROX_HAMMING 4 /* vsa_findapproxcompletematches, -h    */
+/* vmatch -dnavsprot: records as the engine delivers them on a six-frame
+   batch (vsa_queries_translate; queryseq counts the six frames of every DNA
+   sequence, without an offset), the index a protein index.  numofqueries,
+   querystart, querylength and querytotallength describe the DNA Multiseq,
+   numofchars is the protein alphabet's.  Every record is converted
+   (sixframeconvertmatch, Vmatch/procfinal.c:262-289) and printed with length2
+   = 3 * length, the forward-strand position in the DNA sequence and the flag
+   F (forward frame) or G (reverse frame) in place of D|P; E-value from the
+   multiplier totallength * length of the DNA sequence and lenmatch = length2
+   (procfinal.c:196-258), score = length1 + length2.  palindromic must be 0.
+   vsa_select_*, vsa_cluster_*, vsa_matchcluster_* and vsa_chain_* answer
+   VSA_NOT_COVERED for a layout of this kind.
+   VSA_SINK_TRANSLATED_COMPLETE: the same for the records of
+   vsa_findcompletematches on such a batch (-dnavsprot -complete), whose
+   E-value has the multiplier totallength alone, as for VSA_SINK_COMPLETE. */
+#define VSA_SINK_TRANSLATED     5
+#define VSA_SINK_TRANSLATED_COMPLETE 6
 
 /* Vmatch option -> bit of showmode (include/outinfo.h SHOW...) */
 #define VSA_SHOW_ABSOLUTE   1u /* -absolute   */
@@ -1595,6 +1612,110 @@ int64_t vsa_chain_format_host(vsa_sink *sink, int flags, uint64_t nchains,
    Vmatch/outinfo.h:93-98: 5, 6, 6, 3, 3) */
 int vsa_sink_setdigits(vsa_sink *sink, int length, int position1,
                        int position2, int seqnum1, int seqnum2);
+
+/* ---- DNA queries against a protein index in six reading frames: vmatch
+   -dnavsprot transnum -q Q PROTIDX (kurtz/sixframe.c:70-264,
+   kurtz/codon.c:292-999, Vmatch/procmatch.c:450-460,
+   Vmatch/procfinal.c:196-289; the rules: csrc/sixframe_rules.h) -------------
+
+   The translation reads the ORIGINAL CHARACTERS of the DNA sequences, not
+   mapped codes: a c g t u, the wildcards n s y w r k v b d h m, either case;
+   any other character in a sequence of three characters or more is the
+   reference's error "illegal char c0='X'(88)" (shorter sequences have no
+   codon and are not looked at).  DNA sequence s of len characters becomes
+   the sequences 6 s .. 6 s + 5 of a protein Multiseq: the forward frames f =
+   0, 1, 2 (codons at f, f + 3, ..: (len - f) / 3 symbols, 0 where len < f),
+   then the reverse frames r = 0, 1, 2 (codon k = the complemented characters
+   at len - 1 - r - 3 k and the two below it: (len - r) / 3 symbols).  Every
+   frame is followed by VSA_SEPARATOR except the last frame of the last
+   sequence, start[i] = markpos[i - 1] + 1; an empty frame is two adjacent
+   separators.  A wildcard in codon position 1 or 2 stands for the smallest
+   base of its set in the order T < C < A < G; in position 3 for the amino
+   acid all its bases agree on, else for its smallest base.  In the reverse
+   frames only the four plain bases are complemented, the set of a wildcard
+   is not, and W stands for {A, C}: the reference's rules, reproduced.  The
+   amino-acid character ('*' for a stop codon) goes through symbolmap, the
+   symbol map of the INDEX (character -> code; VSA_WILDCARD for its wildcard
+   class, VSA_UNDEFBWT for a character outside the alphabet).
+   Deviation: an amino acid whose code lies in [numofchars, 253] (numofchars
+   = the largest code below 253 of the map, plus 1) is an error (-2), the
+   contract of vsa_queries_from_host; the reference stores whatever its map
+   says.  It cannot happen under mkvtree -protein.
+   transnum: the NCBI tables 1-6, 9-16, 21-23. */
+
+/* 0, or -2 with the reference's message "illegal translation table number
+   N: must be number in the range [1,23] except for 7, 8, 17, 18, 19 and 20" */
+int vsa_transnum_check(uint32_t transnum);
+
+/* Host code, no GPU.  Sequence i = dnachars[start[i] .. start[i] +
+   length[i]).  protein takes the symbols (-3 if capacity is too small: sum
+   over the sequences of 2 (len / 3 + (len - 1) / 3 + (len - 2) / 3) + 6,
+   minus 1), pstart / plength (6 nq entries each) the frames, *nsymbols the
+   total.  On an error *nsymbols is 0 and the other outputs are undefined. */
+int vsa_translate_host(uint32_t transnum, const uint8_t *dnachars,
+                       uint64_t nchars, const uint64_t *start,
+                       const uint64_t *length, uint64_t nq,
+                       const uint8_t symbolmap[256], uint8_t *protein,
+                       uint64_t capacity, uint64_t *pstart, uint64_t *plength,
+                       uint64_t *nsymbols);
+
+/* The same translation on the GPU: an ordinary query batch of 6 nq sequences
+   in the layout above, for vsa_findquerymatches (-l L counts amino acids),
+   vsa_findcompletematches (which stops with "patternlength=0 must be >=
+   1=prefixlen" at the first frame shorter than the prefix length, as the
+   reference does) and the other engine calls.  The batch is ragged: it takes
+   the byte paths of the engine.  It keeps the DNA lengths on the device for
+   vsa_translated_convert.  vsa_queries_set_offset counts SIX-FRAME sequences
+   on it: a shard of reads that starts at read `first` sets 6 * first.
+   An error (illegal character, unmapped amino acid) leaves no batch behind.
+   _translate: ragged characters in host memory; _translate_device: nq reads
+   of m characters back to back in device memory (not modified, not kept). */
+int vsa_queries_translate(uint32_t transnum, const uint8_t *dnachars,
+                          uint64_t nchars, const uint64_t *start,
+                          const uint64_t *length, uint64_t nq,
+                          const uint8_t symbolmap[256], int device,
+                          vsa_queries **protein);
+int vsa_queries_translate_device(uint32_t transnum, const void *device_chars,
+                                 uint64_t nq, uint32_t m,
+                                 const uint8_t symbolmap[256], int device,
+                                 vsa_queries **protein);
+/* the symbols (numofsymbols of vsa_queries_getinfo) and the start / length
+   of every sequence (numofqueries each) of a batch that holds bytes, back in
+   host memory; NULL pointers are skipped.  -2 for a packed batch whose bytes
+   have not been made. */
+int vsa_queries_download(const vsa_queries *queries, uint8_t *symbols,
+                         uint64_t *start, uint64_t *length);
+/* codons of one grid a workgroup of the translation kernel translates */
+#define VSA_TRANSLATE_TILE 256u
+uint64_t vsa_translate_tile(void);
+/* HIP-event time of the translation kernels of the batch in ms (0 for a
+   batch that is not translated) */
+double vsa_queries_translate_ms(const vsa_queries *protein);
+
+/* sixframeconvertmatch (kurtz/sixframe.c:232-264) for every record of a list
+   the engine delivered on a translated batch: a new resident list, the query
+   view in DNA coordinates of the forward strand --
+     length = 3 * length, dbstart unchanged, queryseq = q / 6 (q and the
+     result both count from the batch's offset), querystart = 3 * querystart
+     + f in forward frame f, len - 3 * (querystart + length) - r in reverse
+     frame r
+   -- which is what vsa_coverage_mark(.., VSA_COVERAGE_QUERIES) needs on a
+   coverage opened over the DNA batch (-qnomatch, -qmaskmatch of DNA reads
+   against a protein database; -dbnomatch takes the list as it is).  reverse
+   (host, vsa_result_count entries, may be NULL): 1 for a record of a reverse
+   frame.  VSA_NOT_COVERED: a packed-pair result.  -2: a batch that is not
+   translated, an offset that is no multiple of 6, a record that does not lie
+   in its frame.  The HIP-event time of the kernel is total_device_ms of the
+   new list's stats. */
+int vsa_translated_convert(const vsa_result *result,
+                           const vsa_queries *protein, vsa_result **queryview,
+                           uint8_t *reverse, uint64_t capacity);
+/* the same on the host: dnalength[numofdna] the lengths of the DNA
+   sequences, offset that of the six-frame batch */
+int vsa_translated_convert_host(const vsa_match *matches, uint64_t n,
+                                const uint64_t *dnalength, uint64_t numofdna,
+                                uint64_t offset, vsa_match *queryview,
+                                uint8_t *reverse);
 
 #ifdef __cplusplus
 }

@@ -416,6 +416,16 @@ def _load():
                                U64, V, U64]),
         "vsa_chain_format_host": (C.c_int64, [V, I, U64, V, V, V, V, V,
                                               U64]),
+        "vsa_transnum_check": (I, [U32]),
+        "vsa_translate_host": (I, [U32, V, U64, V, V, U64, V, V, U64, V, V,
+                                   C.POINTER(U64)]),
+        "vsa_queries_translate": (I, [U32, V, U64, V, V, U64, V, I, PP]),
+        "vsa_queries_translate_device": (I, [U32, V, U64, U32, V, I, PP]),
+        "vsa_queries_download": (I, [V, V, V, V]),
+        "vsa_translate_tile": (U64, []),
+        "vsa_queries_translate_ms": (C.c_double, [V]),
+        "vsa_translated_convert": (I, [V, V, PP, V, U64]),
+        "vsa_translated_convert_host": (I, [V, U64, V, U64, U64, V, V]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -575,7 +585,54 @@ class Queries:
                                            C.byref(h)))
         return cls(h, nq)
 
+    @classmethod
+    def translate(cls, transnum, dnachars, start, length, symbolmap,
+                  device=0):
+        """vmatch -dnavsprot transnum: the six reading frames of DNA sequences
+        given as CHARACTERS (sequence i = dnachars[start[i]:start[i] +
+        length[i]]) as a batch of 6 * len(start) protein queries under the
+        symbol map of the index (vsa_queries_translate)"""
+        dnachars = np.ascontiguousarray(dnachars, np.uint8)
+        start = np.ascontiguousarray(start, np.uint64)
+        length = np.ascontiguousarray(length, np.uint64)
+        symbolmap = np.ascontiguousarray(symbolmap, np.uint8)
+        assert symbolmap.shape == (256,)
+        h = C.c_void_p()
+        _check(lib.vsa_queries_translate(
+            int(transnum), _ptr(dnachars), dnachars.shape[0], _ptr(start),
+            _ptr(length), start.shape[0], _ptr(symbolmap), device,
+            C.byref(h)))
+        return cls(h, 6 * start.shape[0])
+
+    @classmethod
+    def translate_device(cls, transnum, device_chars, nq, m, symbolmap,
+                         device=0):
+        """the same for nq reads of m characters back to back in device
+        memory (vsa_queries_translate_device)"""
+        symbolmap = np.ascontiguousarray(symbolmap, np.uint8)
+        assert symbolmap.shape == (256,)
+        h = C.c_void_p()
+        _check(lib.vsa_queries_translate_device(
+            int(transnum), device_chars, int(nq), int(m), _ptr(symbolmap),
+            device, C.byref(h)))
+        return cls(h, 6 * int(nq))
+
+    def translate_ms(self):
+        """HIP-event time of the translation kernels of a translated batch"""
+        return float(lib.vsa_queries_translate_ms(self._h))
+
+    def download(self):
+        """-> (symbols, start, length) of a byte batch as numpy arrays"""
+        qi = self.info()
+        sym = np.zeros(qi.numofsymbols, np.uint8)
+        start = np.zeros(qi.numofqueries, np.uint64)
+        length = np.zeros(qi.numofqueries, np.uint64)
+        _check(lib.vsa_queries_download(self._h, _ptr(sym), _ptr(start),
+                                        _ptr(length)))
+        return sym, start, length
+
     def set_offset(self, offset):
+        """(a translated batch counts six-frame sequences: 6 * first read)"""
         _check(lib.vsa_queries_set_offset(self._h, int(offset)))
 
     def info(self):
@@ -987,6 +1044,10 @@ class Pipeline:
 
 SINK_COMPLETE, SINK_QUERY, SINK_SELF, SINK_APPROX_EDIST, \
     SINK_APPROX_HAMMING = range(5)
+# vmatch -dnavsprot: records of a six-frame batch (Queries.translate), the
+# query Multiseq of the layout is the DNA one; lines with the flags F / G
+# (_COMPLETE: the records of findcompletematches on such a batch)
+SINK_TRANSLATED, SINK_TRANSLATED_COMPLETE = 5, 6
 SHOW_ABSOLUTE, SHOW_NODIST, SHOW_NOEVALUE, SHOW_NOSCORE, SHOW_NOIDENTITY = (
     1, 2, 4, 8, 16)
 
@@ -1051,6 +1112,63 @@ class Sink:
 
     def __del__(self):
         self.close()
+
+
+# ---- six-frame translation (vmatch -dnavsprot) ------------------------------
+
+TRANSLATE_TILE = int(lib.vsa_translate_tile())
+TRANSLATION_TABLES = (1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 14, 15, 16, 21, 22,
+                      23)
+
+
+def transnum_check(transnum):
+    """raises the reference's error for an illegal translation table number"""
+    _check(lib.vsa_transnum_check(int(transnum)))
+
+
+def translate_host(transnum, dnachars, start, length, symbolmap):
+    """the six-frame translation on the host (vsa_translate_host, no GPU)
+    -> (symbols, start, length) of the 6 * len(start) protein sequences"""
+    dnachars = np.ascontiguousarray(dnachars, np.uint8)
+    start = np.ascontiguousarray(start, np.uint64)
+    length = np.ascontiguousarray(length, np.uint64)
+    symbolmap = np.ascontiguousarray(symbolmap, np.uint8)
+    assert symbolmap.shape == (256,)
+    nq = start.shape[0]
+    cap = int((length // np.uint64(3)).sum()) * 6 + 6 * nq + 1
+    protein = np.zeros(cap, np.uint8)
+    pstart, plength = np.zeros(6 * nq, np.uint64), np.zeros(6 * nq, np.uint64)
+    n = C.c_uint64(0)
+    _check(lib.vsa_translate_host(
+        int(transnum), _ptr(dnachars), dnachars.shape[0], _ptr(start),
+        _ptr(length), nq, _ptr(symbolmap), _ptr(protein), cap, _ptr(pstart),
+        _ptr(plength), C.byref(n)))
+    return protein[:n.value].copy(), pstart, plength
+
+
+def translated_convert(result, protein):
+    """a list the engine delivered on a translated batch -> (Result with the
+    query view in DNA coordinates, one strand byte per record: 1 = reverse
+    frame) (vsa_translated_convert)"""
+    n = result.count
+    reverse = np.zeros(n, np.uint8)
+    h = C.c_void_p()
+    _check(lib.vsa_translated_convert(result._h, protein._h, C.byref(h),
+                                      _ptr(reverse), n))
+    return Result(h), reverse
+
+
+def translated_convert_host(matches, dnalength, offset=0):
+    """the same on a MATCH_DTYPE array in host memory
+    (vsa_translated_convert_host) -> (query view, strand bytes)"""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    dnalength = np.ascontiguousarray(dnalength, np.uint64)
+    view = np.zeros(matches.shape[0], MATCH_DTYPE)
+    reverse = np.zeros(matches.shape[0], np.uint8)
+    _check(lib.vsa_translated_convert_host(
+        _ptr(matches), matches.shape[0], _ptr(dnalength), dnalength.shape[0],
+        int(offset), _ptr(view), _ptr(reverse)))
+    return view, reverse
 
 
 # ---- match coverage (vmatch -dbnomatch / -qnomatch / -dbmaskmatch /

@@ -793,6 +793,7 @@ extern "C" void vsa_queries_free(vsa_queries *q)
   (void) hipFree(q->symbols);
   (void) hipFree(q->start);
   (void) hipFree(q->length);
+  (void) hipFree(q->dnalength);
   if (q->ownsrows)
   {
     (void) hipFree(q->rows);

@@ -31,6 +31,7 @@
 #include <unistd.h>
 #include "vstree_amd.h"
 #include "evalues.h"
+#include "sixframe_rules.h"
 
 char *vsa_errbuf(void);
 #define ERRSIZE 1024
@@ -423,17 +424,23 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
       position1, position2, lenmatch;
   int64_t distance, ad, score;
   double multiplier = 0.0;
+  uint8_t reverse = 0; /* VSA_SINK_TRANSLATED: a reverse frame, flag G */
+  const int istranslated = s->p.kind == VSA_SINK_TRANSLATED ||
+                           s->p.kind == VSA_SINK_TRANSLATED_COMPLETE;
   const int isquery = s->p.kind != VSA_SINK_SELF;
   const int iscomplete = s->p.kind == VSA_SINK_COMPLETE ||
                          s->p.kind == VSA_SINK_APPROX_EDIST ||
-                         s->p.kind == VSA_SINK_APPROX_HAMMING;
+                         s->p.kind == VSA_SINK_APPROX_HAMMING ||
+                         s->p.kind == VSA_SINK_TRANSLATED_COMPLETE;
 
   position1 = m->dbstart;
   length1 = m->length;
   seqinfo(s, position1, &seqnum1, &start1, &len1seq);
   if (isquery)
   {
-    const uint64_t q = m->queryseq;
+    /* (translated: the record counts the six frames of every DNA sequence) */
+    const uint64_t q = istranslated ? m->queryseq / VSA_SF_FRAMES
+                                    : m->queryseq;
     uint64_t seqstart2, seqlength2;
     if (q >= s->p.numofqueries)
     {
@@ -442,7 +449,18 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
     seqstart2 = s->qstart[q];
     seqlength2 = s->qlength[q];
     seqnum2 = q;
-    if (s->p.kind == VSA_SINK_QUERY)
+    if (istranslated)
+    {
+      /* sixframeconvertmatch, Vmatch/procfinal.c:262-289 */
+      vsa_match dna;
+      if (vsa_sf_convert(m, m->queryseq, seqlength2, 0, &dna, &reverse) != 0)
+      {
+        return NULL;
+      }
+      length2 = dna.length;
+      relpos2 = dna.querystart;
+      distance = 0;
+    } else if (s->p.kind == VSA_SINK_QUERY)
     {
       length2 = m->length;
       relpos2 = m->querystart;
@@ -503,7 +521,8 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
     *o++ = ' ';
     o = putunsigned(o, position1 - start1, s->wpos1);
   }
-  memcpy(o, s->p.palindromic ? "   P " : "   D ", 5);
+  memcpy(o, istranslated ? (reverse ? "   G " : "   F ")
+                         : (s->p.palindromic ? "   P " : "   D "), 5);
   o = putunsigned(o + 5, length2, s->wlength);
   if (s->p.showmode & VSA_SHOW_ABSOLUTE)
   {
@@ -532,7 +551,7 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
                        ? 0.5 * (double) s->p.totallength *
                              (double) s->p.querytotallength
                        : (double) s->p.totallength *
-                             (double) s->qlength[m->queryseq];
+                             (double) s->qlength[seqnum2];
     } else if (s->p.totalquerylength > 0)
     {
       multiplier = (double) s->dblen * (double) s->p.totalquerylength;

@@ -56,6 +56,13 @@ int vsa_mc_checklayout(const vsa_sinkparams *layout,
              "(selfpalindromic) are not covered", who);
     return VSA_NOT_COVERED;
   }
+  if (layout->kind == VSA_SINK_TRANSLATED ||
+      layout->kind == VSA_SINK_TRANSLATED_COMPLETE)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of a six-frame translated "
+             "batch (VSA_SINK_TRANSLATED) are not covered", who);
+    return VSA_NOT_COVERED;
+  }
   if (layout->kind < VSA_SINK_COMPLETE ||
       layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
       layout->totalquerylength + 1 > layout->totallength ||

@@ -68,6 +68,13 @@ int vsa_selctx_init(vsa_selctx *ctx, const vsa_sinkparams *layout,
   const uint64_t dblen = layout->totallength - layout->totalquerylength - 1;
 
   memset(ctx, 0, sizeof *ctx);
+  if (layout->kind == VSA_SINK_TRANSLATED ||
+      layout->kind == VSA_SINK_TRANSLATED_COMPLETE)
+  {
+    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: lists of a six-frame "
+             "translated batch (VSA_SINK_TRANSLATED) are not covered");
+    return VSA_NOT_COVERED;
+  }
   if (layout->kind < VSA_SINK_COMPLETE ||
       layout->kind > VSA_SINK_APPROX_HAMMING || layout->numofchars < 2 ||
       layout->totallength == 0 ||

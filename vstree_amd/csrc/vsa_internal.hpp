@@ -208,6 +208,10 @@ struct vsa_queries
   std::vector<uint64_t> hlength; // host copy (needed for ragged batches)
   bool uniform;                  // all lengths equal
   bool dense;                    // uniform and start[i] = i * length
+  // a six-frame translated batch (translate.hip): the lengths of its nq / 6
+  // DNA sequences on the device, for vsa_translated_convert; nullptr else
+  uint64_t *dnalength = nullptr;
+  double translate_ms = 0.0; // HIP-event time of the translation kernels
 };
 
 struct vsa_result
