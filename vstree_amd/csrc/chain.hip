@@ -38,9 +38,8 @@
 //             second walk writes the members front to back.
 // Record and fragment numbers are 32 bit (the entry points refuse more),
 // positions and scores 64 bit.  Nothing is launched on zero elements.
-#include "search_host.hpp"
+#include "resident_list.hpp"
 #include "chain_rules.h"
-#include <rocprim/rocprim.hpp>
 #include <vector>
 #include "tile_compact.inc"
 
@@ -62,15 +61,16 @@ static_assert(CH_TILE == TC_BLOCK, "one thread per fragment of a tile");
 
 struct vsa_chain
 {
+  static constexpr const char *finishname = "vsa_chain_finish";
   int device = 0;
   vsa_selrules view; // the query Multiseq and markpos in device memory
   vsa_clrules seqs;
-  uint64_t *d_qstart = nullptr, *d_qlen = nullptr, *d_markpos = nullptr;
+  DeviceLayout layout;
   vsa_chainparams params;
-  // the records so far, and those the last finish saw
-  uint64_t n = 0, nfinished = 0, capacity = 0;
-  vsa_match *recs = nullptr;
-  uint8_t *flags = nullptr;
+  // the records so far with their fragments and sequence numbers, and how
+  // many of them the last finish saw
+  ResidentList list;
+  uint64_t nfinished = 0;
   vsa_chfrag *frag = nullptr;
   uint64_t *seq1 = nullptr, *seq2 = nullptr;
   uint64_t *maxima = nullptr; // the largest position2, seqnum1, seqnum2
@@ -137,17 +137,13 @@ k_ch_view(vsa_selrules view, vsa_clrules seqs, double wf,
   m0 = ch_wavemax(m0);
   m1 = ch_wavemax(m1);
   m2 = ch_wavemax(m2);
-  const uint64_t b = __ballot(isbad);
   if ((threadIdx.x & 63u) == 0)
   {
     atomicMax(&maxima[0], (unsigned long long) m0);
     atomicMax(&maxima[1], (unsigned long long) m1);
     atomicMax(&maxima[2], (unsigned long long) m2);
-    if (b != 0)
-    {
-      atomicAdd(bad, (unsigned long long) __popcll((unsigned long long) b));
-    }
   }
+  wave_count(isbad, bad);
 }
 
 // *differs != 0: some record lies in another pair than record 0
@@ -258,26 +254,6 @@ struct HeadF
   }
 };
 
-// the first place of a[0 .. n) that is not below x
-__device__ __forceinline__ uint64_t ch_lower(const uint64_t *__restrict__ a,
-                                             uint64_t n, uint64_t x)
-{
-  uint64_t lo = 0, hi = n;
-  while (lo < hi)
-  {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a[mid] < x)
-    {
-      lo = mid + 1;
-    }
-    else
-    {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
 // ---- replay ---------------------------------------------------------------------
 
 // runflag[lo] = 1 for the first place lo of every run of one seqnum1 of more
@@ -291,7 +267,7 @@ k_ch_markruns(const vsa_chfrag *__restrict__ sfrag,
   const uint64_t t = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (t < n && ch_tie(1, sfrag, sseq1, sseq2, t))
   {
-    const uint64_t s = sseq1[t], lo = ch_lower(sseq1, n, s);
+    const uint64_t s = sseq1[t], lo = vsa_lowerbound(sseq1, n, s);
     uint64_t hi = lo + VSA_CH_STABLEWIDTH;
     if (hi < n && sseq1[hi] == s)
     {
@@ -313,7 +289,7 @@ struct ReplayF
 
   __device__ int cls(uint64_t t, Payload &) const
   {
-    return runflag[ch_lower(sseq1, n, sseq1[t])] ? 0 : -1;
+    return runflag[vsa_lowerbound(sseq1, n, sseq1[t])] ? 0 : -1;
   }
   __device__ void put(int, uint64_t rank, uint64_t t, const Payload &) const
   {
@@ -380,7 +356,7 @@ k_ch_pid(const uint64_t *__restrict__ pstart, uint64_t nproblems, uint64_t n,
   if (t < n)
   {
     // the last problem that starts at t or before it
-    pid[t] = (uint32_t) (ch_lower(pstart, nproblems, t + 1) - 1);
+    pid[t] = (uint32_t) (vsa_lowerbound(pstart, nproblems, t + 1) - 1);
   }
 }
 
@@ -797,26 +773,6 @@ struct EndF
   }
 };
 
-// the first place of a[0 .. n) that is not below x
-__device__ __forceinline__ uint64_t ch_lower32(const uint32_t *__restrict__ a,
-                                               uint64_t n, uint64_t x)
-{
-  uint64_t lo = 0, hi = n;
-  while (lo < hi)
-  {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (a[mid] < x)
-    {
-      lo = mid + 1;
-    }
-    else
-    {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
 // one lane per chain: problem, number, score and length; one more lane
 // writes length[nchains] = 0 for the exclusive sum
 __global__ void __launch_bounds__(TC_BLOCK)
@@ -838,7 +794,7 @@ k_ch_chains(Retr q, const uint32_t *__restrict__ ends, uint64_t nchains,
   const uint32_t p = q.pid[t];
   const uint64_t b = q.pstart[p];
   problem[c] = p;
-  number[c] = c - ch_lower32(ends, nchains, b);
+  number[c] = c - vsa_lowerbound(ends, nchains, b);
   if (ch_single(q, p))
   {
     const vsa_chfrag f = q.a.f[t];
@@ -882,41 +838,7 @@ k_ch_members(Retr q, const uint32_t *__restrict__ ends, uint64_t nchains,
   }
 }
 
-__global__ void __launch_bounds__(TC_BLOCK)
-k_ch_gatherrecs(const vsa_match *__restrict__ recs,
-                const uint8_t *__restrict__ flags,
-                const uint32_t *__restrict__ members, uint64_t k,
-                vsa_match *__restrict__ out, uint8_t *__restrict__ outflags)
-{
-  const uint64_t t = vsa_bid() * TC_BLOCK + threadIdx.x;
-  if (t < k)
-  {
-    out[t] = recs[members[t]];
-    outflags[t] = flags[members[t]];
-  }
-}
-
 // ---- host -----------------------------------------------------------------------
-
-// room for `need` records; what is there stays
-int reserve(vsa_chain *c, uint64_t need)
-{
-  if (need <= c->capacity)
-  {
-    return 0;
-  }
-  const uint64_t cap = std::max<uint64_t>(need, 2 * c->capacity);
-  if (grow((void **) &c->recs, c->n, cap, sizeof(vsa_match)) != 0 ||
-      grow((void **) &c->flags, c->n, cap, 1) != 0 ||
-      grow((void **) &c->frag, c->n, cap, sizeof(vsa_chfrag)) != 0 ||
-      grow((void **) &c->seq1, c->n, cap, 8) != 0 ||
-      grow((void **) &c->seq2, c->n, cap, 8) != 0)
-  {
-    return -100;
-  }
-  c->capacity = cap;
-  return 0;
-}
 
 // the largest problem of a class: the constant of chain_rules.h, or for the
 // measurement of scripts/chain_probe.py what the environment says (a lane
@@ -940,11 +862,11 @@ uint32_t classbound(const char *name, uint32_t preset, uint32_t least)
 struct Sorter
 {
   const vsa_chain *c;
-  DevBuf idx, idx2, key, key2, temp;
+  DevBuf idx, idx2, key, key2;
 
   int init()
   {
-    const uint64_t n = c->n;
+    const uint64_t n = c->list.n;
     if (idx.alloc(n * 4) != 0 || idx2.alloc(n * 4) != 0 ||
         key.alloc(n * 8) != 0 || key2.alloc(n * 8) != 0)
     {
@@ -957,17 +879,16 @@ struct Sorter
   // a stable sort by one word of the key, of which `bits` bits count
   int pass(int which, unsigned int bits, const uint32_t *last)
   {
-    const uint64_t n = c->n;
+    const uint64_t n = c->list.n;
     k_ch_key<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(
         which, c->frag, c->seq1, c->seq2, last, idx.as<uint32_t>(), n,
         key.as<uint64_t>());
     VSA_HIP(hipGetLastError());
-    VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-      return rocprim::radix_sort_pairs(p, tb, key.as<uint64_t>(),
-                                       key2.as<uint64_t>(),
-                                       idx.as<uint32_t>(), idx2.as<uint32_t>(),
-                                       (size_t) n, 0u, bits, nullptr);
-    }));
+    if (sortpairs(key.as<uint64_t>(), key2.as<uint64_t>(), idx.as<uint32_t>(),
+                  idx2.as<uint32_t>(), n, bits, nullptr) != 0)
+    {
+      return -100;
+    }
     std::swap(idx.p, idx2.p);
     return 0;
   }
@@ -984,45 +905,22 @@ struct Sorter
   }
 };
 
-int needfinished(const vsa_chain *c, const char *who)
-{
-  if (c == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  if (!c->finished)
-  {
-    VSA_ERROR("%s: vsa_chain_finish has not seen the last list", who);
-    return -2;
-  }
-  return 0;
-}
-
 // the members and their records into host memory, once per finish
-int gathermembers(vsa_chain *c)
+int hostmembers(vsa_chain *c)
 {
   if (c->gathered)
   {
     return 0;
   }
   const uint64_t k = c->stats.chained;
-  c->memberrecs.resize(k);
   c->hmembers.resize(k);
+  if (members_to_host(c->list, c->members, k, c->memberrecs) != 0)
+  {
+    return -100;
+  }
   if (k > 0)
   {
     std::vector<uint32_t> h(k);
-    DevBuf drecs, dflags;
-    if (drecs.alloc(k * sizeof(vsa_match)) != 0 || dflags.alloc(k) != 0)
-    {
-      return -100;
-    }
-    k_ch_gatherrecs<<<gridfor(k), TC_BLOCK, 0, nullptr>>>(
-        c->recs, c->flags, c->members, k, drecs.as<vsa_match>(),
-        dflags.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(hipMemcpy(c->memberrecs.data(), drecs.p, k * sizeof(vsa_match),
-                      hipMemcpyDeviceToHost));
     VSA_HIP(hipMemcpy(h.data(), c->members, k * 4, hipMemcpyDeviceToHost));
     for (uint64_t t = 0; t < k; t++)
     {
@@ -1041,15 +939,8 @@ extern "C" void vsa_chain_close(vsa_chain *c)
   {
     return;
   }
-  (void) hipSetDevice(c->device);
-  (void) hipFree(c->d_qstart);
-  (void) hipFree(c->d_qlen);
-  (void) hipFree(c->d_markpos);
-  vsa_dev_free(c->recs);
-  vsa_dev_free(c->flags);
-  vsa_dev_free(c->frag);
-  vsa_dev_free(c->seq1);
-  vsa_dev_free(c->seq2);
+  c->layout.release();
+  c->list.release();
   vsa_dev_free(c->maxima);
   vsa_dev_free(c->members);
   delete c;
@@ -1078,26 +969,23 @@ extern "C" int vsa_chain_open(const vsa_sinkparams *layout,
     return -100;
   }
   vsa_chain *c = new vsa_chain();
-  c->device = device;
+  c->device = c->layout.device = c->list.device = device;
+  c->list.column(&c->frag);
+  c->list.column(&c->seq1);
+  c->list.column(&c->seq2);
   c->view = view;
   c->seqs = seqs;
   c->params = *params;
   memset(&c->stats, 0, sizeof c->stats);
-  const size_t markbytes = (size_t) (seqs.numofsequences - 1) * 8;
-  if (upload_queryview(view.nq, &c->view.qstart, &c->view.qlen, &c->d_qstart,
-                       &c->d_qlen, "vsa_chain_open") != 0 ||
+  if (c->layout.upload("vsa_chain_open", view.nq, &c->view.qstart,
+                       &c->view.qlen, seqs.numofsequences - 1,
+                       &c->seqs.markpos) != 0 ||
       vsa_dev_alloc((void **) &c->maxima, 3 * 8) != 0 ||
-      hipMemset(c->maxima, 0, 3 * 8) != hipSuccess ||
-      (markbytes > 0 &&
-       (vsa_hip_malloc((void **) &c->d_markpos, markbytes) != hipSuccess ||
-        hipMemcpy(c->d_markpos, seqs.markpos, markbytes,
-                  hipMemcpyHostToDevice) != hipSuccess)))
+      hipMemset(c->maxima, 0, 3 * 8) != hipSuccess)
   {
-    VSA_ERROR("vsa_chain_open: upload of the layout failed");
     vsa_chain_close(c);
     return -100;
   }
-  c->seqs.markpos = c->d_markpos;
   *chain = c;
   return 0;
 }
@@ -1105,77 +993,47 @@ extern "C" int vsa_chain_open(const vsa_sinkparams *layout,
 extern "C" int vsa_chain_add(vsa_chain *c, const vsa_result *r,
                              int palindromic)
 {
-  if (c == nullptr || r == nullptr)
+  const int g = gate("vsa_chain_add", "chain", "chaining", c, r,
+                     [&]() { return selfform(c->view.kind, palindromic); },
+                     CH_MAXRECORDS, "records: only fewer than 2^32 - 1");
+  if (g != 0)
   {
-    VSA_ERROR("vsa_chain_add: NULL argument");
-    return -1;
+    return g < 0 ? g : 0;
   }
-  if (r->packbits != 0)
-  {
-    VSA_ERROR("vsa_chain_add: a packed candidate result has no records to "
-              "chain");
-    return VSA_NOT_COVERED;
-  }
-  if (palindromic && c->view.kind == VSA_SINK_SELF)
-  {
-    VSA_ERROR("vsa_chain_add: palindromic self matches are the "
-              "selfpalindromic form");
-    return VSA_NOT_COVERED;
-  }
-  if (r->device != c->device)
-  {
-    VSA_ERROR("vsa_chain_add: result on device %d, chaining on device %d",
-              r->device, c->device);
-    return -2;
-  }
-  if (c->n + r->count >= CH_MAXRECORDS)
-  {
-    VSA_ERROR("vsa_chain_add: %lu records: only fewer than 2^32 - 1 are "
-              "covered", (unsigned long) (c->n + r->count));
-    return VSA_NOT_COVERED;
-  }
-  if (enter(c->device) != 0)
-  {
-    return -100;
-  }
-  if (r->count == 0)
-  {
-    return 0;
-  }
-  if (reserve(c, c->n + r->count) != 0)
-  {
-    return -100;
-  }
-  DevBuf scratch; // the maxima with this list, and the bad records
-  if (scratch.alloc(4 * 8) != 0)
+  ScratchWords scratch; // the maxima with this list, and the bad records
+  if (c->list.reserve(c->list.n + r->count) != 0 || scratch.alloc(4) != 0)
   {
     return -100;
   }
   Timer t(nullptr);
   t.start();
-  VSA_HIP(hipMemcpyAsync(scratch.p, c->maxima, 3 * 8,
+  VSA_HIP(hipMemcpyAsync(scratch.word(0), c->maxima, 3 * 8,
                          hipMemcpyDeviceToDevice, nullptr));
-  VSA_HIP(hipMemsetAsync(scratch.as<uint64_t>() + 3, 0, 8, nullptr));
+  if (scratch.zero(3, 1) != 0)
+  {
+    return -100;
+  }
   k_ch_view<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
       c->view, c->seqs, c->params.weightfactor, r->matches, r->count,
-      palindromic != 0, c->n, c->recs, c->flags, c->frag, c->seq1, c->seq2,
-      scratch.as<unsigned long long>(), scratch.as<unsigned long long>() + 3);
+      palindromic != 0, c->list.n, c->list.recs, c->list.flags, c->frag,
+      c->seq1, c->seq2, scratch.word(0), scratch.word(3));
   VSA_HIP(hipGetLastError());
   t.stop();
   uint64_t nbad = 0;
-  VSA_HIP(hipMemcpy(&nbad, scratch.as<uint64_t>() + 3, 8,
-                    hipMemcpyDeviceToHost));
+  if (scratch.fetch(3, 1, &nbad) != 0)
+  {
+    return -100;
+  }
   c->ms[CH_VIEW] += t.ms();
   if (nbad != 0)
   {
-    // (what the kernel wrote lies behind the records that count)
-    VSA_ERROR("vsa_chain_add: %lu records do not fit the layout (a query "
-              "number outside the set, a match that leaves its sequence or "
-              "the text)", (unsigned long) nbad);
-    return -2;
+    return misfits("vsa_chain_add", nbad,
+                   "a query number outside the set, a match that leaves its "
+                   "sequence or the text");
   }
-  VSA_HIP(hipMemcpy(c->maxima, scratch.p, 3 * 8, hipMemcpyDeviceToDevice));
-  c->n += r->count;
+  VSA_HIP(hipMemcpy(c->maxima, scratch.word(0), 3 * 8,
+                    hipMemcpyDeviceToDevice));
+  c->list.n += r->count;
   c->finished = false;
   return 0;
 }
@@ -1191,7 +1049,7 @@ extern "C" int vsa_chain_finish(vsa_chain *c)
   {
     return -100;
   }
-  const uint64_t n = c->n;
+  const uint64_t n = c->list.n;
   vsa_chainstats st;
   memset(&st, 0, sizeof st);
   st.matches = n;
@@ -1365,7 +1223,7 @@ extern "C" int vsa_chain_finish(vsa_chain *c)
                 "covers at most %lu (vsa_chain_host takes any size)",
                 (unsigned long) largest, (unsigned long) VSA_CHAIN_MAXGROUP);
       // back to the last finish: its chains stay, the lists since then go
-      c->n = c->nfinished;
+      c->list.n = c->nfinished;
       c->finished = c->everfinished;
       return VSA_NOT_COVERED;
     }
@@ -1517,7 +1375,7 @@ extern "C" int vsa_chain_finish(vsa_chain *c)
     c->ms[q] += ms[q];
   }
   c->finished = c->everfinished = true;
-  c->nfinished = c->n;
+  c->nfinished = c->list.n;
   c->gathered = false;
   return 0;
 }
@@ -1574,7 +1432,7 @@ extern "C" int vsa_chain_members(vsa_chain *c, uint64_t *members)
     VSA_ERROR("vsa_chain_members: NULL argument");
     return -1;
   }
-  if (enter(c->device) != 0 || gathermembers(c) != 0)
+  if (enter(c->device) != 0 || hostmembers(c) != 0)
   {
     return -100;
   }
@@ -1603,37 +1461,8 @@ extern "C" int vsa_chain_records(vsa_chain *c, vsa_result **records,
   {
     return -100;
   }
-  const uint64_t k = c->stats.chained;
-  vsa_result *res = newresult(c->device);
-  if (k == 0)
-  {
-    *records = res;
-    return 0;
-  }
-  ResultGuard guard = {res};
-  DevBuf oflags;
-  if (oflags.alloc(k) != 0 ||
-      vsa_dev_alloc((void **) &res->matches, k * sizeof(vsa_match)) != 0)
-  {
-    return -100;
-  }
-  k_ch_gatherrecs<<<gridfor(k), TC_BLOCK, 0, nullptr>>>(
-      c->recs, c->flags, c->members, k, res->matches, oflags.as<uint8_t>());
-  VSA_HIP(hipGetLastError());
-  VSA_HIP(hipStreamSynchronize(nullptr));
-  if (palindromic != nullptr)
-  {
-    VSA_HIP(hipMemcpy(palindromic, oflags.p, k, hipMemcpyDeviceToHost));
-  }
-  res->count = k;
-  res->stats.count = k;
-  if (sumlengths(res->matches, k, nullptr, &res->stats.sumlength) != 0)
-  {
-    return -100;
-  }
-  guard.r = nullptr;
-  *records = res;
-  return 0;
+  return records_of(c->list, c->members, c->stats.chained, palindromic,
+                    nullptr, records);
 }
 
 extern "C" int64_t vsa_chain_format(vsa_chain *c, vsa_sink *sink, int flags,
@@ -1649,7 +1478,7 @@ extern "C" int64_t vsa_chain_format(vsa_chain *c, vsa_sink *sink, int flags,
     VSA_ERROR("vsa_chain_format: NULL argument");
     return -1;
   }
-  if (enter(c->device) != 0 || gathermembers(c) != 0)
+  if (enter(c->device) != 0 || hostmembers(c) != 0)
   {
     return -100;
   }

@@ -32,21 +32,20 @@
 //            order addClusterEdge leaves them in.
 // Sequence and edge numbers are 32 bit (the entry points refuse more),
 // positions and record indices 64 bit.
-#include "search_host.hpp"
+#include "resident_list.hpp"
 #include "cluster_rules.h"
 #include "cluster_forest.inc"
 
 struct vsa_cluster
 {
+  static constexpr const char *finishname = "vsa_cluster_finish";
   int device = 0;
   int kind = 0;
   vsa_clrules rules; // markpos in device memory
-  uint64_t *d_markpos = nullptr;
-  // the edges so far
-  uint64_t nedges = 0, capacity = 0;
+  DeviceLayout layout;
+  // the edges so far: their records and flags, and their ends
+  ResidentList list;
   uint32_t *e1 = nullptr, *e2 = nullptr;
-  vsa_match *recs = nullptr;
-  uint8_t *flags = nullptr;
   bool finished = false;
   vsa_clresult res;
   vsa_clusterstats stats;
@@ -91,27 +90,6 @@ struct EdgeF
   }
 };
 
-// room for `need` edges; what is there stays.  Array by array (one wait
-// each, the old and the new block of one array at a time): where a later one
-// fails, the earlier ones are larger than `capacity` says, which stays right
-int reserve(vsa_cluster *c, uint64_t need)
-{
-  if (need <= c->capacity)
-  {
-    return 0;
-  }
-  const uint64_t cap = std::max<uint64_t>(need, 2 * c->capacity);
-  if (grow((void **) &c->e1, c->nedges, cap, 4) != 0 ||
-      grow((void **) &c->e2, c->nedges, cap, 4) != 0 ||
-      grow((void **) &c->recs, c->nedges, cap, sizeof(vsa_match)) != 0 ||
-      grow((void **) &c->flags, c->nedges, cap, 1) != 0)
-  {
-    return -100;
-  }
-  c->capacity = cap;
-  return 0;
-}
-
 } // namespace
 
 extern "C" void vsa_cluster_close(vsa_cluster *c)
@@ -120,12 +98,8 @@ extern "C" void vsa_cluster_close(vsa_cluster *c)
   {
     return;
   }
-  (void) hipSetDevice(c->device);
-  (void) hipFree(c->d_markpos);
-  vsa_dev_free(c->e1);
-  vsa_dev_free(c->e2);
-  vsa_dev_free(c->recs);
-  vsa_dev_free(c->flags);
+  c->layout.release();
+  c->list.release();
   vsa_cl_freeresult(&c->res);
   delete c;
 }
@@ -150,22 +124,21 @@ extern "C" int vsa_cluster_open(const vsa_sinkparams *layout,
     return -100;
   }
   vsa_cluster *c = new vsa_cluster();
-  c->device = device;
+  c->device = c->layout.device = c->list.device = device;
+  c->list.column(&c->e1);
+  c->list.column(&c->e2);
   c->kind = layout->kind;
   memset(&c->stats, 0, sizeof c->stats);
   memset(&c->res, 0, sizeof c->res);
-  const uint64_t nmark = layout->numofsequences - 1;
-  if (vsa_hip_malloc((void **) &c->d_markpos, nmark * 8) != hipSuccess ||
-      hipMemcpy(c->d_markpos, layout->markpos, nmark * 8,
-                hipMemcpyHostToDevice) != hipSuccess)
+  c->rules.markpos = layout->markpos;
+  if (c->layout.upload("vsa_cluster_open", 0, nullptr, nullptr,
+                       layout->numofsequences - 1, &c->rules.markpos) != 0)
   {
-    VSA_ERROR("vsa_cluster_open: upload of the separator positions failed");
     vsa_cluster_close(c);
     return -100;
   }
   c->rules.totallength = layout->totallength;
   c->rules.numofsequences = layout->numofsequences;
-  c->rules.markpos = c->d_markpos;
   c->rules.percsmall = params->percsmall;
   c->rules.perclarge = params->perclarge;
   *cluster = c;
@@ -175,36 +148,18 @@ extern "C" int vsa_cluster_open(const vsa_sinkparams *layout,
 extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
                                int palindromic)
 {
-  if (c == nullptr || r == nullptr)
+  // (the edges are counted below: their limit is not the gate's)
+  const int g = gate("vsa_cluster_add", "cluster by", "clustering", c, r,
+                     [&]() {
+                       return !palindromic && c->kind != VSA_SINK_SELF
+                                  ? "a direct list, the layout is that of "
+                                    "vmatch -p IDX"
+                                  : nullptr;
+                     },
+                     0, nullptr);
+  if (g != 0)
   {
-    VSA_ERROR("vsa_cluster_add: NULL argument");
-    return -1;
-  }
-  if (r->packbits != 0)
-  {
-    VSA_ERROR("vsa_cluster_add: a packed candidate result has no records to "
-              "cluster by");
-    return VSA_NOT_COVERED;
-  }
-  if (!palindromic && c->kind != VSA_SINK_SELF)
-  {
-    VSA_ERROR("vsa_cluster_add: a direct list, the layout is that of vmatch "
-              "-p IDX");
-    return VSA_NOT_COVERED;
-  }
-  if (r->device != c->device)
-  {
-    VSA_ERROR("vsa_cluster_add: result on device %d, clustering on device %d",
-              r->device, c->device);
-    return -2;
-  }
-  if (enter(c->device) != 0)
-  {
-    return -100;
-  }
-  if (r->count == 0)
-  {
-    return 0;
+    return g < 0 ? g : 0;
   }
   Timer t(nullptr);
   t.start();
@@ -212,7 +167,7 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
   ef.r = c->rules;
   ef.matches = r->matches;
   ef.palindromic = palindromic != 0;
-  ef.base = c->nedges;
+  ef.base = c->list.n;
   ef.e1 = ef.e2 = nullptr;
   ef.recs = nullptr;
   ef.flags = nullptr;
@@ -231,23 +186,23 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
     return -2;
   }
   const uint64_t m = totals[VSA_CL_EDGE];
-  if (c->nedges + m >= 0xFFFFFFFFull)
+  if (c->list.n + m >= 0xFFFFFFFFull)
   {
     VSA_ERROR("vsa_cluster_add: %lu edges: only fewer than 2^32 - 1 are "
-              "covered", (unsigned long) (c->nedges + m));
+              "covered", (unsigned long) (c->list.n + m));
     return VSA_NOT_COVERED;
   }
   if (m > 0)
   {
-    int rc = reserve(c, c->nedges + m);
+    int rc = c->list.reserve(c->list.n + m);
     if (rc != 0)
     {
       return rc;
     }
     ef.e1 = c->e1;
     ef.e2 = c->e2;
-    ef.recs = c->recs;
-    ef.flags = c->flags;
+    ef.recs = c->list.recs;
+    ef.flags = c->list.flags;
     if (tc_emit<1>(ef, r->count, offsets) != 0)
     {
       return -100;
@@ -256,13 +211,13 @@ extern "C" int vsa_cluster_add(vsa_cluster *c, const vsa_result *r,
   t.stop();
   VSA_HIP(hipStreamSynchronize(nullptr));
   c->add_ms += t.ms();
-  c->nedges += m;
+  c->list.n += m;
   c->finished = false;
   c->stats.seen += r->count;
   c->stats.samesequence += totals[VSA_CL_SAME];
   c->stats.mirrordropped += totals[VSA_CL_MIRROR];
   c->stats.rejected += totals[VSA_CL_REJECTED];
-  c->stats.edges = c->nedges;
+  c->stats.edges = c->list.n;
   return 0;
 }
 
@@ -281,9 +236,9 @@ extern "C" int vsa_cluster_finish(vsa_cluster *c)
   uint64_t rounds = 0, changed = 0;
   Timer t(nullptr);
   t.start();
-  if (c->nedges > 0)
+  if (c->list.n > 0)
   {
-    const int rc = cl_forest(c->rules.numofsequences, c->e1, c->e2, c->nedges,
+    const int rc = cl_forest(c->rules.numofsequences, c->e1, c->e2, c->list.n,
                              f1, f2, &rounds, "vsa_cluster_finish");
     if (rc != 0)
     {
@@ -328,21 +283,6 @@ extern "C" int vsa_cluster_getstats(const vsa_cluster *c,
     return -1;
   }
   *stats = c->stats;
-  return 0;
-}
-
-static int needfinished(const vsa_cluster *c, const char *who)
-{
-  if (c == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  if (!c->finished)
-  {
-    VSA_ERROR("%s: vsa_cluster_finish has not seen the last list", who);
-    return -2;
-  }
   return 0;
 }
 
@@ -430,56 +370,34 @@ extern "C" int vsa_cluster_edges(vsa_cluster *c, vsa_result **edges,
   {
     return -100;
   }
-  const uint64_t ne = c->nedges, nseq = c->rules.numofsequences,
+  const uint64_t ne = c->list.n, nseq = c->rules.numofsequences,
                  ncl = c->res.clusters;
-  vsa_result *res = newresult(c->device);
   if (ne == 0)
   {
     if (edgestart != nullptr)
     {
       edgestart[0] = 0;
     }
-    *edges = res;
-    return 0;
+    return records_of(c->list, nullptr, 0, nullptr, nullptr, edges);
   }
-  ResultGuard guard = {res};
   Timer t(nullptr);
   t.start();
-  DevBuf order, oflags;
+  DevBuf order;
   std::vector<uint64_t> hstart;
-  if (oflags.alloc(ne) != 0 ||
-      vsa_dev_alloc((void **) &res->matches, ne * sizeof(vsa_match)) != 0)
-  {
-    return -100;
-  }
   rc = cl_group(c->e1, c->e2, ne, c->res.label, nseq, ncl, order, hstart,
                 "vsa_cluster_edges");
+  if (rc == 0)
+  {
+    rc = records_of(c->list, order.as<uint32_t>(), ne, palindromic, &t, edges);
+  }
   if (rc != 0)
   {
     return rc;
   }
-  const RecGather g = {c->recs, c->flags, res->matches, oflags.as<uint8_t>()};
-  k_cl_gather<RecGather><<<gridfor(ne), TC_BLOCK, 0, nullptr>>>(
-      g, order.as<uint32_t>(), ne);
-  VSA_HIP(hipGetLastError());
-  t.stop();
-  VSA_HIP(hipStreamSynchronize(nullptr));
   c->edges_ms += t.ms();
-  if (palindromic != nullptr)
-  {
-    VSA_HIP(hipMemcpy(palindromic, oflags.p, ne, hipMemcpyDeviceToHost));
-  }
   if (edgestart != nullptr)
   {
     memcpy(edgestart, hstart.data(), (ncl + 1) * 8);
   }
-  res->count = ne;
-  res->stats.count = ne;
-  if (sumlengths(res->matches, ne, nullptr, &res->stats.sumlength) != 0)
-  {
-    return -100;
-  }
-  guard.r = nullptr;
-  *edges = res;
   return 0;
 }

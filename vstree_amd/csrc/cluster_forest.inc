@@ -2,7 +2,7 @@
 // translation units that cluster something: cluster.hip (the sequences of an
 // index, vmatch -dbcluster) and matchcluster.hip (the matches of a list,
 // vmatch -pp matchcluster).  Included inside no namespace, after
-// search_host.hpp and the rules of the including file (VSA_CL_CLASSES,
+// resident_list.hpp and the rules of the including file (VSA_CL_CLASSES,
 // vsa_clresult); everything here lands in an unnamed one.
 //
 //   compaction  tile_compact.inc, which this file includes: the functors
@@ -70,11 +70,7 @@ k_cl_pick(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
       atomicMin(&best[rv], (unsigned long long) i);
     }
   }
-  const uint64_t b = __ballot(cross);
-  if (b != 0 && (threadIdx.x & 63u) == (uint32_t) (__ffsll((unsigned long long) b) - 1))
-  {
-    atomicAdd(crossing, (unsigned long long) __popcll((unsigned long long) b));
-  }
+  wave_count(cross, crossing);
 }
 
 // next[x] = the parent of x after this round's hooks; parent[] and best[] are
@@ -155,33 +151,6 @@ k_cl_keys(const uint32_t *__restrict__ e1, const uint32_t *__restrict__ e2,
   }
 }
 
-// out[t] = in[order[t]], whatever G::move makes of it
-template <class G>
-__global__ void __launch_bounds__(TC_BLOCK)
-k_cl_gather(G g, const uint32_t *__restrict__ order, uint64_t n)
-{
-  const uint64_t t = vsa_bid() * TC_BLOCK + threadIdx.x;
-  if (t < n)
-  {
-    g.move(t, order[t]);
-  }
-}
-
-// a record and its D/P flag
-struct RecGather
-{
-  const vsa_match *recs;
-  const uint8_t *flags;
-  vsa_match *outrecs;
-  uint8_t *outflags;
-
-  __device__ void move(uint64_t t, uint32_t i) const
-  {
-    outrecs[t] = recs[i];
-    outflags[t] = flags[i];
-  }
-};
-
 // start[c] = the first position of the sorted keys that is not below c
 __global__ void __launch_bounds__(TC_BLOCK)
 k_cl_starts(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nclusters,
@@ -190,20 +159,7 @@ k_cl_starts(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nclusters,
   const uint64_t c = vsa_bid() * TC_BLOCK + threadIdx.x;
   if (c <= nclusters)
   {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi)
-    {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (keys[mid] < c)
-      {
-        lo = mid + 1;
-      }
-      else
-      {
-        hi = mid;
-      }
-    }
-    start[c] = lo;
+    start[c] = vsa_lowerbound(keys, n, c);
   }
 }
 
@@ -341,7 +297,7 @@ int cl_group(const uint32_t *e1, const uint32_t *e2, uint64_t ne,
       vals.as<uint32_t>(), bad.as<unsigned long long>());
   VSA_HIP(hipGetLastError());
   if (sortpairs(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
-                order.as<uint32_t>(), ne, nullptr) != 0)
+                order.as<uint32_t>(), ne, 64, nullptr) != 0)
   {
     return -100;
   }

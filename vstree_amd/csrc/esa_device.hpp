@@ -58,6 +58,32 @@ __device__ __forceinline__ vsa_u128 vsa_load16(const void *p)
   return v;
 }
 
+// The first place of the ascending a[0 .. n) that is not below x: the one
+// bisection of the handles that post-process match lists, whatever the width
+// of the elements.  (matchcluster.hip keeps two of its own, whose contracts
+// differ: mc_upper starts at a place of the caller's and finds the first
+// element ABOVE x; mc_owner finds the last place not above x between two
+// places that are known to bracket it.)
+template <typename T>
+__device__ __forceinline__ uint64_t vsa_lowerbound(const T *__restrict__ a,
+                                                   uint64_t n, uint64_t x)
+{
+  uint64_t lo = 0, hi = n;
+  while (lo < hi)
+  {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (a[mid] < x)
+    {
+      lo = mid + 1;
+    }
+    else
+    {
+      hi = mid;
+    }
+  }
+  return lo;
+}
+
 // ---- reads that live in HBM at two bits per symbol (DevQueries::rows) ------
 // The fast paths take such a read as a PackedQuery (registers); the paths that
 // compare byte for byte -- the reference walk, a comparison that met a special

@@ -35,10 +35,9 @@
 // Match numbers, places of the sorted order and edge numbers are 32 bit (the
 // entry points refuse more); positions, candidate counts and slot numbers
 // are 64 bit.  Nothing is launched on zero elements.
-#include "search_host.hpp"
+#include "resident_list.hpp"
 #include "matchcluster_rules.h"
 #include "erate_rules.h"
-#include <rocprim/rocprim.hpp>
 #include "cluster_forest.inc"
 
 #define MC_DEFAULT_CHUNK ((uint64_t) 1 << 26)
@@ -58,9 +57,10 @@ static_assert(MC_GROUP + 1 == VSA_MATCHCLUSTER_STAGES,
 
 struct vsa_matchcluster
 {
+  static constexpr const char *finishname = "vsa_matchcluster_finish";
   int device = 0;
   vsa_selrules view; // the query Multiseq in device memory
-  uint64_t *d_qstart = nullptr, *d_qlen = nullptr;
+  DeviceLayout layout;
   vsa_mcrules rules;
   unsigned int sortbits = 1;
   // mode VSA_MATCHCLUSTER_ERATE: the text of the index (which outlives the
@@ -70,9 +70,7 @@ struct vsa_matchcluster
   uint32_t errorrate = 0;
   uint64_t longest = 0; // the longest match so far
   // the matches so far
-  uint64_t n = 0, capacity = 0;
-  vsa_match *recs = nullptr;
-  uint8_t *flags = nullptr;
+  ResidentList list;
   uint64_t *start = nullptr;  // 2 per match
   uint64_t *length = nullptr; // 1 per match
   // the edges of the last finish, in the order of their numbers
@@ -126,12 +124,7 @@ k_mc_refs(vsa_selrules view, const vsa_match *__restrict__ in, uint64_t n,
       length[at] = v.length1;
     }
   }
-  const uint64_t b = __ballot(isbad);
-  if (b != 0 && (threadIdx.x & 63u) ==
-                    (uint32_t) (__ffsll((unsigned long long) b) - 1))
-  {
-    atomicAdd(bad, (unsigned long long) __popcll((unsigned long long) b));
-  }
+  wave_count(isbad, bad);
 }
 
 // ---- window ---------------------------------------------------------------------
@@ -280,52 +273,22 @@ struct EdgeGather
 
 // ---- host -----------------------------------------------------------------------
 
-// room for `need` matches; what is there stays
-int reserve(vsa_matchcluster *c, uint64_t need)
-{
-  if (need <= c->capacity)
-  {
-    return 0;
-  }
-  const uint64_t cap = std::max<uint64_t>(need, 2 * c->capacity);
-  if (grow((void **) &c->recs, c->n, cap, sizeof(vsa_match)) != 0 ||
-      grow((void **) &c->flags, c->n, cap, 1) != 0 ||
-      grow((void **) &c->start, 2 * c->n, 2 * cap, 8) != 0 ||
-      grow((void **) &c->length, c->n, cap, 8) != 0)
-  {
-    return -100;
-  }
-  c->capacity = cap;
-  return 0;
-}
-
-// the edges of one finish while they are found
+// the edges of one finish while they are found: a list without records
 struct EdgeList
 {
-  uint64_t n = 0, capacity = 0;
   uint32_t *e1 = nullptr, *e2 = nullptr;
   uint64_t *value = nullptr;
+  ResidentList list;
+  EdgeList()
+  {
+    list.records = false;
+    list.column(&e1);
+    list.column(&e2);
+    list.column(&value);
+  }
   ~EdgeList()
   {
-    vsa_dev_free(e1);
-    vsa_dev_free(e2);
-    vsa_dev_free(value);
-  }
-  int reserve(uint64_t need)
-  {
-    if (need <= capacity)
-    {
-      return 0;
-    }
-    const uint64_t cap = std::max<uint64_t>(need, 2 * capacity);
-    if (grow((void **) &e1, n, cap, 4) != 0 ||
-        grow((void **) &e2, n, cap, 4) != 0 ||
-        grow((void **) &value, n, cap, 8) != 0)
-    {
-      return -100;
-    }
-    capacity = cap;
-    return 0;
+    list.release();
   }
 };
 
@@ -349,8 +312,8 @@ uint64_t chunkslots()
 int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
               double *ms)
 {
-  const uint64_t nrefs = 2 * c->n;
-  DevBuf idx, sidx, sstart, temp, send, count, off;
+  const uint64_t nrefs = 2 * c->list.n;
+  DevBuf idx, sidx, sstart, send, count, off;
   Timer tsort(nullptr), twindow(nullptr), tpairs(nullptr);
   if (idx.alloc(nrefs * 4) != 0 || sidx.alloc(nrefs * 4) != 0 ||
       sstart.alloc(nrefs * 8) != 0 || send.alloc(nrefs * 8) != 0 ||
@@ -362,12 +325,11 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
   k_tc_iota<<<gridfor(nrefs), TC_BLOCK, 0, nullptr>>>(idx.as<uint32_t>(),
                                                       nrefs);
   VSA_HIP(hipGetLastError());
-  const unsigned int endbit = c->sortbits;
-  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-    return rocprim::radix_sort_pairs(p, tb, c->start, sstart.as<uint64_t>(),
-                                     idx.as<uint32_t>(), sidx.as<uint32_t>(),
-                                     (size_t) nrefs, 0u, endbit, nullptr);
-  }));
+  if (sortpairs(c->start, sstart.as<uint64_t>(), idx.as<uint32_t>(),
+                sidx.as<uint32_t>(), nrefs, c->sortbits, nullptr) != 0)
+  {
+    return -100;
+  }
   tsort.stop();
   twindow.start();
   k_mc_window<<<gridfor(nrefs + 1), TC_BLOCK, 0, nullptr>>>(
@@ -405,7 +367,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
     VSA_HIP(hipGetLastError());
     pf.first = first.as<uint64_t>();
     pf.c0 = c0;
-    pf.base = edges.n;
+    pf.base = edges.list.n;
     pf.e1 = pf.e2 = nullptr;
     pf.value = nullptr;
     if (tc_count<1, VSA_CL_CLASSES>(pf, ns, offsets, totals) != 0)
@@ -415,15 +377,15 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
     const uint64_t m = totals[VSA_MC_EDGE];
     st->samematch += totals[VSA_MC_SAME];
     st->below += totals[VSA_MC_BELOW];
-    if (edges.n + m >= 0xFFFFFFFFull)
+    if (edges.list.n + m >= 0xFFFFFFFFull)
     {
       VSA_ERROR("vsa_matchcluster_finish: %lu edges: only fewer than 2^32 - 1 "
-                "are covered", (unsigned long) (edges.n + m));
+                "are covered", (unsigned long) (edges.list.n + m));
       return VSA_NOT_COVERED;
     }
     if (m > 0)
     {
-      if (edges.reserve(edges.n + m) != 0)
+      if (edges.list.reserve(edges.list.n + m) != 0)
       {
         return -100;
       }
@@ -434,7 +396,7 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
       {
         return -100;
       }
-      edges.n += m;
+      edges.list.n += m;
     }
     // (first and offsets are read by the kernels of this pass)
     VSA_HIP(hipStreamSynchronize(nullptr));
@@ -448,21 +410,6 @@ int findedges(vsa_matchcluster *c, EdgeList &edges, vsa_matchclusterstats *st,
 }
 
 #include "matchcluster_erate.inc"
-
-int needfinished(const vsa_matchcluster *c, const char *who)
-{
-  if (c == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  if (!c->finished)
-  {
-    VSA_ERROR("%s: vsa_matchcluster_finish has not seen the last list", who);
-    return -2;
-  }
-  return 0;
-}
 
 // the edges grouped by cluster into host memory, once per finish
 int group(vsa_matchcluster *c, const char *who)
@@ -487,7 +434,7 @@ int group(vsa_matchcluster *c, const char *who)
     // labels on the host, as that of vsa_cluster_edges does)
     Timer t(nullptr);
     t.start();
-    const int rc = cl_group(c->e1, c->e2, ne, c->res.label, c->n, ncl, order,
+    const int rc = cl_group(c->e1, c->e2, ne, c->res.label, c->list.n, ncl, order,
                             c->edgestart, who);
     if (rc != 0)
     {
@@ -514,52 +461,34 @@ int group(vsa_matchcluster *c, const char *who)
   return 0;
 }
 
-// out[t] = the record of match who[t] (and its flag), t < k, in device memory
-int gatherrecords(const vsa_matchcluster *c, const uint64_t *who, uint64_t k,
-                  vsa_match *out, uint8_t *outflags)
+// order[t] = the number of member t of the clusters, t < res.inclusters, in
+// device memory
+int memberorder(const vsa_matchcluster *c, DevBuf &order)
 {
+  const uint64_t k = c->res.inclusters;
   std::vector<uint32_t> h(k);
   for (uint64_t t = 0; t < k; t++)
   {
-    h[t] = (uint32_t) who[t];
+    h[t] = (uint32_t) c->res.members[t];
   }
-  DevBuf order;
   if (order.alloc(k * 4) != 0)
   {
     return -100;
   }
-  VSA_HIP(hipMemcpy(order.p, h.data(), k * 4, hipMemcpyHostToDevice));
-  const RecGather g = {c->recs, c->flags, out, outflags};
-  k_cl_gather<RecGather><<<gridfor(k), TC_BLOCK, 0, nullptr>>>(
-      g, order.as<uint32_t>(), k);
-  VSA_HIP(hipGetLastError());
-  VSA_HIP(hipStreamSynchronize(nullptr));
+  if (k > 0)
+  {
+    VSA_HIP(hipMemcpy(order.p, h.data(), k * 4, hipMemcpyHostToDevice));
+  }
   return 0;
 }
 
-// the records of all members into host memory, once per finish
-int gathermembers(vsa_matchcluster *c)
+vsa_matchcluster *newhandle(int device)
 {
-  if (c->gathered)
-  {
-    return 0;
-  }
-  const uint64_t k = c->res.inclusters;
-  c->memberrecs.resize(k);
-  if (k > 0)
-  {
-    DevBuf drecs, dflags;
-    if (drecs.alloc(k * sizeof(vsa_match)) != 0 || dflags.alloc(k) != 0 ||
-        gatherrecords(c, c->res.members, k, drecs.as<vsa_match>(),
-                      dflags.as<uint8_t>()) != 0)
-    {
-      return -100;
-    }
-    VSA_HIP(hipMemcpy(c->memberrecs.data(), drecs.p, k * sizeof(vsa_match),
-                      hipMemcpyDeviceToHost));
-  }
-  c->gathered = true;
-  return 0;
+  vsa_matchcluster *c = new vsa_matchcluster();
+  c->device = c->layout.device = c->list.device = device;
+  c->list.column(&c->start, 2);
+  c->list.column(&c->length);
+  return c;
 }
 
 } // namespace
@@ -570,13 +499,8 @@ extern "C" void vsa_matchcluster_close(vsa_matchcluster *c)
   {
     return;
   }
-  (void) hipSetDevice(c->device);
-  (void) hipFree(c->d_qstart);
-  (void) hipFree(c->d_qlen);
-  vsa_dev_free(c->recs);
-  vsa_dev_free(c->flags);
-  vsa_dev_free(c->start);
-  vsa_dev_free(c->length);
+  c->layout.release();
+  c->list.release();
   vsa_dev_free(c->e1);
   vsa_dev_free(c->e2);
   vsa_dev_free(c->value);
@@ -606,8 +530,7 @@ extern "C" int vsa_matchcluster_open(const vsa_sinkparams *layout,
   {
     return -100;
   }
-  vsa_matchcluster *c = new vsa_matchcluster();
-  c->device = device;
+  vsa_matchcluster *c = newhandle(device);
   c->view = view;
   c->rules = rules;
   memset(&c->stats, 0, sizeof c->stats);
@@ -616,8 +539,8 @@ extern "C" int vsa_matchcluster_open(const vsa_sinkparams *layout,
                                  layout->kind == VSA_SINK_SELF
                                      ? (uint64_t) 0
                                      : layout->querytotallength));
-  if (upload_queryview(view.nq, &c->view.qstart, &c->view.qlen, &c->d_qstart,
-                       &c->d_qlen, "vsa_matchcluster_open") != 0)
+  if (c->layout.upload("vsa_matchcluster_open", view.nq, &c->view.qstart,
+                       &c->view.qlen, 0, nullptr) != 0)
   {
     vsa_matchcluster_close(c);
     return -100;
@@ -654,8 +577,7 @@ extern "C" int vsa_eratecluster_open(const vsa_sinkparams *layout,
   {
     return -100;
   }
-  vsa_matchcluster *c = new vsa_matchcluster();
-  c->device = device;
+  vsa_matchcluster *c = newhandle(device);
   c->view = view;
   c->rules.mode = VSA_MATCHCLUSTER_ERATE;
   c->rules.maxgapsize = c->rules.minpercentoverlap = 0;
@@ -671,74 +593,45 @@ extern "C" int vsa_eratecluster_open(const vsa_sinkparams *layout,
 extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
                                     int palindromic)
 {
-  if (c == nullptr || r == nullptr)
-  {
-    VSA_ERROR("vsa_matchcluster_add: NULL argument");
-    return -1;
-  }
-  if (r->packbits != 0)
-  {
-    VSA_ERROR("vsa_matchcluster_add: a packed candidate result has no records "
-              "to cluster");
-    return VSA_NOT_COVERED;
-  }
-  if (palindromic && c->view.kind == VSA_SINK_SELF)
-  {
-    VSA_ERROR("vsa_matchcluster_add: palindromic self matches are the "
-              "selfpalindromic form");
-    return VSA_NOT_COVERED;
-  }
-  if (r->device != c->device)
-  {
-    VSA_ERROR("vsa_matchcluster_add: result on device %d, clustering on "
-              "device %d", r->device, c->device);
-    return -2;
-  }
   // the index 2m + side of a reference is 32 bit: fewer than 2^31 matches
-  if (c->n + r->count >= MC_MAXMATCHES)
+  const int g = gate("vsa_matchcluster_add", "cluster", "clustering", c, r,
+                     [&]() { return selfform(c->view.kind, palindromic); },
+                     MC_MAXMATCHES, "matches: only fewer than 2^31");
+  if (g != 0)
   {
-    VSA_ERROR("vsa_matchcluster_add: %lu matches: only fewer than 2^31 are "
-              "covered", (unsigned long) (c->n + r->count));
-    return VSA_NOT_COVERED;
+    return g < 0 ? g : 0;
   }
-  if (enter(c->device) != 0)
-  {
-    return -100;
-  }
-  if (r->count == 0)
-  {
-    return 0;
-  }
-  if (reserve(c, c->n + r->count) != 0)
-  {
-    return -100;
-  }
-  DevBuf bad;
-  if (bad.alloc(24) != 0)
+  ScratchWords bad;
+  if (c->list.reserve(c->list.n + r->count) != 0 || bad.alloc(3) != 0)
   {
     return -100;
   }
   Timer t(nullptr);
   t.start();
-  VSA_HIP(hipMemsetAsync(bad.p, 0, 24, nullptr));
+  if (bad.zero(0, 3) != 0)
+  {
+    return -100;
+  }
   if (c->rules.mode == VSA_MATCHCLUSTER_ERATE)
   {
     k_er_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
-        c->view, c->text, c->textlength, r->matches, r->count, c->n, c->recs,
-        c->flags, c->start, c->length, bad.as<unsigned long long>());
+        c->view, c->text, c->textlength, r->matches, r->count, c->list.n,
+        c->list.recs, c->list.flags, c->start, c->length, bad.word(0));
   } else
   {
     k_mc_refs<<<gridfor(r->count), TC_BLOCK, 0, nullptr>>>(
-        c->view, r->matches, r->count, palindromic != 0, c->n,
+        c->view, r->matches, r->count, palindromic != 0, c->list.n,
         c->sortbits < 64 ? (uint64_t) 1 << c->sortbits : ~(uint64_t) 0,
-        c->recs, c->flags, c->start, c->length,
-        bad.as<unsigned long long>());
+        c->list.recs, c->list.flags, c->start, c->length, bad.word(0));
   }
   VSA_HIP(hipGetLastError());
   t.stop();
   // (erate: records that do not fit, records too long, the longest length)
   uint64_t bads[3] = {0, 0, 0};
-  VSA_HIP(hipMemcpy(bads, bad.p, 24, hipMemcpyDeviceToHost));
+  if (bad.fetch(0, 3, bads) != 0)
+  {
+    return -100;
+  }
   const uint64_t nbad = bads[0];
   c->ms[MC_REFS] += t.ms();
   if (bads[1] != 0)
@@ -747,22 +640,15 @@ extern "C" int vsa_matchcluster_add(vsa_matchcluster *c, const vsa_result *r,
               "erate covers shorter ones", (unsigned long) bads[1]);
     return VSA_NOT_COVERED;
   }
-  if (nbad != 0 && c->rules.mode == VSA_MATCHCLUSTER_ERATE)
-  {
-    VSA_ERROR("vsa_matchcluster_add: %lu records do not fit the layout (a "
-              "match that leaves the text or holds a separator)",
-              (unsigned long) nbad);
-    return -2;
-  }
   if (nbad != 0)
   {
-    // (what the kernel wrote lies behind the matches that count)
-    VSA_ERROR("vsa_matchcluster_add: %lu records do not fit the layout (a "
-              "query number outside the set, a match that leaves its "
-              "sequence or the text)", (unsigned long) nbad);
-    return -2;
+    return misfits("vsa_matchcluster_add", nbad,
+                   c->rules.mode == VSA_MATCHCLUSTER_ERATE
+                       ? "a match that leaves the text or holds a separator"
+                       : "a query number outside the set, a match that leaves "
+                         "its sequence or the text");
   }
-  c->n += r->count;
+  c->list.n += r->count;
   c->longest = std::max(c->longest, bads[2]);
   c->finished = false;
   return 0;
@@ -781,10 +667,10 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
   }
   vsa_matchclusterstats st;
   memset(&st, 0, sizeof st);
-  st.matches = c->n;
+  st.matches = c->list.n;
   EdgeList edges;
   double ms[VSA_MATCHCLUSTER_STAGES] = {0, 0, 0, 0, 0, 0};
-  if (c->n >= 2)
+  if (c->list.n >= 2)
   {
     const int rc = c->rules.mode == VSA_MATCHCLUSTER_ERATE
                        ? findedges_erate(c, edges, &st, ms)
@@ -796,11 +682,11 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
   }
   std::vector<uint32_t> f1, f2;
   uint64_t changed = 0;
-  if (edges.n > 0)
+  if (edges.list.n > 0)
   {
     Timer t(nullptr);
     t.start();
-    const int rc = cl_forest(c->n, edges.e1, edges.e2, edges.n, f1, f2,
+    const int rc = cl_forest(c->list.n, edges.e1, edges.e2, edges.list.n, f1, f2,
                              &st.rounds, "vsa_matchcluster_finish");
     if (rc != 0)
     {
@@ -811,7 +697,7 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
     ms[MC_FOREST] += t.ms();
   }
   vsa_clresult res;
-  const int rc = vsa_cl_replay(c->n, f1.data(), f2.data(), f1.size(), &changed,
+  const int rc = vsa_cl_replay(c->list.n, f1.data(), f2.data(), f1.size(), &changed,
                                &res);
   if (rc != 0)
   {
@@ -832,7 +718,7 @@ extern "C" int vsa_matchcluster_finish(vsa_matchcluster *c)
   c->e1 = edges.e1;
   c->e2 = edges.e2;
   c->value = edges.value;
-  c->nedges = edges.n;
+  c->nedges = edges.list.n;
   edges.e1 = edges.e2 = nullptr;
   edges.value = nullptr;
   vsa_cl_freeresult(&c->res);
@@ -897,9 +783,9 @@ extern "C" int vsa_matchcluster_labels(const vsa_matchcluster *c,
     VSA_ERROR("vsa_matchcluster_labels: NULL argument");
     return -1;
   }
-  if (c->n > 0)
+  if (c->list.n > 0)
   {
-    memcpy(label, c->res.label, c->n * 8);
+    memcpy(label, c->res.label, c->list.n * 8);
   }
   return 0;
 }
@@ -948,39 +834,13 @@ extern "C" int vsa_matchcluster_records(vsa_matchcluster *c,
     return -1;
   }
   *records = nullptr;
-  if (enter(c->device) != 0)
+  DevBuf order;
+  if (enter(c->device) != 0 || memberorder(c, order) != 0)
   {
     return -100;
   }
-  const uint64_t k = c->res.inclusters;
-  vsa_result *res = newresult(c->device);
-  if (k == 0)
-  {
-    *records = res;
-    return 0;
-  }
-  ResultGuard guard = {res};
-  DevBuf oflags;
-  if (oflags.alloc(k) != 0 ||
-      vsa_dev_alloc((void **) &res->matches, k * sizeof(vsa_match)) != 0 ||
-      gatherrecords(c, c->res.members, k, res->matches,
-                    oflags.as<uint8_t>()) != 0)
-  {
-    return -100;
-  }
-  if (palindromic != nullptr)
-  {
-    VSA_HIP(hipMemcpy(palindromic, oflags.p, k, hipMemcpyDeviceToHost));
-  }
-  res->count = k;
-  res->stats.count = k;
-  if (sumlengths(res->matches, k, nullptr, &res->stats.sumlength) != 0)
-  {
-    return -100;
-  }
-  guard.r = nullptr;
-  *records = res;
-  return 0;
+  return records_of(c->list, order.as<uint32_t>(), c->res.inclusters,
+                    palindromic, nullptr, records);
 }
 
 extern "C" int64_t vsa_matchcluster_format(const vsa_matchcluster *c,
@@ -996,7 +856,7 @@ extern "C" int64_t vsa_matchcluster_format(const vsa_matchcluster *c,
     VSA_ERROR("vsa_matchcluster_format: NULL argument");
     return -1;
   }
-  return vsa_mc_format(c->n, &c->res, buffer, capacity);
+  return vsa_mc_format(c->list.n, &c->res, buffer, capacity);
 }
 
 extern "C" int64_t vsa_matchcluster_format_cluster(vsa_matchcluster *c,
@@ -1031,9 +891,17 @@ extern "C" int64_t vsa_matchcluster_format_cluster(vsa_matchcluster *c,
   const uint64_t first = c->res.clusterstart[cnum],
                  size = c->res.clusterstart[cnum + 1] - first,
                  e0 = c->edgestart[cnum], ne = c->edgestart[cnum + 1] - e0;
-  if (gathermembers(c) != 0)
+  if (!c->gathered)
   {
-    return -100;
+    // the records of all members into host memory, once per finish
+    DevBuf order;
+    if (memberorder(c, order) != 0 ||
+        members_to_host(c->list, order.as<uint32_t>(), c->res.inclusters,
+                        c->memberrecs) != 0)
+    {
+      return -100;
+    }
+    c->gathered = true;
   }
   return vsa_matchcluster_format_host(
       sink, c->rules.mode, c->res.members + first,

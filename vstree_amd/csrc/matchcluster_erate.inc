@@ -92,34 +92,37 @@ k_er_refs(vsa_selrules view, const uint8_t *__restrict__ text,
           uint64_t *__restrict__ length, unsigned long long *__restrict__ bad)
 {
   const uint64_t i = vsa_bid() * TC_BLOCK + threadIdx.x;
-  if (i >= n)
+  int rc = 0;
+  if (i < n)
   {
-    return;
+    const vsa_match m = in[i];
+    vsa_selvalues v;
+    rc = vsa_sel_values(&view, &m, 0, &v) != 0 ? -2 : 0;
+    if (rc == 0)
+    {
+      rc = vsa_er_checkplace(textlength, v.length1, v.position1, v.position2);
+    }
+    if (rc == 0 && (er_hasseparator(text + v.position1, v.length1) ||
+                    er_hasseparator(text + v.position2, v.length1)))
+    {
+      rc = -2;
+    }
+    if (rc == 0)
+    {
+      atomicMax(&bad[2], (unsigned long long) v.length1);
+      const uint64_t at = base + i;
+      recs[at] = m;
+      flags[at] = 0;
+      start[2 * at] = v.position1;
+      start[2 * at + 1] = v.position2;
+      length[at] = v.length1;
+    }
+    else if (rc != -2)
+    {
+      atomicAdd(&bad[1], 1ull);
+    }
   }
-  const vsa_match m = in[i];
-  vsa_selvalues v;
-  int rc = vsa_sel_values(&view, &m, 0, &v) != 0 ? -2 : 0;
-  if (rc == 0)
-  {
-    rc = vsa_er_checkplace(textlength, v.length1, v.position1, v.position2);
-  }
-  if (rc == 0 && (er_hasseparator(text + v.position1, v.length1) ||
-                  er_hasseparator(text + v.position2, v.length1)))
-  {
-    rc = -2;
-  }
-  if (rc != 0)
-  {
-    atomicAdd(&bad[rc == -2 ? 0 : 1], 1ull);
-    return;
-  }
-  atomicMax(&bad[2], (unsigned long long) v.length1);
-  const uint64_t at = base + i;
-  recs[at] = m;
-  flags[at] = 0;
-  start[2 * at] = v.position1;
-  start[2 * at + 1] = v.position2;
-  length[at] = v.length1;
+  wave_count(rc == -2, &bad[0]);
 }
 
 // ---- rows -----------------------------------------------------------------------
@@ -491,7 +494,7 @@ struct EdgeF
 int findedges_erate(vsa_matchcluster *c, EdgeList &edges,
                     vsa_matchclusterstats *st, double *ms)
 {
-  const uint64_t n = c->n;
+  const uint64_t n = c->list.n;
   const uint32_t E = c->errorrate;
   DevBuf count, off;
   Timer trows(nullptr), tpairs(nullptr);
@@ -595,7 +598,7 @@ int findedges_erate(vsa_matchcluster *c, EdgeList &edges,
       ef.si = wf.si;
       ef.sj = wf.sj;
       ef.answer = ans;
-      ef.base = edges.n;
+      ef.base = edges.list.n;
       ef.e1 = ef.e2 = nullptr;
       ef.value = nullptr;
       DevBuf eoffsets;
@@ -605,15 +608,15 @@ int findedges_erate(vsa_matchcluster *c, EdgeList &edges,
         return -100;
       }
       const uint64_t m = etotals[0];
-      if (edges.n + m >= 0xFFFFFFFFull)
+      if (edges.list.n + m >= 0xFFFFFFFFull)
       {
         VSA_ERROR("vsa_matchcluster_finish: %lu edges: only fewer than 2^32 - "
-                  "1 are covered", (unsigned long) (edges.n + m));
+                  "1 are covered", (unsigned long) (edges.list.n + m));
         return VSA_NOT_COVERED;
       }
       if (m > 0)
       {
-        if (edges.reserve(edges.n + m) != 0)
+        if (edges.list.reserve(edges.list.n + m) != 0)
         {
           return -100;
         }
@@ -624,7 +627,7 @@ int findedges_erate(vsa_matchcluster *c, EdgeList &edges,
         {
           return -100;
         }
-        edges.n += m;
+        edges.list.n += m;
       }
     }
     // (the buffers of this pass are read by its kernels)
@@ -632,7 +635,7 @@ int findedges_erate(vsa_matchcluster *c, EdgeList &edges,
   }
   tpairs.stop();
   VSA_HIP(hipStreamSynchronize(nullptr));
-  st->below = total - edges.n;
+  st->below = total - edges.list.n;
   ms[MC_WINDOW] += trows.ms();
   ms[MC_PAIRS] += tpairs.ms();
   return 0;

@@ -350,14 +350,16 @@ int sortbykey(uint64_t *keys_in, uint64_t *keys_out, vsa_match *in,
   return 0;
 }
 
-// stable sort of (key, index) pairs by the whole key (fewer than 2^32 pairs)
+// stable sort of (key, index) pairs by key bits [0, endbit) (fewer than 2^32
+// pairs)
 int sortpairs(uint64_t *keys_in, uint64_t *keys_out, uint32_t *vals_in,
-              uint32_t *vals_out, uint64_t n, hipStream_t stream)
+              uint32_t *vals_out, uint64_t n, unsigned int endbit,
+              hipStream_t stream)
 {
   DevBuf temp;
   VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
     return rocprim::radix_sort_pairs(p, tb, keys_in, keys_out, vals_in,
-                                     vals_out, (size_t) n, 0u, 64u, stream);
+                                     vals_out, (size_t) n, 0u, endbit, stream);
   }));
   return 0;
 }

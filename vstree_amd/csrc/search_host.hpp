@@ -1,8 +1,9 @@
 // Host-side helpers shared by the translation units of the search engine
 // (esa_search.hip, selfmum_search.hip, approx_entry.hip, selfmatch_entry.hip,
 // candidate_partition.hip, index_derive.hip, index_build.hip) and of the
-// handles that post-process match lists (coverage.hip, select.hip,
-// cluster.hip, matchcluster.hip).  Small things are inline here; what
+// handles that post-process match lists (coverage.hip, and through
+// resident_list.hpp select.hip, cluster.hip, matchcluster.hip, chain.hip).
+// Small things are inline here; what
 // instantiates rocPRIM is defined once, in search_common.hip.  (rocprim_run()
 // is a template over its caller's lambda: it instantiates nothing of rocPRIM
 // by itself.)
@@ -201,10 +202,11 @@ VSA_HIDDEN int sortbykey(uint64_t *keys_in, uint64_t *keys_out, vsa_match *in,
                          vsa_match *out, uint64_t n, unsigned int endbit,
                          hipStream_t stream);
 
-// stable sort of (key, index) pairs by the whole key (fewer than 2^32 pairs)
+// stable sort of (key, index) pairs by key bits [0, endbit) (fewer than 2^32
+// pairs)
 VSA_HIDDEN int sortpairs(uint64_t *keys_in, uint64_t *keys_out,
                          uint32_t *vals_in, uint32_t *vals_out, uint64_t n,
-                         hipStream_t stream);
+                         unsigned int endbit, hipStream_t stream);
 
 VSA_HIDDEN vsa_result *newresult(int device);
 

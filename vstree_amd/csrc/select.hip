@@ -32,7 +32,7 @@
 //   next vsa_select_add: a key that is not smaller never enters the pool.
 // Positions, lengths and every index into a list are 64 bit; only the
 // indices inside the selection (at most N < 2^32) are 32 bit.
-#include "search_host.hpp"
+#include "resident_list.hpp"
 #include "select_internal.h"
 #include "tile_compact.inc"
 
@@ -46,7 +46,7 @@ struct vsa_select
   int selfpalindromic = 0; // the layout says vmatch -p IDX: not covered
   vsa_selctx ctx;
   vsa_selrules drules; // ctx.rules with the pointers into device memory
-  uint64_t *d_qstart = nullptr, *d_qlen = nullptr;
+  DeviceLayout layout;
   double *d_table = nullptr, *d_hequot = nullptr;
   int64_t *d_linestart = nullptr;
   // -best: the selection, sorted, distinct: key word w of entry j at
@@ -56,9 +56,7 @@ struct vsa_select
   vsa_match *srecs = nullptr;
   uint64_t worst[SEL_W];
   // filters only: the list so far
-  uint64_t nlist = 0;
-  vsa_match *lrecs = nullptr;
-  uint8_t *lflags = nullptr;
+  ResidentList list;
   std::vector<uint8_t> lastflags; // of the list finish delivered last
   uint64_t lastpasses = 0;        // histogram kernels of the last add
   vsa_selectstats stats;
@@ -443,8 +441,8 @@ int upload_tables(vsa_select *s)
   s->drules.table = s->d_table;
   s->drules.linestart = s->d_linestart;
   s->drules.hequot = s->d_hequot;
-  s->drules.qstart = s->d_qstart;
-  s->drules.qlen = s->d_qlen;
+  s->drules.qstart = s->layout.d_qstart;
+  s->drules.qlen = s->layout.d_qlen;
   return 0;
 }
 
@@ -476,35 +474,18 @@ int ensure_tables(vsa_select *s, const vsa_result *r)
   return grew > 0 ? upload_tables(s) : 0;
 }
 
-// what vsa_select_add and vsa_select_evalues refuse
+// the gate of vsa_select_add and vsa_select_evalues
 int check_list(const vsa_select *s, const vsa_result *r, int palindromic,
                const char *who)
 {
-  if (r->packbits != 0)
-  {
-    VSA_ERROR("%s: a packed candidate result has no records to select from",
-              who);
-    return VSA_NOT_COVERED;
-  }
-  if (s->selfpalindromic)
-  {
-    VSA_ERROR("%s: lists of vmatch -p IDX (selfpalindromic) are not covered",
-              who);
-    return VSA_NOT_COVERED;
-  }
-  if (s->ctx.rules.kind == VSA_SINK_SELF && palindromic)
-  {
-    VSA_ERROR("%s: palindromic self matches are the selfpalindromic form",
-              who);
-    return VSA_NOT_COVERED;
-  }
-  if (r->device != s->device)
-  {
-    VSA_ERROR("%s: result on device %d, selection on device %d", who,
-              r->device, s->device);
-    return -2;
-  }
-  return 0;
+  return gate(who, "select from", "selection", s, r,
+              [&]() {
+                return s->selfpalindromic
+                           ? "lists of vmatch -p IDX (selfpalindromic) are "
+                             "not covered"
+                           : selfform(s->ctx.rules.kind, palindromic);
+              },
+              0, nullptr);
 }
 
 // The threshold of the radix select: T = the key of rank `need` (1 based,
@@ -596,8 +577,8 @@ int sel_sortunique(const uint64_t *keys, uint64_t stride,
     k_sel_gatherword<<<gridfor(n), TC_BLOCK, 0, nullptr>>>(
         keys + (uint64_t) w * stride, selected, p, n, kw.as<uint64_t>());
     VSA_HIP(hipGetLastError());
-    if (sortpairs(kw.as<uint64_t>(), kw2.as<uint64_t>(), p, p2, n, nullptr) !=
-        0)
+    if (sortpairs(kw.as<uint64_t>(), kw2.as<uint64_t>(), p, p2, n, 64,
+                  nullptr) != 0)
     {
       return -100;
     }
@@ -774,14 +755,11 @@ extern "C" void vsa_select_close(vsa_select *s)
   {
     return;
   }
-  (void) hipSetDevice(s->device);
+  s->layout.release();
   free_tables(s);
-  (void) hipFree(s->d_qstart);
-  (void) hipFree(s->d_qlen);
   vsa_dev_free(s->skeys);
   vsa_dev_free(s->srecs);
-  vsa_dev_free(s->lrecs);
-  vsa_dev_free(s->lflags);
+  s->list.release();
   vsa_selctx_free(&s->ctx);
   delete s;
 }
@@ -838,7 +816,7 @@ extern "C" int vsa_select_open(const vsa_sinkparams *layout,
     return -100;
   }
   vsa_select *s = new vsa_select();
-  s->device = device;
+  s->device = s->layout.device = s->list.device = device;
   s->selfpalindromic = layout->selfpalindromic != 0;
   memset(&s->stats, 0, sizeof s->stats);
   memset(s->worst, 0, sizeof s->worst);
@@ -852,8 +830,7 @@ extern "C" int vsa_select_open(const vsa_sinkparams *layout,
   }
   // (upload_tables makes drules of ctx.rules and points it to the copies)
   const uint64_t *hstart = s->ctx.rules.qstart, *hlen = s->ctx.rules.qlen;
-  rc = upload_queryview(nq, &hstart, &hlen, &s->d_qstart, &s->d_qlen,
-                        "vsa_select_open");
+  rc = s->layout.upload("vsa_select_open", nq, &hstart, &hlen, 0, nullptr);
   if (rc == 0)
   {
     rc = upload_tables(s);
@@ -870,22 +847,13 @@ extern "C" int vsa_select_open(const vsa_sinkparams *layout,
 extern "C" int vsa_select_add(vsa_select *s, const vsa_result *r,
                               int palindromic)
 {
-  if (s == nullptr || r == nullptr)
-  {
-    VSA_ERROR("vsa_select_add: NULL argument");
-    return -1;
-  }
   int rc = check_list(s, r, palindromic, "vsa_select_add");
-  if (rc != 0)
+  if (rc < 0)
   {
     return rc;
   }
-  if (enter(s->device) != 0)
-  {
-    return -100;
-  }
   s->lastpasses = 0;
-  if (r->count == 0)
+  if (rc > 0)
   {
     return 0;
   }
@@ -930,32 +898,19 @@ extern "C" int vsa_select_add(vsa_select *s, const vsa_result *r,
   else if (m > 0)
   {
     // filters only: the survivors behind the list so far
-    DevBuf recs, flags;
-    if (recs.alloc((s->nlist + m) * sizeof(vsa_match)) != 0 ||
-        flags.alloc(s->nlist + m) != 0)
+    if (s->list.reserve(s->list.n + m) != 0)
     {
       return -100;
     }
-    if (s->nlist > 0)
-    {
-      VSA_HIP(hipMemcpyAsync(recs.p, s->lrecs, s->nlist * sizeof(vsa_match),
-                             hipMemcpyDeviceToDevice, nullptr));
-      VSA_HIP(hipMemcpyAsync(flags.p, s->lflags, s->nlist,
-                             hipMemcpyDeviceToDevice, nullptr));
-    }
-    kf.lrecs = recs.as<vsa_match>();
-    kf.lflags = flags.as<uint8_t>();
-    kf.base = s->nlist;
+    kf.lrecs = s->list.recs;
+    kf.lflags = s->list.flags;
+    kf.base = s->list.n;
     if (tc_emit<1>(kf, r->count, offsets) != 0)
     {
       return -100;
     }
     VSA_HIP(hipStreamSynchronize(nullptr));
-    vsa_dev_free(s->lrecs);
-    vsa_dev_free(s->lflags);
-    s->lrecs = (vsa_match *) recs.release();
-    s->lflags = (uint8_t *) flags.release();
-    s->nlist += m;
+    s->list.n += m;
   }
   s->stats.seen += r->count;
   s->stats.rejected += totals[2];
@@ -976,8 +931,8 @@ extern "C" int vsa_select_finish(vsa_select *s, vsa_result **selected)
     return -100;
   }
   const bool best = s->ctx.params.bestnumber > 0;
-  const uint64_t n = best ? s->nsel : s->nlist;
-  const vsa_match *recs = best ? s->srecs : s->lrecs;
+  const uint64_t n = best ? s->nsel : s->list.n;
+  const vsa_match *recs = best ? s->srecs : s->list.recs;
   s->lastflags.assign(n, 0);
   s->stats.containedremoved = 0;
   DevBuf flags;
@@ -993,7 +948,7 @@ extern "C" int vsa_select_finish(vsa_select *s, vsa_result **selected)
           s->skeys + (uint64_t) (SEL_W - 1) * n, n, flags.as<uint8_t>());
       VSA_HIP(hipGetLastError());
     }
-    VSA_HIP(hipMemcpy(s->lastflags.data(), best ? flags.p : s->lflags, n,
+    VSA_HIP(hipMemcpy(s->lastflags.data(), best ? flags.p : s->list.flags, n,
                       hipMemcpyDeviceToHost));
   }
   if (best && s->ctx.params.sortmode != VSA_SORT_NONE && n > 0)
@@ -1076,7 +1031,7 @@ extern "C" int vsa_select_evalues(vsa_select *s, const vsa_result *r,
                                   int palindromic, double *evalues,
                                   uint64_t capacity)
 {
-  if (s == nullptr || r == nullptr || (evalues == nullptr && capacity > 0))
+  if (evalues == nullptr && capacity > 0)
   {
     VSA_ERROR("vsa_select_evalues: NULL argument");
     return -1;
@@ -1084,11 +1039,7 @@ extern "C" int vsa_select_evalues(vsa_select *s, const vsa_result *r,
   int rc = check_list(s, r, palindromic, "vsa_select_evalues");
   if (rc != 0)
   {
-    return rc;
-  }
-  if (enter(s->device) != 0)
-  {
-    return -100;
+    return rc < 0 ? rc : 0;
   }
   const uint64_t n = std::min(capacity, r->count);
   if (n == 0)
