@@ -15,7 +15,8 @@ it cannot: -mum -l 20, 100 bp reads against a 300 Mbp index,
            compare n symbols per chunk on a text of one period)
 
 each with the walk off (VSA_TUNE=16, first and last) and with chunks of 4, 8
-and 32 offsets: ms per call and kernel_searches.
+and 32 offsets, through the tile queue and (VSA_TUNE=32) through the workgroup
+tiles: ms per call and kernel_searches.
 
   walk_probe.py [n [reads [calls]]]        all runs, one process each
   walk_probe.py --one KIND [n reads calls] one run under the environment given
@@ -85,8 +86,11 @@ def main():
     vals = [int(float(x)) for x in args]
     n, nq, calls = vals + [300_000_000, 1_000_000, 20][len(vals):]
     for kind in ("random", "repeat"):
-        for tune, chunk in (("16", None), (None, "4"), (None, "8"),
-                            (None, "32"), ("16", None)):
+        # (VSA_TUNE=32: the workgroup tiles of k_query_search_planned instead
+        # of the tile queue, the same chunks)
+        for tune, chunk in (("16", None), (None, "4"), ("32", "4"),
+                            (None, "8"), ("32", "8"), (None, "32"),
+                            ("32", "32"), ("16", None)):
             env = dict(os.environ)
             env.pop("VSA_TUNE", None)
             env.pop("VSA_WALK_CHUNK", None)

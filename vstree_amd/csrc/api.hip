@@ -524,6 +524,7 @@ extern "C" int vsa_index_clone(const vsa_index *src, int device,
   ix->D = src->D;
   ix->tune = src->tune;
   ix->walkshift = src->walkshift;
+  ix->walkgridasked = src->walkgridasked;
   ix->qspeedup = src->qspeedup;
   ix->slotwords = src->slotwords;
   ix->firstspecial = src->firstspecial;

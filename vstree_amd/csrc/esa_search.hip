@@ -13,7 +13,9 @@
 //                            sort by work-item number = reference order
 //   mum_workplan.inc     K2a k_mum_first / k_mum_plan: which offsets of a read
 //                            can be MUM candidates at all; K2 in its planned
-//                            form, k_query_search_planned
+//                            forms: k_mum_walk_tiles (MUM: wavefronts that
+//                            take tiles of planned reads from a queue) and
+//                            k_query_search_planned (MEM; VSA_TUNE=32)
 //   mem_workplan.inc     K2m k_repeat_bits / k_mem_plan: which offsets of a
 //                            read a MEM search has to look at
 //   candidate_sort.inc   K4s candidates as (sort key, value) pairs thrown
@@ -60,10 +62,18 @@
 //   VSA_TUNE=16       no walk in the planned MUM search: every planned offset
 //                     is located, one per work-item (A/B and cross-check of
 //                     the walk, mum_workplan.inc)
-//                     (a bit mask: 2, 4, 8 and 16 combine)
+//   VSA_TUNE=32       the planned MUM search through the workgroup tiles of
+//                     k_query_search_planned: a lane keeps one chunk per pass
+//                     (A/B and cross-check of the tile queue,
+//                     k_mum_walk_tiles)
+//                     (a bit mask: 2, 4, 8, 16 and 32 combine)
 //   VSA_WALK_CHUNK=N  offsets of a plan range that one lane walks (a power of
-//                     two, else the next one below; default 32; 1 is
-//                     VSA_TUNE=16)
+//                     two, else the next one below; default 8; 1 is
+//                     VSA_TUNE=16: every planned offset a work-item of its
+//                     own)
+//   VSA_WALK_GRID=N   workgroups of the tile queue (default 0: as many as the
+//                     device holds at once; for tests and probes: 1 makes four
+//                     wavefronts take every tile)
 //   VSA_NO_ESA8=1     no deep tables: the reference walk, probe for probe
 //   VSA_DEEP_PREFIX=D their depth (default ceil(log4 n), at most 16)
 //   VSA_FORCE_WIDE=1  64-bit device tables whatever the size of the text
@@ -960,13 +970,71 @@ int mum_plan(QueryRun &st, const DevIndex<IDX> &ix)
   return 0;
 }
 
-// the search kernel: the planned form behind a plan, else every (query,
-// offset) pair (MEM, and MUM batches without a plan)
+// does the planned MUM search take its chunks from the tile queue
+// (k_mum_walk_tiles)?  VSA_TUNE=32: the workgroup tiles of
+// k_query_search_planned, which the MEM plan goes through anyway
+bool tilequeue(const QueryRun &st)
+{
+  return st.fromplan && st.domum && (st.index->tune & 32u) == 0;
+}
+
+// workgroups of the tile queue: VSA_WALK_GRID, or what the device holds at
+// once (the kernel's occupancy times the compute units; kept in the index)
+template <typename IDX>
+int walkgrid(const QueryRun &st, uint32_t *grid)
+{
+  const vsa_index *index = st.index;
+  if (index->walkgridasked != 0)
+  {
+    *grid = index->walkgridasked;
+    return 0;
+  }
+  hipError_t e = hipSuccess;
+  withform(st.form, [&](auto deep, auto, auto rows, auto) {
+    uint32_t &kept = index->walkgrid[deep ? 1 : 0][rows ? 1 : 0];
+    if (kept == 0)
+    {
+      int percu = 0, cus = 0;
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &percu, k_mum_walk_tiles<IDX, deep, rows>, 256, 0);
+      if (e == hipSuccess)
+      {
+        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  index->device);
+      }
+      if (e == hipSuccess)
+      {
+        kept = (uint32_t) std::max(percu, 1) * (uint32_t) std::max(cus, 1);
+      }
+    }
+    *grid = kept;
+  });
+  VSA_HIP(e);
+  return 0;
+}
+
+// the search kernel: the planned form behind a plan (nplanblocks workgroups:
+// of the tile queue, or one per perblock reads), else every (query, offset)
+// pair (MEM, and MUM batches without a plan); regions: the cursor regions the
+// tile queue spreads its workgroups over (a power of two)
 template <typename IDX>
 void launch_search(QueryRun &st, const DevIndex<IDX> &ix,
-                   uint64_t nplanblocks)
+                   uint64_t nplanblocks, uint32_t regions)
 {
   withform(st.form, [&](auto deep, auto, auto rows, auto) {
+    auto tiles = [&]() {
+      // (the tile counter: behind the cursors, zeroed with them)
+      unsigned long long *cursors = st.cursor.as<unsigned long long>();
+      k_mum_walk_tiles<IDX, deep, rows>
+          <<<vsa_grid(nplanblocks), 256, 0, st.stream>>>(
+              ix, st.qs, st.dbase, st.perquery, st.wplan.as<PlanRanges>(),
+              st.wcount.as<uint32_t>(), st.wlist.as<uint32_t>(), st.nlistword,
+              cursors + (size_t) VSA_CURSOR_SHARDS * VSA_CURSOR_STRIDE,
+              st.searchlength, st.rawout.as<vsa_match>(),
+              st.rawkeys.as<uint64_t>(), st.shardcap, regions - 1, cursors,
+              st.rec.packbits, st.rec.valbits,
+              st.blocksum.as<PlannedWork>(), st.index->walkshift);
+    };
     auto planned = [&](auto mum) {
       k_query_search_planned<IDX, 256, deep, rows, mum>
           <<<vsa_grid(nplanblocks), 256, 0, st.stream>>>(
@@ -987,7 +1055,10 @@ void launch_search(QueryRun &st, const DevIndex<IDX> &ix,
               st.cursor.as<unsigned long long>(), st.rec.packbits,
               st.rec.valbits);
     };
-    if (st.fromplan && st.domum)
+    if (tilequeue(st))
+    {
+      tiles();
+    } else if (st.fromplan && st.domum)
     {
       planned(std::true_type());
     } else if (st.fromplan)
@@ -1010,55 +1081,72 @@ void launch_search(QueryRun &st, const DevIndex<IDX> &ix,
 // report at most one match per work-item but typically about one per query;
 // MEM is unbounded.  The kernel counts what it needs and never writes past a
 // region's capacity; on overflow of any region run again with regions of the
-// size that was asked for.
+// size that was asked for.  (The tile queue: which wavefront takes which tile
+// differs from launch to launch, and with it what a region receives.  Its
+// second attempt writes everything into ONE region with room for all that
+// was asked for, a number that does not depend on the schedule; the regions
+// behind it stay empty and are never looked at.)
 template <typename IDX>
 int search(QueryRun &st, const DevIndex<IDX> &ix)
 {
   const uint32_t nshards = VSA_CURSOR_SHARDS;
   // (reads per workgroup of k_query_search_planned<IDX, 256>)
   const uint64_t perblock = 256 * (st.domum ? VSA_WALK_READS : 1);
-  const uint64_t nplanblocks = (st.queries->nq + perblock - 1) / perblock;
+  uint64_t nplanblocks = (st.queries->nq + perblock - 1) / perblock;
+  // entries of blocksum: one per workgroup, or (the tile queue) per wavefront
+  uint64_t persum = 1;
   size_t rbytes = 0;
+  if (tilequeue(st))
+  {
+    uint32_t grid = 0;
+    if (walkgrid<IDX>(st, &grid))
+    {
+      return -100;
+    }
+    nplanblocks = grid;
+    persum = 4;
+  }
+  const uint64_t nsums = persum * nplanblocks;
   if (st.fromplan)
   {
     // the work of the planned search (the locates it really makes -- the
     // walk leaves planned offsets out -- and the offsets planned): summed per
-    // workgroup by the kernel, reduced behind it into the fifth and sixth
-    // word of the shard summary
-    if (st.blocksum.alloc((vsa_grid_blocks(nplanblocks) + 1) *
+    // workgroup or wavefront by the kernel, reduced behind it into the fifth
+    // and sixth word of the shard summary
+    if (st.blocksum.alloc((persum * vsa_grid_blocks(nplanblocks) + 1) *
                           sizeof(PlannedWork)))
     {
       return -100;
     }
     VSA_HIP(rocprim::reduce(nullptr, rbytes, st.blocksum.as<PlannedWork>(),
                             (PlannedWork *) nullptr, PlannedWork{0, 0},
-                            (size_t) nplanblocks, PlannedWorkPlus(),
-                            st.stream));
+                            (size_t) nsums, PlannedWorkPlus(), st.stream));
     if (st.rtemp.alloc(rbytes))
     {
       return -100;
     }
   }
-  if (st.cursor.alloc((size_t) nshards * VSA_CURSOR_STRIDE * 8) ||
-      st.doff.alloc(nshards * 8) || st.summary.alloc(6 * 8))
+  // (one more line behind the cursors: the tile counter of k_mum_walk_tiles)
+  const size_t cursorbytes = (size_t) (nshards + 1) * VSA_CURSOR_STRIDE * 8;
+  if (st.cursor.alloc(cursorbytes) || st.doff.alloc(nshards * 8) ||
+      st.summary.alloc(6 * 8))
   {
     return -100;
   }
   st.shardcap =
       std::max<uint64_t>((st.queries->nq * 2 / nshards) * 5 / 4 + 64, 256);
   uint64_t maxshard = 0;
+  uint32_t regions = nshards;
   for (int attempt = 0; attempt < 2; attempt++)
   {
-    if (st.rawout.alloc(nshards * st.shardcap * st.rec.recsize) ||
-        st.rawkeys.alloc(nshards * st.shardcap * 8))
+    if (st.rawout.alloc(regions * st.shardcap * st.rec.recsize) ||
+        st.rawkeys.alloc(regions * st.shardcap * 8))
     {
       return -100;
     }
-    VSA_HIP(hipMemsetAsync(st.cursor.p, 0,
-                           (size_t) nshards * VSA_CURSOR_STRIDE * 8,
-                           st.stream));
+    VSA_HIP(hipMemsetAsync(st.cursor.p, 0, cursorbytes, st.stream));
     st.tsearch.start();
-    launch_search(st, ix, nplanblocks);
+    launch_search(st, ix, nplanblocks, regions);
     st.tsearch.stop();
     VSA_HIP(hipGetLastError());
     if (st.fromplan)
@@ -1067,8 +1155,7 @@ int search(QueryRun &st, const DevIndex<IDX> &ix)
       VSA_HIP(rocprim::reduce(
           st.rtemp.p, rbytes, st.blocksum.as<PlannedWork>(),
           reinterpret_cast<PlannedWork *>(st.summary.as<uint64_t>() + 4),
-          PlannedWork{0, 0}, (size_t) nplanblocks, PlannedWorkPlus(),
-          st.stream));
+          PlannedWork{0, 0}, (size_t) nsums, PlannedWorkPlus(), st.stream));
     }
     // where each region goes in the dense list, how much there is
     const uint64_t *sm = st.summary.as<uint64_t>();
@@ -1100,6 +1187,11 @@ int search(QueryRun &st, const DevIndex<IDX> &ix)
       return 0;
     }
     st.shardcap = maxshard;
+    if (tilequeue(st))
+    {
+      regions = 1;
+      st.shardcap = st.needed;
+    }
   }
   VSA_ERROR("match buffer overflow: %llu > %llu",
             (unsigned long long) maxshard, (unsigned long long) st.shardcap);

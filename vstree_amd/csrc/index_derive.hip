@@ -147,6 +147,11 @@ int vsa_index_make_esa8(vsa_index *ix)
     {
       ix->walkshift++;
     }
+    // workgroups of the tile queue (0: as many as the device holds)
+    const char *wg = getenv("VSA_WALK_GRID");
+    const int grid = wg != nullptr ? atoi(wg) : 0;
+    ix->walkgridasked = (grid >= 1 && grid <= (1 << 20)) ? (uint32_t) grid : 0;
+    memset(ix->walkgrid, 0, sizeof ix->walkgrid);
   }
   if (ix->esa8 != nullptr)
   {

@@ -408,7 +408,8 @@ struct PlannedWorkPlus
 // locate and, on packed batches, a second copy of the walk for the reads with
 // a special symbol: 74 to 76 VGPRs.  Held to 64 they spill 10 to 13 VGPRs to
 // scratch (40 to 56 bytes per lane), at 7 wavefronts (72 VGPRs) the packed
-// form still spills 20 bytes: 6 wavefronts per SIMD, no scratch.
+// form still spills 20 bytes: 6 wavefronts per SIMD, no scratch.  (The tile
+// queue: 66 VGPRs on bytes, 80 on rows, no scratch -- profiles/r16.)
 #ifndef VSA_WALK_WAVES
 #define VSA_WALK_WAVES 6
 #endif
@@ -420,8 +421,9 @@ struct PlannedWorkPlus
 #ifndef VSA_WALK_READS
 #define VSA_WALK_READS 4
 #endif
-// K2 for a planned MUM batch, straight from the plans: a workgroup takes BLK
-// consecutive queries, lays their planned offsets out in LDS (a scan of the
+// K2 in its workgroup tiles, straight from the plans (the MEM plan; the MUM
+// forms under VSA_TUNE=32 -- by default they take the tile queue,
+// k_mum_walk_tiles below): a workgroup takes BLK consecutive queries, lays their planned offsets out in LDS (a scan of the
 // counts, the ranges of every plan) and walks that list BLK work-items at a
 // time -- no expanded work list in memory (8 bytes per work-item written and
 // read back in round 1), no scan over all queries, no host round trip before
@@ -697,6 +699,316 @@ k_query_search_planned(const DevIndex<IDX> ix, const DevQueries qs,
       }
       blocksum[vsa_bid()].locates = s;
     }
+  }
+}
+
+// ---- the tile queue ------------------------------------------------------
+//
+// K2 for a planned MUM batch as every call runs it (VSA_TUNE=32 takes the MUM
+// forms back to k_query_search_planned above): the same chunks through the
+// same step, vsa_walk_step, handed out differently.  Above, a lane keeps one
+// chunk per pass and a workgroup keeps its slot until its slowest wavefront is
+// done; a chunk takes 1 to 8 dependent locates on the headline, so the
+// wavefronts went round with about 0.6 of their lanes busy.  Here a wavefront
+// works on its own: it takes tiles of 64 consecutive entries of the list of
+// the reads that have a plan (the list k_mum_plan works from, its length read
+// on the device) from one counter in global memory, and in front of EVERY
+// step its free lanes take the next chunks of the tile, the next tile when
+// that one is used up.  Nothing waits for another wavefront: no
+// __syncthreads(), the launch is as large as the device holds (any other size
+// is as right), and the reads without a plan are never looked at.
+//
+// A tile lies in the wavefront's own slice of LDS: the reads, their ranges and
+// the exclusive prefix of their chunk counts.  Chunk i of the tile belongs to
+// the last read k with pre[k] <= i and is its (i - pre[k])-th chunk, ranges
+// cut from their first offset on as above.  Head and tail of the tile are
+// wavefront-uniform.
+struct WalkTile
+{
+  PlanRanges pr[64];
+  uint32_t q[64];
+  uint32_t pre[65];
+};
+// chunks of reads of a packed batch that have a special symbol, set aside for
+// the byte form of the step (read, first | off << 16): filled up to 64 + 63
+#define VSA_WALK_ASIDE 128
+struct WalkAside
+{
+  uint32_t q[VSA_WALK_ASIDE], r[VSA_WALK_ASIDE];
+};
+
+// what one lane wrote into the wavefront's slice before, every lane of it sees
+// behind this (LDS operations of a wavefront run in order: the compiler has to
+// keep them so, nothing has to be waited for)
+__device__ __forceinline__ void vsa_wave_lds_fence()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the lanes of `mask` in front of this one
+__device__ __forceinline__ uint32_t vsa_rank_in(uint64_t mask)
+{
+  return __builtin_amdgcn_mbcnt_hi(
+      (uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
+}
+
+// the r-th chunk of a plan: [first, off]
+__device__ __forceinline__ void vsa_plan_chunk(const PlanRanges &p, uint32_t r,
+                                               uint32_t cshift,
+                                               uint32_t &first, uint32_t &off)
+{
+  const uint32_t chunk = 1u << cshift;
+#pragma unroll
+  for (int k = 0; k < VSA_PLAN_RANGES; k++)
+  {
+    const uint32_t rf = p.r[k] & 0xFFFFu, len = p.r[k] >> 16,
+                   nchunks = (len + chunk - 1) >> cshift;
+    if (r < nchunks)
+    {
+      const uint32_t at = r << cshift, n = len - at < chunk ? len - at : chunk;
+      first = rf + at;
+      off = first + n - 1;
+      r = 0xFFFFFFFFu; // found: no later range takes it
+    } else if (r != 0xFFFFFFFFu)
+    {
+      r -= nchunks;
+    }
+  }
+}
+
+// blocksum[4 * workgroup + wavefront] = the locates the wavefront made and the
+// planned offsets of the tiles it took.  tilecounter: zero at the launch.
+// ROWS: the chunks of a read with a special symbol go to the aside list and
+// are walked on the read's bytes, 64 at a time, when no lane has a chunk of
+// the other kind (with 64 of them waiting nothing new is handed out), so that
+// the two forms of the step never run with each other's state alive.
+template <typename IDX, bool DEEP = true, bool ROWS = false>
+__global__ void __launch_bounds__(256, VSA_WALK_WAVES)
+k_mum_walk_tiles(const DevIndex<IDX> ix, const DevQueries qs,
+                 const uint64_t *__restrict__ base, uint32_t perquery,
+                 const PlanRanges *__restrict__ plan,
+                 const uint32_t *__restrict__ plancount,
+                 const uint32_t *__restrict__ list,
+                 const uint64_t *__restrict__ nlistword,
+                 unsigned long long *__restrict__ tilecounter,
+                 uint32_t searchlength, vsa_match *__restrict__ out,
+                 uint64_t *__restrict__ outkey, uint64_t shardcap,
+                 uint32_t shardmask, unsigned long long *__restrict__ cursors,
+                 uint32_t packbits, uint32_t valbits,
+                 PlannedWork *__restrict__ blocksum, uint32_t chunkshift)
+{
+  __shared__ WalkTile tiles[4];
+  __shared__ WalkAside asides[ROWS ? 4 : 1];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  WalkTile &tile = tiles[wave];
+  WalkAside &aside = asides[ROWS ? wave : 0];
+  const uint64_t nlist = *nlistword & 0xFFFFFFFFull;
+  const uint32_t shard = vsa_bid() & shardmask;
+  // of the wavefront: the chunks of its tile are [0, tail), [0, head) are
+  // handed out; the counter has run out; chunks set aside
+  uint32_t head = 0, tail = 0, naside = 0;
+  bool exhausted = false;
+  // of the lane: its chunk [first, off] of read q, off comes down
+  bool active = false;
+  uint32_t off = 0, first = 0, q = 0, qlen = qs.uniformlen;
+  uint32_t locates = 0, offsets = 0;
+  const uint8_t *qstart = qs.symbols;
+  for (;;)
+  {
+    // hand-out: all lanes are here together
+    uint64_t freemask = __ballot(!active);
+    while (freemask != 0 && !(ROWS && naside >= 64))
+    {
+      if (head == tail)
+      {
+        if (exhausted)
+        {
+          break;
+        }
+        // the next tile
+        unsigned long long mine = 0;
+        if (lane == 0)
+        {
+          mine = atomicAdd(tilecounter, 1ull);
+        }
+        const uint64_t t0 =
+            ((uint64_t) __builtin_amdgcn_readfirstlane((uint32_t) (mine >> 32))
+             << 32) |
+            __builtin_amdgcn_readfirstlane((uint32_t) mine);
+        if (t0 * 64 >= nlist)
+        {
+          exhausted = true;
+          break;
+        }
+        const uint64_t t = t0 * 64 + lane;
+        uint32_t tq = 0, nch = 0;
+        PlanRanges p;
+#pragma unroll
+        for (int g = 0; g < VSA_PLAN_RANGES; g++)
+        {
+          p.r[g] = 0;
+        }
+        if (t < nlist)
+        {
+          tq = list[t];
+          const uint32_t c = plancount[tq];
+          p = plan[tq];
+          offsets += c;
+          if (c > 0)
+          {
+#pragma unroll
+            for (int g = 0; g < VSA_PLAN_RANGES; g++)
+            {
+              nch += ((p.r[g] >> 16) + (1u << chunkshift) - 1) >> chunkshift;
+            }
+          }
+        }
+        const uint32_t incl = vsa_wave_inclusive_sum(nch);
+        vsa_wave_lds_fence(); // (the last tile has been read)
+        tile.q[lane] = tq;
+        tile.pr[lane] = p;
+        tile.pre[lane + 1] = incl;
+        if (lane == 0)
+        {
+          tile.pre[0] = 0;
+        }
+        vsa_wave_lds_fence();
+        head = 0;
+        tail = __builtin_amdgcn_readlane(incl, 63);
+        continue;
+      }
+      // the free lanes take chunks [head, head + take) by their rank
+      const uint32_t nfree = (uint32_t) __popcll(freemask),
+                     take = nfree < tail - head ? nfree : tail - head,
+                     rank = vsa_rank_in(freemask);
+      const bool took = !active && rank < take;
+      bool flagged = false;
+      if (took)
+      {
+        const uint32_t i = head + rank;
+        // last k with pre[k] <= i
+        uint32_t lo = 0;
+#pragma unroll
+        for (uint32_t d = 32; d >= 1; d >>= 1)
+        {
+          if (tile.pre[lo + d] <= i)
+          {
+            lo += d;
+          }
+        }
+        q = tile.q[lo];
+        vsa_plan_chunk(tile.pr[lo], i - tile.pre[lo], chunkshift, first, off);
+        if constexpr (ROWS)
+        {
+          RowQuery rq;
+          QSrc src;
+          flagged = vsa_row_of(qs, q, qs.uniformlen, rq, src);
+        } else
+        {
+          if (qs.dense)
+          {
+            qstart = qs.symbols + (uint64_t) q * qs.uniformlen;
+          } else
+          {
+            qstart = qs.symbols + qs.start[q];
+            qlen = (uint32_t) qs.length[q];
+          }
+        }
+        active = !flagged;
+      }
+      head += take;
+      if constexpr (ROWS)
+      {
+        const uint64_t fmask = __ballot(flagged);
+        if (flagged)
+        {
+          const uint32_t at = naside + vsa_rank_in(fmask);
+          aside.q[at] = q;
+          aside.r[at] = first | (off << 16);
+        }
+        naside += (uint32_t) __popcll(fmask);
+      }
+      freemask = __ballot(!active);
+    }
+    if (!__any(active))
+    {
+      if constexpr (ROWS)
+      {
+        if (naside > 0)
+        {
+          // the chunks set aside, on their reads' bytes
+          vsa_wave_lds_fence();
+          for (uint32_t a0 = 0; a0 < naside; a0 += 64)
+          {
+            const bool mine = a0 + lane < naside;
+            uint32_t aq = 0, afirst = 0, aoff = 0;
+            RowQuery arq;
+            QSrc src;
+            arq.row = qs.rows;
+            arq.valid = 0;
+            src.row = qs.rows;
+            src.bytes = nullptr;
+            src.pos = src.m = 0;
+            if (mine)
+            {
+              aq = aside.q[a0 + lane];
+              afirst = aside.r[a0 + lane] & 0xFFFFu;
+              aoff = aside.r[a0 + lane] >> 16;
+              (void) vsa_row_of(qs, aq, qs.uniformlen, arq, src);
+            }
+            locates += vsa_walk_chunk<IDX, true, false>(
+                ix, qs, mine, src, nullptr, qlen, afirst, aoff, aq, base,
+                perquery, searchlength, out, outkey, shardcap, shard, cursors,
+                packbits, valbits);
+          }
+          vsa_wave_lds_fence();
+          naside = 0;
+          // (no lane had a chunk: nothing of the lanes' own state is carried
+          // through the walk above)
+          q = first = off = 0;
+          continue;
+        }
+      }
+      break; // no chunk left in the tile, no tile left in the list
+    }
+    if constexpr (DEEP && ROWS)
+    {
+      // (the row from the number of the read: nothing but q travels round
+      // the loop)
+      RowQuery rq;
+      QSrc src;
+      rq.row = qs.rows + (uint64_t) q * qs.roww;
+      rq.valid = qlen;
+      src.row = rq.row;
+      src.bytes = nullptr;
+      src.pos = 0;
+      src.m = (int32_t) qlen;
+      vsa_walk_step<IDX, true, true>(ix, qs, active, src, &rq, qlen, first,
+                                     off, q, base, perquery, searchlength, out,
+                                     outkey, shardcap, shard, cursors, packbits,
+                                     valbits, locates);
+    } else
+    {
+      vsa_walk_step<IDX, DEEP, false>(ix, qs, active, qstart, nullptr, qlen,
+                                      first, off, q, base, perquery,
+                                      searchlength, out, outkey, shardcap,
+                                      shard, cursors, packbits, valbits,
+                                      locates);
+    }
+  }
+  uint64_t sum = locates | ((uint64_t) offsets << 32);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1)
+  {
+    // (a wavefront takes fewer than 2^32 locates: no carry)
+    sum += vsa_shfl64(sum, (int) lane ^ d);
+  }
+  if (lane == 0)
+  {
+    blocksum[vsa_bid() * 4 + wave] =
+        PlannedWork{sum & 0xFFFFFFFFull, sum >> 32};
   }
 }
 

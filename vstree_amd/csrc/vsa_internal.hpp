@@ -94,15 +94,20 @@ struct DevIndex
 #define VSA_LEFTSPECIAL (1ull << 63) // ... is not a regular one / does not exist
 
 // offsets of a plan range that one lane of the planned MUM search walks (a
-// power of two; mum_workplan.inc).  Headline, ms per step, one run each: 2.66 /
-// 2.50 / 2.57 / 2.72 / 2.60 at 2 / 4 / 8 / 16 / 32 against the parent's 2.88 to
-// 2.91.  Chunks of 4 are the fastest there,
-// but on reads from repeats, where a lane can skip nothing and a wavefront
-// goes round once per offset of its longest chunk, they are 11 % SLOWER than
-// no walk at all (7.12 against 6.39-6.43 ms per call); whole ranges in one
-// chunk are faster than no walk on both inputs (6.00 there): 32.
+// power of two; mum_workplan.inc).  Through the tile queue, where a lane that
+// is done takes the next chunk at once (one
+// run each): headline 2.59 / 2.41 / 2.42 / 2.48 / 2.49 ms per step at 2 / 4 /
+// 8 / 16 / 32 against the parent's 2.64; reads from repeats, where a lane can
+// skip nothing, 3.38 / 3.32 / 3.08 ms per call at 4 / 8 / 32 against 4.84
+// without the walk.  Whole ranges in one chunk make the fewest locates, but
+// the wavefronts end on their longest chunks with few lanes busy; chunks of 8
+// make more locates than whole ranges (5.17 M against 4.36 M on the probe's
+// random input) and, like every size tried, are faster than no walk on both
+// inputs: 8.  (Under the
+// workgroup tiles, VSA_TUNE=32, chunks of 4 and 8 are SLOWER than no walk on
+// the repeat input, 7.1 and 7.3 against 4.8 ms: round 13 chose 32.)
 #ifndef VSA_WALK_CHUNK
-#define VSA_WALK_CHUNK 32
+#define VSA_WALK_CHUNK 8
 #endif
 
 struct vsa_index
@@ -125,6 +130,13 @@ struct vsa_index
   // log2 of the offsets one lane of the planned MUM search walks
   // (VSA_WALK_CHUNK, VSA_TUNE & 16: esa_search.hip, mum_workplan.inc)
   uint32_t walkshift;
+  // workgroups of the tile queue of the planned MUM search (k_mum_walk_tiles):
+  // walkgridasked = VSA_WALK_GRID, 0: as many as the device holds at once,
+  // the occupancy of the kernel times the compute units -- walkgrid[deep
+  // tables][packed rows], made by the first call that runs that form of the
+  // kernel and kept (0 before)
+  uint32_t walkgridasked;
+  mutable uint32_t walkgrid[2][2];
   uint32_t qspeedup; // vsa_index_set_queryspeedup: 0 or 2 (default)
   uint64_t querysepposition;
   int hasindexedqueries;
