@@ -16,79 +16,40 @@
 #include <stdint.h>
 #include "vstree_amd.h"
 #include "chain_rules.h"
-
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 int vsa_ch_checklayout(const vsa_sinkparams *layout,
                        const vsa_chainparams *params, const char *who,
                        vsa_selrules *rules, vsa_clrules *seqs)
 {
+  int rc;
+
   if (layout == NULL || params == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
-    return -1;
+    return vsa_fail(-1, "%s: NULL argument", who);
   }
   if (params->thread)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: chain thread (closing the gaps of a "
-             "chain) is not covered", who);
-    return VSA_NOT_COVERED;
+    return vsa_fail(VSA_NOT_COVERED, "%s: chain thread (closing the gaps of "
+                    "a chain) is not covered", who);
   }
   if (params->kind < VSA_CHAIN_GLOBAL || params->kind > VSA_CHAIN_LOCAL_PERCENT)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: illegal kind %d", who, params->kind);
-    return -2;
+    return vsa_fail(-2, "%s: illegal kind %d", who, params->kind);
   }
   if (!(params->weightfactor > 0.0))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: the weight factor must be positive",
-             who);
-    return -2;
+    return vsa_fail(-2, "%s: the weight factor must be positive", who);
   }
   if (params->kind == VSA_CHAIN_LOCAL_BEST && params->value < 1)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: local Kb needs K >= 1", who);
-    return -2;
+    return vsa_fail(-2, "%s: local Kb needs K >= 1", who);
   }
-  if (layout->selfpalindromic)
+  if ((rc = vsa_layout_view(layout, who, VSA_NEEDS_NOSELFPAL |
+                            VSA_NEEDS_SEQUENCES | VSA_NEEDS_QUERIES,
+                            rules)) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of vmatch -p IDX "
-             "(selfpalindromic) are not covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (layout->kind == VSA_SINK_TRANSLATED ||
-      layout->kind == VSA_SINK_TRANSLATED_COMPLETE)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of a six-frame translated "
-             "batch (VSA_SINK_TRANSLATED) are not covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (layout->kind < VSA_SINK_COMPLETE ||
-      layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
-      layout->numofsequences == 0 ||
-      (layout->numofsequences > 1 && layout->markpos == NULL) ||
-      layout->totalquerylength + 1 > layout->totallength ||
-      (layout->kind != VSA_SINK_SELF && layout->numofqueries > 0 &&
-       (layout->querystart == NULL || layout->querylength == NULL)))
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: incomplete layout", who);
-    return -2;
-  }
-  /* the view of a match (select_rules.h); no E-value is looked at */
-  memset(rules, 0, sizeof *rules);
-  rules->kind = layout->kind;
-  rules->noevalue = 1;
-  rules->totallength = (double) layout->totallength;
-  if (layout->kind == VSA_SINK_SELF)
-  {
-    rules->hasindexedqueries = layout->totalquerylength > 0;
-    rules->dblenplus1 = layout->totallength - layout->totalquerylength;
-  } else
-  {
-    rules->nq = layout->numofqueries;
-    rules->qstart = layout->querystart;
-    rules->qlen = layout->querylength;
+    return rc;
   }
   memset(seqs, 0, sizeof *seqs);
   seqs->totallength = layout->totallength;
@@ -97,29 +58,13 @@ int vsa_ch_checklayout(const vsa_sinkparams *layout,
   return 0;
 }
 
-/* bounded text: the bytes that did not fit are counted, not written */
-typedef struct
-{
-  char *p;
-  uint64_t cap, len;
-} textbuf;
-
-static void put(textbuf *t, const char *s, size_t n)
-{
-  if (t->len + n < t->cap)
-  {
-    memcpy(t->p + t->len, s, n);
-  }
-  t->len += n;
-}
-
 /* outvmatchchain, chainvm.c:137-151 */
 int64_t vsa_chain_format_host(vsa_sink *sink, int flags, uint64_t nchains,
                               const uint64_t *number, const int64_t *score,
                               const uint64_t *start, const vsa_match *records,
                               char *buffer, uint64_t capacity)
 {
-  textbuf t = {buffer, capacity, 0};
+  vsa_textbuf t = {buffer, capacity, 0};
   char line[512];
   uint64_t c, k;
 
@@ -127,17 +72,13 @@ int64_t vsa_chain_format_host(vsa_sink *sink, int flags, uint64_t nchains,
       (nchains > 0 && (number == NULL || score == NULL || start == NULL ||
                        records == NULL)))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_format_host: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_chain_format_host: NULL argument");
   }
   for (c = 0; c < nchains; c++)
   {
-    const int n = snprintf(line, sizeof line,
-                           "# chain %lu: length %lu score %ld\n",
-                           (unsigned long) number[c],
-                           (unsigned long) (start[c + 1] - start[c]),
-                           (long) score[c]);
-    put(&t, line, (size_t) n);
+    vsa_putf(&t, "# chain %lu: length %lu score %ld\n",
+             (unsigned long) number[c],
+             (unsigned long) (start[c + 1] - start[c]), (long) score[c]);
     if (flags & VSA_CHAIN_SILENT)
     {
       continue;
@@ -150,18 +91,10 @@ int64_t vsa_chain_format_host(vsa_sink *sink, int flags, uint64_t nchains,
       {
         return w;
       }
-      put(&t, line, (size_t) w);
+      vsa_put(&t, line, (size_t) w);
     }
   }
-  if (t.len >= t.cap)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_format: %lu bytes do not fit a "
-             "buffer of %lu", (unsigned long) t.len + 1,
-             (unsigned long) t.cap);
-    return -3;
-  }
-  t.p[t.len] = '\0';
-  return (int64_t) t.len;
+  return vsa_endtext(&t, "vsa_chain_format");
 }
 
 /* ---- sorting --------------------------------------------------------------- */
@@ -328,8 +261,7 @@ int vsa_ch_grouprank(const uint64_t *seq1, const uint64_t *seq2,
 
   if (perm == NULL || tmp == NULL || num == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   for (i = 0; i < n; i++)
@@ -347,8 +279,7 @@ int vsa_ch_grouprank(const uint64_t *seq1, const uint64_t *seq2,
       if (first + 1 < i &&
           groupquicksort(perm, (int64_t) first, (int64_t) i - 1, seq2) != 0)
       {
-        snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-        rc = -1;
+        rc = vsa_fail(-1, "out of memory");
         goto done;
       }
       first = i;
@@ -674,6 +605,7 @@ int vsa_chain_host(const vsa_sinkparams *layout,
                    int64_t *score, uint64_t *start, uint64_t chaincapacity,
                    uint64_t *members, uint64_t membercapacity)
 {
+  static const char who[] = "vsa_chain_host";
   vsa_selrules view;
   vsa_clrules seqs;
   vsa_chainstats st;
@@ -685,22 +617,11 @@ int vsa_chain_host(const vsa_sinkparams *layout,
   uint32_t *order = NULL, *tmp = NULL, *rank = NULL;
   uint64_t i, first, runsize = 0, nproblems = 0;
   int onepair = 1, grouped, runtie = 0;
-  int rc = vsa_ch_checklayout(layout, params, "vsa_chain_host", &view, &seqs);
+  int rc = vsa_ch_checklayout(layout, params, who, &view, &seqs);
 
-  if (rc != 0)
+  if (rc != 0 || (rc = vsa_list_check(who, "records", matches, n)) != 0)
   {
     return rc;
-  }
-  if (matches == NULL && n > 0)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_host: NULL argument");
-    return -1;
-  }
-  if (n >= 0xFFFFFFFFull)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_host: %lu records: only fewer "
-             "than 2^32 - 1 are covered", (unsigned long) n);
-    return VSA_NOT_COVERED;
   }
   memset(&st, 0, sizeof st);
   memset(&p, 0, sizeof p);
@@ -728,28 +649,22 @@ int vsa_chain_host(const vsa_sinkparams *layout,
       p.first == NULL || p.perm == NULL || p.tree == NULL || p.key == NULL ||
       p.avail == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   p.r = params;
   p.tmp = tmp;
   for (i = 0; i < n; i++)
   {
-    const int pal = palindromic != NULL && palindromic[i] != 0;
-    if (pal && layout->kind == VSA_SINK_SELF)
+    int pal;
+    if ((rc = vsa_list_flag(who, layout->kind, palindromic, i, &pal)) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_host: palindromic self "
-               "matches are the selfpalindromic form");
-      rc = VSA_NOT_COVERED;
       goto done;
     }
     if (vsa_ch_view(&view, &seqs, params->weightfactor, matches + i, pal,
                     frag + i, seq1 + i, seq2 + i) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_host: record %lu does not "
-               "fit the layout", (unsigned long) i);
-      rc = -2;
+      rc = vsa_list_misfit(who, i);
       goto done;
     }
     if (seq1[i] != seq1[0] || seq2[i] != seq2[0])
@@ -855,11 +770,10 @@ int vsa_chain_host(const vsa_sinkparams *layout,
         start != NULL) && out.nchains > chaincapacity) ||
       (members != NULL && out.nmembers > membercapacity))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_chain_host: %lu chains of %lu "
-             "members, room for %lu and %lu", (unsigned long) out.nchains,
-             (unsigned long) out.nmembers, (unsigned long) chaincapacity,
-             (unsigned long) membercapacity);
-    rc = -3;
+    rc = vsa_fail(-3, "%s: %lu chains of %lu members, room for %lu and %lu",
+                  who, (unsigned long) out.nchains,
+                  (unsigned long) out.nmembers, (unsigned long) chaincapacity,
+                  (unsigned long) membercapacity);
   }
 done:
   free(frag);

@@ -14,9 +14,8 @@
 #include <stdint.h>
 #include "vstree_amd.h"
 #include "cluster_rules.h"
+#include "host_common.h"
 
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
 #define NIL 0xFFFFFFFFu
 
 typedef struct
@@ -53,8 +52,7 @@ static int clset_init(clset *s, uint64_t numofelems)
       s->first == NULL || s->last == NULL)
   {
     clset_free(s);
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -1;
+    return vsa_fail(-1, "out of memory");
   }
   memset(s->cnum, 0xFF, (size_t) numofelems * sizeof *s->cnum);
   return 0;
@@ -155,8 +153,7 @@ static int clset_result(const clset *s, vsa_clresult *r)
   if (r->clusterstart == NULL || r->members == NULL || r->label == NULL)
   {
     vsa_cl_freeresult(r);
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -1;
+    return vsa_fail(-1, "out of memory");
   }
   for (e = 0; e < s->numofelems; e++)
   {
@@ -178,10 +175,9 @@ static int clset_result(const clset *s, vsa_clresult *r)
     if (pos - r->clusterstart[k] != s->csize[c])
     {
       vsa_cl_freeresult(r);
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster: the chain of cluster %lu "
-               "does not have its %lu elements", (unsigned long) k,
-               (unsigned long) s->csize[c]);
-      return -101;
+      return vsa_fail(-101, "vsa_cluster: the chain of cluster %lu does not "
+                      "have its %lu elements", (unsigned long) k,
+                      (unsigned long) s->csize[c]);
     }
     k++;
   }
@@ -207,10 +203,9 @@ int vsa_cl_replay(uint64_t numofsequences, const uint32_t *e1,
     if (e1[i] >= numofsequences || e2[i] >= numofsequences || e1[i] == e2[i])
     {
       clset_free(&s);
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster: edge %lu (%lu, %lu) among "
-               "%lu sequences", (unsigned long) i, (unsigned long) e1[i],
-               (unsigned long) e2[i], (unsigned long) numofsequences);
-      return -101;
+      return vsa_fail(-101, "vsa_cluster: edge %lu (%lu, %lu) among %lu "
+                      "sequences", (unsigned long) i, (unsigned long) e1[i],
+                      (unsigned long) e2[i], (unsigned long) numofsequences);
     }
     ch += (uint64_t) clset_link(&s, e1[i], e2[i]);
   }
@@ -223,91 +218,47 @@ int vsa_cl_replay(uint64_t numofsequences, const uint32_t *e1,
   return rc;
 }
 
-/* bounded text: the bytes that did not fit are counted, not written */
-typedef struct
-{
-  char *p;
-  uint64_t cap, len;
-} textbuf;
-
-static void put(textbuf *t, const char *s, size_t n)
-{
-  if (t->len + n < t->cap)
-  {
-    memcpy(t->p + t->len, s, n);
-  }
-  t->len += n;
-}
-
-static void putnum(textbuf *t, const char *before, uint64_t v,
-                   const char *after)
-{
-  char tmp[96];
-  const int n = snprintf(tmp, sizeof tmp, "%s%lu%s", before, (unsigned long) v,
-                         after);
-  put(t, tmp, (size_t) n);
-}
-
 int64_t vsa_cl_format(const vsa_clresult *r, char *buffer, uint64_t capacity)
 {
-  textbuf t = {buffer, capacity, 0};
-  char line[256];
+  vsa_textbuf t = {buffer, capacity, 0};
   const uint64_t all = r->numofsequences, in = r->inclusters;
   uint64_t *dist, c, i;
-  int n;
 
   dist = calloc((size_t) all + 1, sizeof *dist);
   if (dist == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -1;
+    return vsa_fail(-1, "out of memory");
   }
   for (c = 0; c < r->clusters; c++)
   {
     dist[r->clusterstart[c + 1] - r->clusterstart[c]]++;
   }
-  n = snprintf(line, sizeof line, "# %lu cluster%s\n",
-               (unsigned long) r->clusters, r->clusters == 1 ? "" : "s");
-  put(&t, line, (size_t) n);
-  n = snprintf(line, sizeof line,
-               "# %lu elements out of %lu (%.2f%%) are in clusters\n",
-               (unsigned long) in, (unsigned long) all,
-               100.0 * (double) in / all);
-  put(&t, line, (size_t) n);
-  n = snprintf(line, sizeof line,
-               "# %lu elements out of %lu (%.2f%%) are singlets\n",
-               (unsigned long) (all - in), (unsigned long) all,
-               100.0 * (double) (all - in) / all);
-  put(&t, line, (size_t) n);
+  vsa_putf(&t, "# %lu cluster%s\n", (unsigned long) r->clusters,
+           r->clusters == 1 ? "" : "s");
+  vsa_putf(&t, "# %lu elements out of %lu (%.2f%%) are in clusters\n",
+           (unsigned long) in, (unsigned long) all, 100.0 * (double) in / all);
+  vsa_putf(&t, "# %lu elements out of %lu (%.2f%%) are singlets\n",
+           (unsigned long) (all - in), (unsigned long) all,
+           100.0 * (double) (all - in) / all);
   for (i = 2; i <= all; i++)
   {
     if (dist[i] > 0)
     {
-      n = snprintf(line, sizeof line, "# %lu cluster%s of size %lu\n",
-                   (unsigned long) dist[i], dist[i] > 1 ? "s" : "",
-                   (unsigned long) i);
-      put(&t, line, (size_t) n);
+      vsa_putf(&t, "# %lu cluster%s of size %lu\n", (unsigned long) dist[i],
+               dist[i] > 1 ? "s" : "", (unsigned long) i);
     }
   }
   free(dist);
   for (c = 0; c < r->clusters; c++)
   {
-    putnum(&t, "", c, ": ");
+    vsa_putf(&t, "%lu: ", (unsigned long) c);
     for (i = r->clusterstart[c]; i < r->clusterstart[c + 1]; i++)
     {
-      putnum(&t, " ", r->members[i], "");
+      vsa_putf(&t, " %lu", (unsigned long) r->members[i]);
     }
-    put(&t, "\n", 1);
+    vsa_put(&t, "\n", 1);
   }
-  if (t.len >= capacity)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster_format: %lu bytes do not fit "
-             "a buffer of %lu", (unsigned long) t.len + 1,
-             (unsigned long) capacity);
-    return -3;
-  }
-  buffer[t.len] = '\0';
-  return (int64_t) t.len;
+  return vsa_endtext(&t, "vsa_cluster_format");
 }
 
 int vsa_cl_checklayout(const vsa_sinkparams *layout,
@@ -315,38 +266,34 @@ int vsa_cl_checklayout(const vsa_sinkparams *layout,
 {
   if (layout == NULL || params == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
-    return -1;
+    return vsa_fail(-1, "%s: NULL argument", who);
   }
   if (layout->kind != VSA_SINK_SELF &&
       !(layout->kind == VSA_SINK_QUERY && layout->selfpalindromic))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: only self lists and lists of vmatch "
-             "-p IDX are covered, not layout kind %d", who, layout->kind);
-    return VSA_NOT_COVERED;
+    return vsa_fail(VSA_NOT_COVERED, "%s: only self lists and lists of "
+                    "vmatch -p IDX are covered, not layout kind %d", who,
+                    layout->kind);
   }
   if (layout->numofsequences == 1)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "option -dbcluster only possible for "
-             "index with at least two sequences");
-    return -2;
+    return vsa_fail(-2, "option -dbcluster only possible for index with at "
+                    "least two sequences");
   }
   if (layout->numofquerysequences > 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "option -dbcluster requires index without "
-             "query sequences");
-    return -2;
+    return vsa_fail(-2, "option -dbcluster requires index without query "
+                    "sequences");
   }
   if (layout->numofsequences >= 0xFFFFFFFFull)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu sequences: only fewer than 2^32 "
-             "- 1 are covered", who, (unsigned long) layout->numofsequences);
-    return VSA_NOT_COVERED;
+    return vsa_fail(VSA_NOT_COVERED, "%s: %lu sequences: only fewer than "
+                    "2^32 - 1 are covered", who,
+                    (unsigned long) layout->numofsequences);
   }
   if (layout->numofsequences == 0 || layout->markpos == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: incomplete layout", who);
-    return -2;
+    return vsa_fail(-2, "%s: incomplete layout", who);
   }
   return 0;
 }
@@ -359,6 +306,7 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
                      uint64_t *edgerecord, char *buffer, uint64_t capacity,
                      int64_t *written)
 {
+  static const char who[] = "vsa_cluster_host";
   vsa_clrules rules;
   vsa_clusterstats st;
   vsa_clresult res;
@@ -366,16 +314,12 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
   uint64_t *rec = NULL, *fill = NULL;
   uint64_t i, m = 0, count[VSA_CL_CLASSES] = {0};
   int64_t bytes = 0;
-  int rc = vsa_cl_checklayout(layout, params, "vsa_cluster_host");
+  int rc = vsa_cl_checklayout(layout, params, who);
 
-  if (rc != 0)
+  /* (any number of records: the sequences are what is counted in 32 bits) */
+  if (rc != 0 || (rc = vsa_list_check(who, NULL, matches, n)) != 0)
   {
     return rc;
-  }
-  if (matches == NULL && n > 0)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster_host: NULL argument");
-    return -1;
   }
   rules.totallength = layout->totallength;
   rules.numofsequences = layout->numofsequences;
@@ -387,8 +331,7 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
   rec = malloc((size_t) (n + 1) * sizeof *rec);
   if (e1 == NULL || e2 == NULL || rec == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   for (i = 0; i < n; i++)
@@ -398,20 +341,18 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
     int cls;
     if (!pal && layout->kind != VSA_SINK_SELF)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster_host: record %lu is a "
-               "direct match, the layout is that of vmatch -p IDX",
-               (unsigned long) i);
-      rc = VSA_NOT_COVERED;
+      rc = vsa_fail(VSA_NOT_COVERED, "%s: record %lu is a direct match, the "
+                    "layout is that of vmatch -p IDX", who,
+                    (unsigned long) i);
       goto done;
     }
     cls = vsa_cl_classify(&rules, &matches[i], pal, &s1, &s2);
     if (cls == VSA_CL_BAD)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_cluster_host: record %lu does not "
-               "fit the layout (a match that leaves its sequence, or a "
-               "sequence number outside the %lu of the index)",
-               (unsigned long) i, (unsigned long) rules.numofsequences);
-      rc = -2;
+      rc = vsa_fail(-2, "%s: record %lu does not fit the layout (a match "
+                    "that leaves its sequence, or a sequence number outside "
+                    "the %lu of the index)", who, (unsigned long) i,
+                    (unsigned long) rules.numofsequences);
       goto done;
     }
     count[cls]++;
@@ -450,8 +391,7 @@ int vsa_cluster_host(const vsa_sinkparams *layout,
     fill = calloc((size_t) res.clusters + 2, sizeof *fill);
     if (fill == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-      rc = -1;
+      rc = vsa_fail(-1, "out of memory");
       vsa_cl_freeresult(&res);
       goto done;
     }

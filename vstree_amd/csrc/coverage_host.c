@@ -6,9 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "vstree_amd.h"
-
-extern char *vsa_errbuf(void);
-#define ERRBUF_SIZE 1024
+#include "host_common.h"
 
 int64_t vsa_nomatch_format(const vsa_match *intervals, uint64_t n,
                            uint32_t showmode, uint64_t posoffset,
@@ -18,8 +16,7 @@ int64_t vsa_nomatch_format(const vsa_match *intervals, uint64_t n,
 
   if ((intervals == NULL && n > 0) || (buffer == NULL && capacity > 0))
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "vsa_nomatch_format: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_nomatch_format: NULL argument");
   }
   for (i = 0; i < n; i++)
   {
@@ -46,10 +43,8 @@ int64_t vsa_nomatch_format(const vsa_match *intervals, uint64_t n,
     }
     if (used + (uint64_t) len > capacity)
     {
-      snprintf(vsa_errbuf(), ERRBUF_SIZE,
-               "vsa_nomatch_format: buffer of %lu bytes is too small",
-               (unsigned long) capacity);
-      return -2;
+      return vsa_fail(-2, "vsa_nomatch_format: buffer of %lu bytes is too "
+                      "small", (unsigned long) capacity);
     }
     memcpy(buffer + used, line, (size_t) len);
     used += (uint64_t) len;
@@ -64,8 +59,7 @@ int vsa_mask_apply(const uint64_t *bits, uint64_t nbits, uint8_t *chars,
 
   if ((bits == NULL || chars == NULL) && nbits > 0)
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "vsa_mask_apply: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_mask_apply: NULL argument");
   }
   for (i = 0; i < nbits; i++)
   {
@@ -83,9 +77,8 @@ int vsa_mask_apply(const uint64_t *bits, uint64_t nbits, uint8_t *chars,
         chars[i] = (uint8_t) toupper(c);
       } else if (c != '*')
       {
-        snprintf(vsa_errbuf(), ERRBUF_SIZE,
-                 "cannot convert character %c to %s case", c, "upper");
-        return -4;
+        return vsa_fail(-4, "cannot convert character %c to %s case", c,
+                        "upper");
       }
     } else if (maskchar == VSA_MASK_TOLOWER)
     {
@@ -94,9 +87,8 @@ int vsa_mask_apply(const uint64_t *bits, uint64_t nbits, uint8_t *chars,
         chars[i] = (uint8_t) tolower(c);
       } else if (c != '*')
       {
-        snprintf(vsa_errbuf(), ERRBUF_SIZE,
-                 "cannot convert character %c to %s case", c, "lower");
-        return -4;
+        return vsa_fail(-4, "cannot convert character %c to %s case", c,
+                        "lower");
       }
     } else
     {

@@ -13,7 +13,7 @@
 #include <stdio.h>
 #include "vstree_amd.h"
 
-char *vsa_errbuf(void);
+#include "host_common.h"
 
 static int replay(vsa_result *result, int searchrc,
                   vsa_processmatch processmatch, void *info)
@@ -32,7 +32,7 @@ static int replay(vsa_result *result, int searchrc,
     m = (vsa_match *) malloc((size_t) n * sizeof(vsa_match));
     if (m == NULL)
     {
-      snprintf(vsa_errbuf(), 1024, "out of memory for %lu matches",
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "out of memory for %lu matches",
                (unsigned long) n);
       vsa_result_free(result);
       return -101;

@@ -29,8 +29,7 @@
 #include <sys/stat.h>
 #include "vstree_amd.h"
 
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 typedef struct
 {
@@ -55,13 +54,12 @@ static int mapfile(const char *indexname, const char *suffix,
     {
       return 1;
     }
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open \"%s\": %s", path,
-             strerror(errno));
-    return -1;
+    return vsa_fail(-1, "cannot open \"%s\": %s", path,
+                        strerror(errno));
   }
   if (fstat(fd, &st) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot stat \"%s\": %s", path,
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "cannot stat \"%s\": %s", path,
              strerror(errno));
     close(fd);
     return -1;
@@ -69,7 +67,7 @@ static int mapfile(const char *indexname, const char *suffix,
   if ((uint64_t) st.st_size != expected)
   {
     /* the reference's EXPECTED check, kurtz-basic/readvirt.c:118-119 */
-    snprintf(vsa_errbuf(), ERRSIZE,
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
              "mapping file \"%s\": %lu bytes, expected %lu", path,
              (unsigned long) st.st_size, (unsigned long) expected);
     close(fd);
@@ -80,7 +78,7 @@ static int mapfile(const char *indexname, const char *suffix,
     m->ptr = mmap(NULL, (size_t) expected, PROT_READ, MAP_PRIVATE, fd, 0);
     if (m->ptr == MAP_FAILED)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "cannot map \"%s\": %s", path,
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "cannot map \"%s\": %s", path,
                strerror(errno));
       m->ptr = NULL;
       close(fd);
@@ -122,9 +120,8 @@ static int readprj(const char *indexname, Prj *prj)
   fp = fopen(path, "r");
   if (fp == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open \"%s\": %s", path,
-             strerror(errno));
-    return -1;
+    return vsa_fail(-1, "cannot open \"%s\": %s", path,
+                        strerror(errno));
   }
   while (fgets(line, sizeof line, fp) != NULL)
   {
@@ -175,25 +172,20 @@ static int readprj(const char *indexname, Prj *prj)
   fclose(fp);
   if (!prj->have_totallength || !prj->have_prefixlength)
   {
-    snprintf(vsa_errbuf(), ERRSIZE,
-             "%s.prj: missing line totallength= or prefixlength=", indexname);
-    return -1;
+    return vsa_fail(-1, "%s.prj: missing line totallength= or "
+                    "prefixlength=", indexname);
   }
   if (!prj->have_integersize ||
       (prj->integersize != 32 && prj->integersize != 64))
   {
     /* kurtz-basic/multiseq-adv.c:1856-1872 */
-    snprintf(vsa_errbuf(), ERRSIZE,
-             "%s.prj contains illegal line defining the integer size",
-             indexname);
-    return -1;
+    return vsa_fail(-1, "%s.prj contains illegal line defining the integer "
+                    "size", indexname);
   }
   if (!prj->have_littleendian)
   {
-    snprintf(vsa_errbuf(), ERRSIZE,
-             "%s.prj contains illegal line defining the endianness",
-             indexname);
-    return -1;
+    return vsa_fail(-1, "%s.prj contains illegal line defining the endianness",
+                        indexname);
   }
   {
     const uint16_t probe = 1;
@@ -201,12 +193,10 @@ static int readprj(const char *indexname, Prj *prj)
     if ((prj->littleendian != 0) != hostlittle)
     {
       /* kurtz-basic/multiseq-adv.c:1880-1898 */
-      snprintf(vsa_errbuf(), ERRSIZE,
-               "index was built on a computer with %s endian byte order, "
-               "this computer has %s endian byte order",
-               prj->littleendian ? "little" : "big",
-               hostlittle ? "little" : "big");
-      return -1;
+      return vsa_fail(-1, "index was built on a computer with %s endian "
+                      "byte order, this computer has %s endian byte order",
+                      prj->littleendian ? "little" : "big",
+                      hostlittle ? "little" : "big");
     }
   }
   return 0;
@@ -224,9 +214,8 @@ static int readnumofchars(const char *indexname, uint32_t *numofchars)
   fp = fopen(path, "r");
   if (fp == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open \"%s\": %s", path,
-             strerror(errno));
-    return -1;
+    return vsa_fail(-1, "cannot open \"%s\": %s", path,
+                        strerror(errno));
   }
   while (fgets(line, sizeof line, fp) != NULL)
   {
@@ -238,8 +227,7 @@ static int readnumofchars(const char *indexname, uint32_t *numofchars)
   fclose(fp);
   if (lines < 2)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "\"%s\": not a symbol map", path);
-    return -1;
+    return vsa_fail(-1, "\"%s\": not a symbol map", path);
   }
   *numofchars = lines - 1;
   return 0;
@@ -256,8 +244,7 @@ int vsa_index_open(const char *indexname, int device, vsa_index **index)
 
   if (indexname == NULL || index == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_index_open: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_index_open: NULL argument");
   }
   *index = NULL;
   if (readprj(indexname, &prj) != 0 ||
@@ -267,34 +254,30 @@ int vsa_index_open(const char *indexname, int device, vsa_index **index)
   }
   if (prj.prefixlength == 0 || prj.prefixlength > 32)
   {
-    snprintf(vsa_errbuf(), ERRSIZE,
-             "%s.prj: prefixlength=%lu: index has no usable bucket table",
-             indexname, (unsigned long) prj.prefixlength);
-    return -1;
+    return vsa_fail(-1, "%s.prj: prefixlength=%lu: index has no usable "
+                        "bucket table",
+                        indexname, (unsigned long) prj.prefixlength);
   }
   /* sizes that cannot be an index (and whose products below would wrap) */
   if (prj.totallength >= (1ull << 40) ||
       prj.largelcpvalues > prj.totallength + 1 ||
       (prj.integersize != 32 && prj.integersize != 64))
   {
-    snprintf(vsa_errbuf(), ERRSIZE,
-             "%s.prj: totallength=%lu largelcpvalues=%lu integersize=%lu: "
-             "not the sizes of an index", indexname,
-             (unsigned long) prj.totallength,
-             (unsigned long) prj.largelcpvalues,
-             (unsigned long) prj.integersize);
-    return -1;
+    return vsa_fail(-1, "%s.prj: totallength=%lu largelcpvalues=%lu "
+                        "integersize=%lu: not the sizes of an index", indexname,
+                        (unsigned long) prj.totallength,
+                        (unsigned long) prj.largelcpvalues,
+                        (unsigned long) prj.integersize);
   }
   for (k = 0; k < prj.prefixlength; k++)
   {
     numofcodes *= numofchars;
     if (numofcodes > (1ull << 36))
     {
-      snprintf(vsa_errbuf(), ERRSIZE,
-               "%s.prj: prefixlength=%lu is too large for %lu characters",
-               indexname, (unsigned long) prj.prefixlength,
-               (unsigned long) numofchars);
-      return -1;
+      return vsa_fail(-1, "%s.prj: prefixlength=%lu is too large for %lu "
+                          "characters",
+                          indexname, (unsigned long) prj.prefixlength,
+                          (unsigned long) numofchars);
     }
   }
   w = prj.integersize / 8;
@@ -336,7 +319,7 @@ int vsa_index_open(const char *indexname, int device, vsa_index **index)
     if (prj.numofdbsequences == 0 ||
         prj.numofdbsequences > prj.numofsequences - 1)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "%s.prj: inconsistent number of "
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "%s.prj: inconsistent number of "
                "sequences", indexname);
       goto done;
     }

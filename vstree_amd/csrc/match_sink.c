@@ -33,8 +33,7 @@
 #include "evalues.h"
 #include "sixframe_rules.h"
 
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 #define SMALLESTEVALUE 1.0e-300 /* include/evaluedef.h:26 */
 #define MAXEXPONENTOF2 100      /* kurtz/evalues.c:51 */
@@ -198,8 +197,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
 
   if (params == NULL || sink == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_open: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_sink_open: NULL argument");
   }
   *sink = NULL;
   if (params->numofsequences == 0 || params->totallength == 0 ||
@@ -208,14 +206,12 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
       (params->kind != VSA_SINK_SELF && params->numofqueries > 0 &&
        (params->querystart == NULL || params->querylength == NULL)))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_open: incomplete parameters");
-    return -1;
+    return vsa_fail(-1, "vsa_sink_open: incomplete parameters");
   }
   s = (vsa_sink *) calloc(1, sizeof *s);
   if (s == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   s->p = *params;
   nsep = params->numofsequences - 1;
@@ -227,8 +223,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
       s->line == NULL)
   {
     vsa_sink_close(s);
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   if (nsep > 0)
   {
@@ -284,9 +279,8 @@ int vsa_sink_setdigits(vsa_sink *s, int length, int position1, int position2,
       seqnum1 < 1 || seqnum2 < 1 || length > 12 || position1 > 12 ||
       position2 > 12 || seqnum1 > 12 || seqnum2 > 12)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_setdigits: a sink and five "
-             "widths between 1 and 12");
-    return -1;
+    return vsa_fail(-1, "vsa_sink_setdigits: a sink and five "
+                        "widths between 1 and 12");
   }
   s->wlength = length;
   s->wpos1 = position1;
@@ -634,8 +628,7 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
 
   if (s->cache.evalue == NULL && cache_init(&s->cache) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   if (s->p.kind == VSA_SINK_APPROX_EDIST ||
       s->p.kind == VSA_SINK_APPROX_HAMMING)
@@ -651,8 +644,7 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
   if (maxd + 1 > s->ev.nextline &&
       vsa_evalues_extend(&s->ev, (int64_t) maxd) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   return 0;
 }
@@ -726,8 +718,7 @@ static int formatall(vsa_sink *s, const vsa_match *matches, uint64_t n,
     free(chunks);
     free(tid);
     free(arena);
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   while (done < n)
   {
@@ -774,8 +765,8 @@ static int formatall(vsa_sink *s, const vsa_match *matches, uint64_t n,
     {
       if (chunks[t].failed)
       {
-        snprintf(vsa_errbuf(), ERRSIZE, "match refers to a query outside "
-                 "the %lu of the sink, or out of memory",
+        snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "match refers to a query "
+                 "outside the %lu of the sink, or out of memory",
                  (unsigned long) s->p.numofqueries);
         rc = -2;
       } else
@@ -810,9 +801,8 @@ static int emitmemory(void *info, const char *text, uint64_t len)
 
   if (mb->used + len > mb->capacity)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_format: buffer of %lu bytes "
-             "is too small", (unsigned long) mb->capacity);
-    return -3;
+    return vsa_fail(-3, "vsa_sink_format: buffer of %lu bytes "
+                        "is too small", (unsigned long) mb->capacity);
   }
   memcpy(mb->buffer + mb->used, text, (size_t) len);
   mb->used += len;
@@ -823,8 +813,7 @@ static int emitfile(void *info, const char *text, uint64_t len)
 {
   if (len > 0 && fwrite(text, 1, (size_t) len, (FILE *) info) != (size_t) len)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_write: write failed");
-    return -4;
+    return vsa_fail(-4, "vsa_sink_write: write failed");
   }
   return 0;
 }
@@ -838,8 +827,7 @@ int64_t vsa_sink_format(vsa_sink *s, const vsa_match *matches, uint64_t n,
   if (s == NULL || (n > 0 && matches == NULL) ||
       (capacity > 0 && buffer == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_format: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_sink_format: NULL argument");
   }
   mb.buffer = buffer;
   mb.used = 0;
@@ -853,8 +841,7 @@ int vsa_sink_write(vsa_sink *s, const vsa_match *matches, uint64_t n,
 {
   if (s == NULL || file == NULL || (n > 0 && matches == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_sink_write: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_sink_write: NULL argument");
   }
   return formatall(s, matches, n, s->p.threads, emitfile, file);
 }

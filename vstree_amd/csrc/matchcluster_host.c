@@ -17,75 +17,40 @@
 #include "vstree_amd.h"
 #include "matchcluster_rules.h"
 #include "erate_rules.h"
-
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 int vsa_mc_checklayout(const vsa_sinkparams *layout,
                        const vsa_matchclusterparams *params, const char *who,
                        vsa_selrules *rules, vsa_mcrules *mcrules)
 {
+  int rc;
+
   if (layout == NULL || params == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
-    return -1;
+    return vsa_fail(-1, "%s: NULL argument", who);
   }
   if (params->mode == VSA_MATCHCLUSTER_ERATE)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: matchcluster erate (the edit distance "
-             "between the match substrings) is not covered here: it needs the "
-             "text (vsa_eratecluster_open, vsa_eratecluster_host)", who);
-    return VSA_NOT_COVERED;
+    return vsa_fail(VSA_NOT_COVERED, "%s: matchcluster erate (the edit "
+                    "distance between the match substrings) is not covered "
+                    "here: it needs the text (vsa_eratecluster_open, "
+                    "vsa_eratecluster_host)", who);
   }
   if (params->mode != VSA_MATCHCLUSTER_GAP &&
       params->mode != VSA_MATCHCLUSTER_OVERLAP)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: illegal mode %d", who, params->mode);
-    return -2;
+    return vsa_fail(-2, "%s: illegal mode %d", who, params->mode);
   }
   if (params->mode == VSA_MATCHCLUSTER_GAP &&
       params->maxgapsize >= VSA_MC_MAXGAP)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: a gap size of %lu is beyond 2^62", who,
-             (unsigned long) params->maxgapsize);
-    return -2;
+    return vsa_fail(-2, "%s: a gap size of %lu is beyond 2^62", who,
+                    (unsigned long) params->maxgapsize);
   }
-  if (layout->selfpalindromic)
+  if ((rc = vsa_layout_view(layout, who, VSA_NEEDS_NOSELFPAL |
+                            VSA_NEEDS_QUERIES, rules)) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of vmatch -p IDX "
-             "(selfpalindromic) are not covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (layout->kind == VSA_SINK_TRANSLATED ||
-      layout->kind == VSA_SINK_TRANSLATED_COMPLETE)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of a six-frame translated "
-             "batch (VSA_SINK_TRANSLATED) are not covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (layout->kind < VSA_SINK_COMPLETE ||
-      layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
-      layout->totalquerylength + 1 > layout->totallength ||
-      (layout->kind != VSA_SINK_SELF && layout->numofqueries > 0 &&
-       (layout->querystart == NULL || layout->querylength == NULL)))
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: incomplete layout", who);
-    return -2;
-  }
-  /* the view of a match (select_rules.h); no E-value is looked at */
-  memset(rules, 0, sizeof *rules);
-  rules->kind = layout->kind;
-  rules->noevalue = 1;
-  rules->totallength = (double) layout->totallength;
-  if (layout->kind == VSA_SINK_SELF)
-  {
-    rules->hasindexedqueries = layout->totalquerylength > 0;
-    rules->dblenplus1 = layout->totallength - layout->totalquerylength;
-  } else
-  {
-    rules->nq = layout->numofqueries;
-    rules->qstart = layout->querystart;
-    rules->qlen = layout->querylength;
+    return rc;
   }
   mcrules->mode = params->mode;
   mcrules->maxgapsize = params->maxgapsize;
@@ -93,54 +58,20 @@ int vsa_mc_checklayout(const vsa_sinkparams *layout,
   return 0;
 }
 
-/* bounded text: the bytes that did not fit are counted, not written */
-typedef struct
-{
-  char *p;
-  uint64_t cap, len;
-} textbuf;
-
-static void put(textbuf *t, const char *s, size_t n)
-{
-  if (t->len + n < t->cap)
-  {
-    memcpy(t->p + t->len, s, n);
-  }
-  t->len += n;
-}
-
-static int64_t endtext(textbuf *t, const char *who)
-{
-  if (t->len >= t->cap)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu bytes do not fit a buffer of %lu",
-             who, (unsigned long) t->len + 1, (unsigned long) t->cap);
-    return -3;
-  }
-  t->p[t->len] = '\0';
-  return (int64_t) t->len;
-}
-
 /* domatchclustering and showclnum, matchclust.c:10-16,94 */
 int64_t vsa_mc_format(uint64_t matches, const vsa_clresult *r, char *buffer,
                       uint64_t capacity)
 {
-  textbuf t = {buffer, capacity, 0};
-  char line[128];
+  vsa_textbuf t = {buffer, capacity, 0};
   uint64_t c;
-  int n;
 
-  n = snprintf(line, sizeof line, "# cluster %lu matches\n",
-               (unsigned long) matches);
-  put(&t, line, (size_t) n);
+  vsa_putf(&t, "# cluster %lu matches\n", (unsigned long) matches);
   for (c = 0; c < r->clusters; c++)
   {
-    n = snprintf(line, sizeof line, "# create cluster %lu of size %lu\n",
-                 (unsigned long) c,
-                 (unsigned long) (r->clusterstart[c + 1] - r->clusterstart[c]));
-    put(&t, line, (size_t) n);
+    vsa_putf(&t, "# create cluster %lu of size %lu\n", (unsigned long) c,
+             (unsigned long) (r->clusterstart[c + 1] - r->clusterstart[c]));
   }
-  return endtext(&t, "vsa_matchcluster_format");
+  return vsa_endtext(&t, "vsa_matchcluster_format");
 }
 
 /* showclelem and showedge with the two mcllinkinfo functions,
@@ -152,60 +83,52 @@ int64_t vsa_matchcluster_format_host(vsa_sink *sink, int mode,
                                      const uint64_t *value, uint64_t nedges,
                                      char *buffer, uint64_t capacity)
 {
-  textbuf t = {buffer, capacity, 0};
+  vsa_textbuf t = {buffer, capacity, 0};
   char line[512];
   uint64_t i;
-  int n;
 
   if (sink == NULL || buffer == NULL || (size > 0 && (member == NULL ||
       records == NULL)) || (nedges > 0 && (m0 == NULL || m1 == NULL ||
       value == NULL)))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_format_host: NULL "
-             "argument");
-    return -1;
+    return vsa_fail(-1, "vsa_matchcluster_format_host: NULL argument");
   }
   for (i = 0; i < size; i++)
   {
     int64_t w;
-    n = snprintf(line, sizeof line, "# id %lu\n", (unsigned long) member[i]);
-    put(&t, line, (size_t) n);
+    vsa_putf(&t, "# id %lu\n", (unsigned long) member[i]);
     w = vsa_sink_format(sink, records + i, 1, line, sizeof line);
     if (w < 0)
     {
       return w;
     }
-    put(&t, line, (size_t) w);
+    vsa_put(&t, line, (size_t) w);
   }
   for (i = 0; i < nedges; i++)
   {
     if (mode == VSA_MATCHCLUSTER_GAP)
     {
-      n = snprintf(line, sizeof line,
-                   "# linked %lu and %lu with gapsize %lu\n",
-                   (unsigned long) m0[i], (unsigned long) m1[i],
-                   (unsigned long) value[i]);
+      vsa_putf(&t, "# linked %lu and %lu with gapsize %lu\n",
+               (unsigned long) m0[i], (unsigned long) m1[i],
+               (unsigned long) value[i]);
     } else if (mode == VSA_MATCHCLUSTER_ERATE)
     {
       /* cluedistmlclinkinfo, cluedist.c:108-118 */
       const uint64_t edist = value[i] & 0xFFFFFFFFull,
                      minlen = value[i] >> 32;
-      n = snprintf(line, sizeof line,
-                   "# linked %lu and %lu with edit distance %lu (error rate "
-                   "%.2f%%)\n", (unsigned long) m0[i], (unsigned long) m1[i],
-                   (unsigned long) edist,
-                   100.00 * (double) edist / (double) minlen);
+      vsa_putf(&t, "# linked %lu and %lu with edit distance %lu (error rate "
+               "%.2f%%)\n", (unsigned long) m0[i], (unsigned long) m1[i],
+               (unsigned long) edist,
+               100.00 * (double) edist / (double) minlen);
     } else
     {
       double overlap;
       memcpy(&overlap, value + i, 8);
-      n = snprintf(line, sizeof line,
-                   "# linked %lu and %lu with overlap percentage %.2f\n",
-                   (unsigned long) m0[i], (unsigned long) m1[i], overlap);
+      vsa_putf(&t, "# linked %lu and %lu with overlap percentage %.2f\n",
+               (unsigned long) m0[i], (unsigned long) m1[i], overlap);
     }
-    put(&t, line, (size_t) n);
   }
-  return endtext(&t, "vsa_matchcluster_format_cluster");
+  return vsa_endtext(&t, "vsa_matchcluster_format_cluster");
 }
 
 /* ---- the references, sorted like glibc's qsort sorts them ---------------- */
@@ -271,8 +194,7 @@ static int addedge(Edges *e, uint32_t a, uint32_t b, uint64_t value)
     }
     if (v == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-      return -1;
+      return vsa_fail(-1, "out of memory");
     }
     e->value = v;
     e->cap = cap;
@@ -313,9 +235,8 @@ static int deliver(const char *who, uint64_t n, const Edges *edges,
   }
   if ((m0 != NULL || m1 != NULL || value != NULL) && e.n > edgecapacity)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu edges, room for %lu", who,
-             (unsigned long) e.n, (unsigned long) edgecapacity);
-    rc = -3;
+    rc = vsa_fail(-3, "%s: %lu edges, room for %lu", who,
+                  (unsigned long) e.n, (unsigned long) edgecapacity);
     goto done;
   }
   if (buffer != NULL &&
@@ -331,8 +252,7 @@ static int deliver(const char *who, uint64_t n, const Edges *edges,
     fill = calloc((size_t) res.clusters + 2, sizeof *fill);
     if (fill == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-      rc = -1;
+      rc = vsa_fail(-1, "out of memory");
       goto done;
     }
     for (i = 0; i < e.n; i++)
@@ -397,6 +317,7 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
                           uint64_t edgecapacity, char *buffer,
                           uint64_t capacity, int64_t *written)
 {
+  static const char who[] = "vsa_matchcluster_host";
   vsa_selrules rules;
   vsa_mcrules mc;
   vsa_matchclusterstats st;
@@ -404,23 +325,11 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
   Mref *ref = NULL, *tmp = NULL;
   uint64_t *length = NULL;
   uint64_t i, j;
-  int rc = vsa_mc_checklayout(layout, params, "vsa_matchcluster_host", &rules,
-                              &mc);
+  int rc = vsa_mc_checklayout(layout, params, who, &rules, &mc);
 
-  if (rc != 0)
+  if (rc != 0 || (rc = vsa_list_check(who, "matches", matches, n)) != 0)
   {
     return rc;
-  }
-  if (matches == NULL && n > 0)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: NULL argument");
-    return -1;
-  }
-  if (n >= 0xFFFFFFFFull)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: %lu matches: only "
-             "fewer than 2^32 - 1 are covered", (unsigned long) n);
-    return VSA_NOT_COVERED;
   }
   memset(&st, 0, sizeof st);
   st.matches = n;
@@ -429,26 +338,20 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
   length = malloc((size_t) (n + 1) * sizeof *length);
   if (ref == NULL || tmp == NULL || length == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   for (i = 0; i < n; i++)
   {
-    const int pal = palindromic != NULL && palindromic[i] != 0;
     vsa_selvalues v;
-    if (pal && layout->kind == VSA_SINK_SELF)
+    int pal;
+    if ((rc = vsa_list_flag(who, layout->kind, palindromic, i, &pal)) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: palindromic "
-               "self matches are the selfpalindromic form");
-      rc = VSA_NOT_COVERED;
       goto done;
     }
     if (vsa_sel_values(&rules, matches + i, pal, &v) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: record %lu does "
-               "not fit the layout", (unsigned long) i);
-      rc = -2;
+      rc = vsa_list_misfit(who, i);
       goto done;
     }
     length[i] = v.length1;
@@ -483,9 +386,8 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
       {
         if (e.n + 1 >= 0xFFFFFFFFull)
         {
-          snprintf(vsa_errbuf(), ERRSIZE, "vsa_matchcluster_host: only fewer "
-                   "than 2^32 - 1 edges are covered");
-          rc = VSA_NOT_COVERED;
+          rc = vsa_fail(VSA_NOT_COVERED, "%s: only fewer than 2^32 - 1 edges "
+                        "are covered", who);
           goto done;
         }
         if (addedge(&e, ref[i].matchnum, ref[j].matchnum, val) != 0)
@@ -496,7 +398,7 @@ int vsa_matchcluster_host(const vsa_sinkparams *layout,
       }
     }
   }
-  rc = deliver("vsa_matchcluster_host", n, &e, &st, stats, clusterstart,
+  rc = deliver(who, n, &e, &st, stats, clusterstart,
                members, label, edgestart, m0, m1, value, edgecapacity, buffer,
                capacity, written);
 done:
@@ -517,42 +419,33 @@ int vsa_er_checklayout(const vsa_sinkparams *layout, uint32_t errorrate,
 {
   if (layout == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
-    return -1;
+    return vsa_fail(-1, "%s: NULL argument", who);
   }
   if (errorrate > 100)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: an error rate of %lu is beyond 100",
-             who, (unsigned long) errorrate);
-    return -2;
+    return vsa_fail(-2, "%s: an error rate of %lu is beyond 100", who,
+                    (unsigned long) errorrate);
   }
-  if (layout->selfpalindromic)
+  if (vsa_layout_selfpalindromic(layout, who) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: lists of vmatch -p IDX "
-             "(selfpalindromic) are not covered", who);
     return VSA_NOT_COVERED;
   }
   if (layout->kind != VSA_SINK_SELF || layout->totalquerylength > 0)
   {
     /* (the reference takes them and reads position2 off the index text) */
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: matchcluster erate covers lists of "
-             "an index against itself only: the second instance of a match "
-             "against queries is no stretch of the index text", who);
-    return VSA_NOT_COVERED;
+    return vsa_fail(VSA_NOT_COVERED, "%s: matchcluster erate covers lists of "
+                    "an index against itself only: the second instance of a "
+                    "match against queries is no stretch of the index text",
+                    who);
   }
   if (layout->totallength == 0 || layout->totallength != textlength)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: a layout of %lu symbols, a text of "
-             "%lu", who, (unsigned long) layout->totallength,
-             (unsigned long) textlength);
-    return -2;
+    return vsa_fail(-2, "%s: a layout of %lu symbols, a text of %lu", who,
+                    (unsigned long) layout->totallength,
+                    (unsigned long) textlength);
   }
-  memset(rules, 0, sizeof *rules);
-  rules->kind = VSA_SINK_SELF;
-  rules->noevalue = 1;
-  rules->totallength = (double) layout->totallength;
-  rules->dblenplus1 = layout->totallength;
-  return 0;
+  /* a self layout without indexed queries: none of the shared refusals */
+  return vsa_layout_view(layout, who, 0, rules);
 }
 
 /* verifysmalldistance and unitedistfrontSEPgeneric with a bound
@@ -626,16 +519,13 @@ int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
   {
     return rc;
   }
-  if ((matches == NULL && n > 0) || text == NULL)
+  if (text == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: NULL argument", who);
-    return -1;
+    return vsa_fail(-1, "%s: NULL argument", who);
   }
-  if (n >= 0xFFFFFFFFull)
+  if ((rc = vsa_list_check(who, "matches", matches, n)) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "%s: %lu matches: only fewer than 2^32 - 1 "
-             "are covered", who, (unsigned long) n);
-    return VSA_NOT_COVERED;
+    return rc;
   }
   memset(&st, 0, sizeof st);
   st.matches = n;
@@ -643,8 +533,7 @@ int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
   pos = malloc((size_t) (2 * n + 1) * sizeof *pos);
   if (length == NULL || pos == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   for (i = 0; i < n; i++)
@@ -660,7 +549,7 @@ int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
     }
     if (rc != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, rc == -2
+      vsa_fail(rc, rc == -2
                ? "%s: record %lu does not fit the layout (it leaves the text "
                  "or holds a separator)"
                : "%s: record %lu: only lengths below 2^32 are covered", who,
@@ -679,8 +568,7 @@ int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
                  sizeof *front);
   if (front == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -1;
+    rc = vsa_fail(-1, "out of memory");
     goto done;
   }
   for (i = 0; i + 1 < n; i++)
@@ -705,9 +593,8 @@ int vsa_eratecluster_host(const vsa_sinkparams *layout, uint32_t errorrate,
       }
       if (e.n + 1 >= 0xFFFFFFFFull)
       {
-        snprintf(vsa_errbuf(), ERRSIZE, "%s: only fewer than 2^32 - 1 edges "
-                 "are covered", who);
-        rc = VSA_NOT_COVERED;
+        rc = vsa_fail(VSA_NOT_COVERED, "%s: only fewer than 2^32 - 1 edges "
+                      "are covered", who);
         goto done;
       }
       if (addedge(&e, (uint32_t) i, (uint32_t) j,

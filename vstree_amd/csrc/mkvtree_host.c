@@ -25,8 +25,7 @@
 #include <errno.h>
 #include "vstree_amd.h"
 
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 typedef struct
 {
@@ -52,8 +51,7 @@ static int grow(void **p, uint64_t *cap, uint64_t need, size_t elem)
     q = realloc(*p, (size_t) nc * elem);
     if (q == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-      return -1;
+      return vsa_fail(-1, "out of memory");
     }
     *p = q;
     *cap = nc;
@@ -108,9 +106,8 @@ static int readfasta(Text *t, const char *path, const uint8_t map[256],
 
   if (fp == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open file \"%s\": %s", path,
-             strerror(errno));
-    return -1;
+    return vsa_fail(-1, "cannot open file \"%s\": %s", path,
+                        strerror(errno));
   }
   *filelength = 0;
   while ((ch = getc(fp)) != EOF)
@@ -133,7 +130,7 @@ static int readfasta(Text *t, const char *path, const uint8_t map[256],
     {
       if (prev != '\n')
       {
-        snprintf(vsa_errbuf(), ERRSIZE,
+        snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
                  "Illegal character '%c' in file \"%s\" line %lu", ch, path,
                  (unsigned long) linenum);
         fclose(fp);
@@ -169,7 +166,7 @@ static int readfasta(Text *t, const char *path, const uint8_t map[256],
       const uint8_t code = map[(uint8_t) ch];
       if (code == VSA_UNDEFBWT || !seenseq)
       {
-        snprintf(vsa_errbuf(), ERRSIZE,
+        snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
                  "Illegal character '%c' in file \"%s\" line %lu", ch, path,
                  (unsigned long) linenum);
         fclose(fp);
@@ -197,21 +194,19 @@ static int writefile(const char *indexname, const char *suffix,
   fp = fopen(path, "wb");
   if (fp == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open file \"%s\": %s", path,
-             strerror(errno));
-    return -1;
+    return vsa_fail(-1, "cannot open file \"%s\": %s", path,
+                        strerror(errno));
   }
   if (bytes > 0 && fwrite(data, 1, bytes, fp) != bytes)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot write %lu bytes to \"%s\"",
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "cannot write %lu bytes to \"%s\"",
              (unsigned long) bytes, path);
     fclose(fp);
     return -1;
   }
   if (fclose(fp) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot close \"%s\"", path);
-    return -1;
+    return vsa_fail(-1, "cannot close \"%s\"", path);
   }
   return 0;
 }
@@ -251,15 +246,14 @@ static int writeintegers(const char *indexname, const char *suffix,
   out = malloc((size_t) (count ? count : 1) * (bits / 8));
   if (out == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -1;
+    return vsa_fail(-1, "out of memory");
   }
   for (i = 0; i < count; i++)
   {
     const uint64_t x = geti(v, w, i);
     if (bits == 32 && (x >> 32) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE,
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
                "integersize 32 cannot hold the entries of %s.%s", indexname,
                suffix);
       free(out);
@@ -285,8 +279,7 @@ static int makeskiptable(void *skp, const uint8_t *lcp, const void *llv,
   {
     free(depth);
     free(step);
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -1;
+    return vsa_fail(-1, "out of memory");
   }
   depth[0] = 0;
   step[0] = 0;
@@ -310,8 +303,7 @@ static int makeskiptable(void *skp, const uint8_t *lcp, const void *llv,
       step = (uint64_t *) realloc(step, cap * 8);
       if (depth == NULL || step == NULL)
       {
-        snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-        return -1;
+        return vsa_fail(-1, "out of memory");
       }
     }
     depth[top] = cur;
@@ -349,13 +341,11 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   if (dbfiles == NULL || numofdbfiles == 0 || indexname == NULL ||
       (numofqueryfiles > 0 && queryfiles == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_mkvtree: missing argument");
-    return -1;
+    return vsa_fail(-1, "vsa_mkvtree: missing argument");
   }
   if (integersize != 32 && integersize != 64)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "integersize must be 32 or 64");
-    return -1;
+    return vsa_fail(-1, "integersize must be 32 or 64");
   }
   memset(&t, 0, sizeof t);
   dnasymbolmap(map);
@@ -363,7 +353,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   fileend = (uint64_t *) calloc(nfiles, 8);
   if (filelen == NULL || fileend == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "out of memory");
     goto done;
   }
   for (f = 0; f < nfiles; f++)
@@ -382,7 +372,8 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   }
   if (t.numseq == 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "no sequences in multiple fasta file");
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
+             "no sequences in multiple fasta file");
     goto done;
   }
   if (grow((void **) &t.sds, &t.sdscap, t.numseq + 2, 8) != 0)
@@ -417,7 +408,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   if (suf == NULL || lcp == NULL || bwt == NULL || sti1 == NULL ||
       llv == NULL || bck == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "out of memory");
     goto done;
   }
   if (vsa_index_download(ix, NULL, suf, lcp, llv, bck, bwt) != 0 ||
@@ -430,7 +421,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   prj = fopen(path, "w");
   if (prj == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot open file \"%s\": %s", path,
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "cannot open file \"%s\": %s", path,
              strerror(errno));
     goto done;
   }
@@ -502,7 +493,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
   }
   if (fclose(prj) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "cannot close \"%s\"", path);
+    snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "cannot close \"%s\"", path);
     goto done;
   }
   if (writefile(indexname, "al1", dna_al1, strlen(dna_al1)) != 0 ||
@@ -525,7 +516,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
     uint64_t *tmp = (uint64_t *) malloc((size_t) (t.numseq + 2) * 8);
     if (tmp == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "out of memory");
       goto done;
     }
     for (i = 0; i <= t.numseq; i++)
@@ -554,7 +545,7 @@ int vsa_mkvtree(const char *const *dbfiles, uint32_t numofdbfiles,
     skp = malloc((size_t) (t.n + 1) * w);
     if (skp == NULL)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "out of memory");
       goto done;
     }
     if (makeskiptable(skp, lcp, llv, w, t.n) != 0 ||

@@ -17,8 +17,7 @@
 #endif
 #include "vstree_amd.h"
 
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 typedef struct
 {
@@ -154,8 +153,7 @@ int vsa_pack_reads_mt(const uint8_t *symbols, uint64_t numofqueries,
       numofspecial == NULL || querylength == 0 ||
       (specialcapacity > 0 && special == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_pack_reads: bad argument");
-    return -1;
+    return vsa_fail(-1, "vsa_pack_reads: bad argument");
   }
   if (threads == 0)
   {
@@ -179,8 +177,7 @@ int vsa_pack_reads_mt(const uint8_t *symbols, uint64_t numofqueries,
   {
     free(pieces);
     free(tids);
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_pack_reads: out of memory");
-    return -100;
+    return vsa_fail(-100, "vsa_pack_reads: out of memory");
   }
   for (t = 0; t < threads; t++)
   {
@@ -220,7 +217,7 @@ int vsa_pack_reads_mt(const uint8_t *symbols, uint64_t numofqueries,
     uint64_t k;
     if (pieces[t].failed)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_pack_reads: out of memory");
+      snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE, "vsa_pack_reads: out of memory");
       rc = -100;
     }
     for (k = 0; k < pieces[t].nflagged && rc == 0; k++)
@@ -232,7 +229,7 @@ int vsa_pack_reads_mt(const uint8_t *symbols, uint64_t numofqueries,
       {
         /* a symbol that is no base (a wildcard; in a Multiseq also a
            separator would be): the read travels as bytes */
-        snprintf(vsa_errbuf(), ERRSIZE,
+        snprintf(vsa_errbuf(), VSA_ERRBUF_SIZE,
                  "vsa_pack_reads: more than %lu reads with a special symbol",
                  (unsigned long) specialcapacity);
         rc = -2;

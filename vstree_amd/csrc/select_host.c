@@ -24,9 +24,7 @@
 #include <stdint.h>
 #include "vstree_amd.h"
 #include "select_internal.h"
-
-char *vsa_errbuf(void);
-#define ERRSIZE 1024
+#include "host_common.h"
 
 /* ---- the description of a selection ----------------------------------- */
 
@@ -44,8 +42,7 @@ static int settables(vsa_selctx *ctx, int64_t nlines)
       (h = (double *) realloc(ctx->hequot,
                               (size_t) nlines * sizeof(double))) == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   for (d = 0; d < nlines; d++)
   {
@@ -64,80 +61,58 @@ int vsa_selctx_init(vsa_selctx *ctx, const vsa_sinkparams *layout,
                     const uint64_t *qstart, const uint64_t *qlen,
                     uint32_t uniformlen, uint64_t seqoffset)
 {
+  static const char who[] = "vsa_select";
   vsa_selrules *r = &ctx->rules;
   const uint64_t dblen = layout->totallength - layout->totalquerylength - 1;
+  int rc;
 
   memset(ctx, 0, sizeof *ctx);
-  if (layout->kind == VSA_SINK_TRANSLATED ||
-      layout->kind == VSA_SINK_TRANSLATED_COMPLETE)
+  /* (the query arrays are the caller's: their refusal comes below) */
+  if ((rc = vsa_layout_view(layout, who, VSA_NEEDS_CHARS, r)) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: lists of a six-frame "
-             "translated batch (VSA_SINK_TRANSLATED) are not covered");
-    return VSA_NOT_COVERED;
-  }
-  if (layout->kind < VSA_SINK_COMPLETE ||
-      layout->kind > VSA_SINK_APPROX_HAMMING || layout->numofchars < 2 ||
-      layout->totallength == 0 ||
-      layout->totalquerylength + 1 > layout->totallength)
-  {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: incomplete layout");
-    return -2;
+    return rc;
   }
   if (params->sortmode < 0 || params->sortmode > VSA_SORT_NONE)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: illegal sort mode %d",
-             params->sortmode);
-    return -2;
+    return vsa_fail(-2, "%s: illegal sort mode %d", who, params->sortmode);
   }
   if (params->sortmode != VSA_SORT_NONE && params->bestnumber == 0)
   {
     /* Vmatch/parsevm.c: -sort goes with -best */
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: a sort mode needs "
-             "bestnumber > 0");
-    return -2;
+    return vsa_fail(-2, "%s: a sort mode needs bestnumber > 0", who);
   }
   if (params->bestnumber > 0xFFFFFFF0ull)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: bestnumber %lu is beyond "
-             "2^32 - 16", (unsigned long) params->bestnumber);
-    return -2;
+    return vsa_fail(-2, "%s: bestnumber %lu is beyond 2^32 - 16", who,
+                    (unsigned long) params->bestnumber);
   }
   if (params->identity > 100 ||
       (params->hasleastscore && params->leastscore < 0))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: identity must be 0..100, "
-             "leastscore >= 0");
-    return -2;
+    return vsa_fail(-2, "%s: identity must be 0..100, leastscore >= 0", who);
   }
   if ((params->haslowergap || params->hasuppergap) &&
       layout->kind != VSA_SINK_SELF)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: gap bounds go with matches "
-             "of the index against itself (VSA_SINK_SELF)");
-    return -2;
+    return vsa_fail(-2, "%s: gap bounds go with matches of the index against "
+                    "itself (VSA_SINK_SELF)", who);
   }
   if (params->hasuppergap && !params->haslowergap)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: the upper gap bound needs "
-             "the lower one");
-    return -2;
+    return vsa_fail(-2, "%s: the upper gap bound needs the lower one", who);
   }
   if (layout->kind != VSA_SINK_SELF && nq > 0 && uniformlen == 0 &&
       (qstart == NULL || qlen == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: the layout has no query "
-             "Multiseq");
-    return -2;
+    return vsa_fail(-2, "%s: the layout has no query Multiseq", who);
   }
+  /* what the view leaves to a selection: E-values, and the query Multiseq
+     of the batch in copies of its own */
   ctx->params = *params;
-  r->kind = layout->kind;
   r->noevalue = (layout->showmode & VSA_SHOW_NOEVALUE) != 0;
   r->leastlength = layout->leastlength;
-  r->totallength = (double) layout->totallength;
   if (layout->kind == VSA_SINK_SELF)
   {
-    r->hasindexedqueries = layout->totalquerylength > 0;
-    r->dblenplus1 = dblen + 1;
     r->multiplier = r->hasindexedqueries
                         ? (double) dblen * (double) layout->totalquerylength
                         : 0.5 * (double) layout->totallength *
@@ -148,6 +123,7 @@ int vsa_selctx_init(vsa_selctx *ctx, const vsa_sinkparams *layout,
     r->nq = nq;
     r->seqoffset = seqoffset;
     r->uniformlen = uniformlen;
+    r->qstart = r->qlen = NULL;
     if (uniformlen == 0 && nq > 0)
     {
       ctx->qstart = (uint64_t *) malloc((size_t) nq * 8);
@@ -155,8 +131,7 @@ int vsa_selctx_init(vsa_selctx *ctx, const vsa_sinkparams *layout,
       if (ctx->qstart == NULL || ctx->qlen == NULL)
       {
         vsa_selctx_free(ctx);
-        snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-        return -101;
+        return vsa_fail(-101, "out of memory");
       }
       memcpy(ctx->qstart, qstart, (size_t) nq * 8);
       memcpy(ctx->qlen, qlen, (size_t) nq * 8);
@@ -207,9 +182,8 @@ int vsa_selctx_ensure(vsa_selctx *ctx, uint64_t maxdistance)
   }
   if (maxdistance > 1u << 20)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: a distance of %lu",
-             (unsigned long) maxdistance);
-    return -2;
+    return vsa_fail(-2, "vsa_select: a distance of %lu",
+                    (unsigned long) maxdistance);
   }
   return settables(ctx, (int64_t) maxdistance + 1) != 0 ? -101 : 1;
 }
@@ -268,8 +242,7 @@ static int stablesort(void *base, size_t n, size_t size, Cmp cmp,
   tmp = (char *) malloc(n * size);
   if (tmp == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   msort((char *) base, n, size, cmp, info, tmp);
   free(tmp);
@@ -330,8 +303,7 @@ static int64_t removecontained(Stored *tab, uint64_t n, uint64_t *removed)
   reject = (uint8_t *) calloc((size_t) n, 1);
   if (reject == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   for (mptr1 = tab; mptr1 < tab + n; mptr1++)
   {
@@ -447,8 +419,7 @@ int64_t vsa_select_sorttail(const vsa_selctx *ctx, vsa_match *matches,
   tab = (Stored *) malloc((size_t) n * sizeof(Stored));
   if (tab == NULL)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    return -101;
+    return vsa_fail(-101, "out of memory");
   }
   for (i = 0; i < n; i++)
   {
@@ -457,9 +428,8 @@ int64_t vsa_select_sorttail(const vsa_selctx *ctx, vsa_match *matches,
     if (vsa_sel_values(&ctx->rules, matches + i, flags[i], &tab[i].v) != 0)
     {
       free(tab);
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: a selected record does "
-               "not fit the layout");
-      return -2;
+      return vsa_fail(-2, "vsa_select: a selected record does not fit the "
+                      "layout");
     }
     tab[i].v.evalue = evalues[i];
   }
@@ -501,6 +471,7 @@ int vsa_select_host(const vsa_sinkparams *layout,
                     double *evalues, uint64_t capacity, uint64_t *nselected,
                     vsa_selectstats *stats)
 {
+  static const char who[] = "vsa_select";
   vsa_selctx ctx;
   vsa_selectstats st;
   Keyed *tab = NULL;
@@ -512,15 +483,13 @@ int vsa_select_host(const vsa_sinkparams *layout,
   if (layout == NULL || params == NULL || nselected == NULL ||
       (n > 0 && matches == NULL) || (capacity > 0 && selected == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select_host: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_select_host: NULL argument");
   }
   *nselected = 0;
   memset(&st, 0, sizeof st);
-  if (layout->selfpalindromic)
+  /* (the handle takes such lists: the refusal is not vsa_selctx_init's) */
+  if (vsa_layout_selfpalindromic(layout, who) != 0)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: lists of vmatch -p IDX "
-             "(selfpalindromic) are not covered");
     return VSA_NOT_COVERED;
   }
   rc = vsa_selctx_init(&ctx, layout, params, layout->numofqueries,
@@ -531,13 +500,11 @@ int vsa_select_host(const vsa_sinkparams *layout,
   }
   for (i = 0; i < n; i++)
   {
-    if (layout->kind == VSA_SINK_SELF && palindromic != NULL &&
-        palindromic[i])
+    int pal;
+    if ((rc = vsa_list_flag(who, layout->kind, palindromic, i, &pal)) != 0)
     {
       vsa_selctx_free(&ctx);
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: palindromic self matches "
-               "are the selfpalindromic form");
-      return VSA_NOT_COVERED;
+      return rc;
     }
     if (isapprox(layout->kind) && matches[i].querystart > maxd)
     {
@@ -550,8 +517,7 @@ int vsa_select_host(const vsa_sinkparams *layout,
   oev = (double *) malloc((size_t) (n + 1) * sizeof(double));
   if (rc >= 0 && (tab == NULL || oflags == NULL || oev == NULL))
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "out of memory");
-    rc = -101;
+    rc = vsa_fail(-101, "out of memory");
   }
   for (i = 0; rc >= 0 && i < n; i++)
   {
@@ -559,9 +525,7 @@ int vsa_select_host(const vsa_sinkparams *layout,
     const int pal = palindromic != NULL && palindromic[i];
     if (vsa_sel_values(&ctx.rules, matches + i, pal, &v) != 0)
     {
-      snprintf(vsa_errbuf(), ERRSIZE, "vsa_select: record %lu does not fit "
-               "the layout", (unsigned long) i);
-      rc = -2;
+      rc = vsa_list_misfit(who, i);
       break;
     }
     st.seen++;
@@ -602,9 +566,8 @@ int vsa_select_host(const vsa_sinkparams *layout,
   }
   if (rc == 0 && m > capacity)
   {
-    snprintf(vsa_errbuf(), ERRSIZE, "vsa_select_host: %lu records for a "
-             "capacity of %lu", (unsigned long) m, (unsigned long) capacity);
-    rc = -3;
+    rc = vsa_fail(-3, "vsa_select_host: %lu records for a capacity of %lu",
+                  (unsigned long) m, (unsigned long) capacity);
   }
   if (rc == 0)
   {

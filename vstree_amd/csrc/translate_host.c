@@ -8,19 +8,17 @@
 #include "vstree_amd.h"
 #include "sixframe_rules.h"
 
-extern char *vsa_errbuf(void);
-#define ERRBUF_SIZE 1024
+#include "host_common.h"
 
 int vsa_transnum_check(uint32_t transnum)
 {
   if (!vsa_sf_transnum_ok(transnum))
   {
     /* checktransnum, kurtz/codon.c:219-229 */
-    snprintf(vsa_errbuf(), ERRBUF_SIZE,
-             "illegal translation table number %lu: must be number in the "
-             "range [1,23] except for 7, 8, 17, 18, 19 and 20",
-             (unsigned long) transnum);
-    return -2;
+    return vsa_fail(-2, "illegal translation table number %lu: must be "
+                        "number in the range [1,23] except for 7, 8, 17, 18, "
+                        "19 and 20",
+                        (unsigned long) transnum);
   }
   return 0;
 }
@@ -54,19 +52,17 @@ static int codon(const uint8_t *aminos, const uint8_t symbolmap[256],
     /* ILLEGALCHAR, kurtz/codon.c:42-44 */
     const int which = c0 == 0 ? 0 : (c1 == 0 ? 1 : 2);
     const uint8_t ch = which == 0 ? ch0 : (which == 1 ? ch1 : ch2);
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "illegal char c%d='%c'(%lu)", which,
-             ch, (unsigned long) ch);
-    return -2;
+    return vsa_fail(-2, "illegal char c%d='%c'(%lu)", which,
+                        ch, (unsigned long) ch);
   }
   aa = vsa_sf_codon(aminos, forward, c0, c1, c2);
   code = symbolmap[aa];
   if (code >= numofchars && code <= VSA_UNDEFBWT)
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "amino acid '%c' of the translation "
-             "has the code %lu, which is no symbol of the alphabet of %lu "
-             "characters", aa, (unsigned long) code,
-             (unsigned long) numofchars);
-    return -2;
+    return vsa_fail(-2, "amino acid '%c' of the translation has the code "
+                        "%lu, which is no symbol of the alphabet of %lu "
+                        "characters", aa, (unsigned long) code,
+                        (unsigned long) numofchars);
   }
   *symbol = code;
   return 0;
@@ -92,8 +88,7 @@ int vsa_translate_host(uint32_t transnum, const uint8_t *dnachars,
                   plength == NULL)) ||
       (nchars > 0 && dnachars == NULL))
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "vsa_translate_host: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_translate_host: NULL argument");
   }
   if (vsa_transnum_check(transnum) != 0)
   {
@@ -103,21 +98,19 @@ int vsa_translate_host(uint32_t transnum, const uint8_t *dnachars,
   {
     if (start[s] > nchars || length[s] > nchars - start[s])
     {
-      snprintf(vsa_errbuf(), ERRBUF_SIZE, "sequence %lu [%lu, +%lu) lies "
-               "outside the buffer of %lu characters", (unsigned long) s,
-               (unsigned long) start[s], (unsigned long) length[s],
-               (unsigned long) nchars);
-      return -2;
+      return vsa_fail(-2, "sequence %lu [%lu, +%lu) lies outside the "
+                          "buffer of %lu characters", (unsigned long) s,
+                          (unsigned long) start[s], (unsigned long) length[s],
+                          (unsigned long) nchars);
     }
     need += vsa_sf_span(length[s]);
   }
   need -= nq > 0 ? 1 : 0; /* no separator behind the last frame */
   if (need > capacity || (need > 0 && protein == NULL))
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "vsa_translate_host: %lu symbols do "
-             "not fit a buffer of %lu", (unsigned long) need,
-             (unsigned long) capacity);
-    return -3;
+    return vsa_fail(-3, "vsa_translate_host: %lu symbols do "
+                        "not fit a buffer of %lu", (unsigned long) need,
+                        (unsigned long) capacity);
   }
   vsa_sf_aminos(transnum, aminos);
   numofchars = numofcharsof(symbolmap);
@@ -177,15 +170,12 @@ int vsa_translated_convert_host(const vsa_match *matches, uint64_t n,
   if ((n > 0 && (matches == NULL || queryview == NULL)) ||
       (numofdna > 0 && dnalength == NULL))
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE,
-             "vsa_translated_convert_host: NULL argument");
-    return -1;
+    return vsa_fail(-1, "vsa_translated_convert_host: NULL argument");
   }
   if (offset % VSA_SF_FRAMES != 0)
   {
-    snprintf(vsa_errbuf(), ERRBUF_SIZE, "the offset %lu of a six-frame batch "
-             "is no multiple of 6", (unsigned long) offset);
-    return -2;
+    return vsa_fail(-2, "the offset %lu of a six-frame batch "
+                        "is no multiple of 6", (unsigned long) offset);
   }
   for (i = 0; i < n; i++)
   {
@@ -197,10 +187,9 @@ int vsa_translated_convert_host(const vsa_match *matches, uint64_t n,
         vsa_sf_convert(matches + i, q, dnalength[q / VSA_SF_FRAMES],
                        offset / VSA_SF_FRAMES, &out, &rev) != 0)
     {
-      snprintf(vsa_errbuf(), ERRBUF_SIZE, "record %lu does not lie in a "
-               "frame of the %lu DNA sequences", (unsigned long) i,
-               (unsigned long) numofdna);
-      return -2;
+      return vsa_fail(-2, "record %lu does not lie in a "
+                          "frame of the %lu DNA sequences", (unsigned long) i,
+                          (unsigned long) numofdna);
     }
     queryview[i] = out;
     if (reverse != NULL)

@@ -9,12 +9,12 @@
 #include <cstring>
 #include <vector>
 #include "vstree_amd.h"
+#include "host_common.h"
 
 // ---- error plumbing: one message buffer like the reference's messagespace()
 // (include/errordef.h:13), thread local because the library may be used from
-// one thread per GPU.
-extern "C" char *vsa_errbuf();
-#define VSA_ERRBUF_SIZE 1024
+// one thread per GPU.  vsa_errbuf() and VSA_ERRBUF_SIZE are host_common.h's,
+// the same the C files write through.
 #define VSA_ERROR(...)                                                        \
   do                                                                          \
   {                                                                           \
