@@ -1717,6 +1717,134 @@ int vsa_translated_convert_host(const vsa_match *matches, uint64_t n,
                                 uint64_t offset, vsa_match *queryview,
                                 uint8_t *reverse);
 
+/* ---- degenerate matches: vmatch -l L -h K [-seedlength S] [-q Q] IDX -------
+   Exact seeds, each extended to the left and right over at most K mismatches
+   on seed lists that stay in HBM.
+
+   What the reference does: the seed length is max(S, L / (K + 1))
+   (Vmatch/matchlenparm.c:11-22); the seeds are the MEMs of that length in the
+   order of findquerymatches (Vmengine/procexqu.c:17-95) or, without -q, the
+   maximal repeats in the order of findselfmatches (Vmengine/fself.c:95-146);
+   every seed on its own goes through hammingextend (kurtz/extendHD.c:166-374,
+   called by callgenericextend, Vmengine/extendgen.c:24-87), which keeps the
+   best extension of at least L symbols -- best by E-value, then identity,
+   then length, the later candidate on a tie (include/extcmp.c) -- or nothing.
+   Nothing is deduplicated.
+
+   A match is the 32-byte record of its seed's list moved to the left:
+   length1 = length2 in the low 48 bits of `length`, the number of mismatches
+   (the reference stores its negative in Match.distance) in the top 16 bits;
+   dbstart, and querystart or (self layout) queryseq moved left by the same
+   amount.  vsa_result_fetch, _copy_device and _from_host carry such records
+   like any others. */
+#define VSA_HAMMING_LENGTHBITS 48
+#define VSA_HAMMING_MAXDISTANCE 0xFFFFu /* what the record can carry */
+#define VSA_HAMMING_LENGTH(lengthfield) \
+  ((uint64_t) (lengthfield) & (((uint64_t) 1 << VSA_HAMMING_LENGTHBITS) - 1))
+#define VSA_HAMMING_DISTANCE(lengthfield) \
+  ((uint64_t) (lengthfield) >> VSA_HAMMING_LENGTHBITS)
+#define VSA_HAMMING_PACK(length, distance) \
+  ((uint64_t) (length) | (uint64_t) (distance) << VSA_HAMMING_LENGTHBITS)
+
+/* layouts of such lists for the sink: the lines of vmatch -l L -h K -q Q IDX
+   (with palindromic: of its -p pass) and of vmatch -l L -h K IDX, byte for
+   byte.  Everything else as for VSA_SINK_QUERY / VSA_SINK_SELF.  vsa_select_*,
+   vsa_coverage_mark, vsa_cluster_*, vsa_matchcluster_*, vsa_chain_* and
+   vsa_translated_convert answer VSA_NOT_COVERED for them, state untouched.
+   (7 stays what it was, a kind no layout has.)  A result of these entries
+   knows that it holds extended seeds; a list that went through the host and
+   vsa_result_from_host no longer does, and its caller keeps it away from
+   those handles. */
+#define VSA_SINK_QUERY_HAMMING 8
+#define VSA_SINK_SELF_HAMMING  9
+
+/* limits of the device path: distance bounds up to the cap (beyond it
+   VSA_NOT_COVERED and nothing delivered; the host path takes any bound the
+   record can carry), texts and query sequences below 2^32 - 16 symbols,
+   fewer than 2^31 seeds.  A lane of the scan stage looks at up to
+   VSA_EXTEND_LANE_BUDGET symbols of a side before it hands the side to the
+   long stage, where a wavefront covers VSA_EXTEND_LONG_STEP symbols per step.
+   The environment variable VSA_EXTEND_STAGE, read by every call, forces one
+   stage: `lane` -- no budget, no side goes to the long stage; `long` -- every
+   side that is scanned at all goes there.  The lists are the same. */
+#define VSA_EXTEND_MAXDIST 64u
+#define VSA_EXTEND_LANE_BUDGET 256u
+#define VSA_EXTEND_LONG_STEP 1024u
+uint32_t vsa_extend_maxdist(void);
+uint32_t vsa_extend_lane_budget(void);
+uint32_t vsa_extend_long_step(void);
+
+/*
+  hammingextend for every seed of a list in HBM.  seeds: records of
+  vsa_findquerymatches (MEM; layout->kind VSA_SINK_QUERY, queries = the
+  forward batch; palindromic != 0, rcmode of extendgen.c:61-67: the seeds
+  were found on its reverse complement, vsa_queries_reverse_complement, which
+  is made again here and is what the seeds are extended in) or of
+  vsa_findmaximalrepeats (layout->kind VSA_SINK_SELF, queries NULL), or a
+  list of the caller's in one of these forms; of the layout only the kind is
+  read.  leastlength L, maxdist K, seedlength S as on vmatch's command line
+  (S = 0: none given); the seed length rule is applied here.  *result: the
+  matches in the order of their seeds.  A packed 2-bit batch is expanded to
+  bytes first (once per batch, as for the MEM search).
+  Stats of the result: count = matches, sumlength = sum of their lengths,
+  candidates = seeds, searches = sides of seeds the long stage scanned,
+  search_kernel_ms = HIP-event time of the extension (scan, long and choice
+  stage; first_kernel_ms = of the scan stage, anchor_ms = of the long stage
+  alone), total_device_ms = ... of the whole call with the compaction.
+  VSA_NOT_COVERED, nothing delivered, no device memory kept: K above
+  VSA_EXTEND_MAXDIST, the size limits above, a packed-pair seed list.
+  -2: K = 0, L = 0, a layout of another kind, a seed that does not fit the
+  index or its query sequence (nothing is read through such a seed).
+*/
+int vsa_extend_hamming(const vsa_index *index, const vsa_queries *queries,
+                       const vsa_result *seeds, const vsa_sinkparams *layout,
+                       int palindromic, uint64_t leastlength,
+                       uint64_t maxdist, uint64_t seedlength,
+                       vsa_result **result);
+
+/* vmatch -l L -h K [-seedlength S] [-p] -q Q IDX (findquerymatches,
+   Vmengine/fquery.c:1009-1058, with processexactquerymatch extending every
+   MEM, Vmengine/procexqu.c:65-94): the seed length rule, vsa_findquerymatches
+   on the batch -- with palindromic != 0 on its reverse complement
+   (vsa_queries_reverse_complement) --, vsa_extend_hamming; the seed list is
+   freed.  A seed length below the prefix length of the index is the
+   reference's error "searchlength=%lu must be >= %lu=prefixlen"
+   (fquery.c:440-446). */
+int vsa_findquerymatches_hamming(const vsa_index *index,
+                                 const vsa_queries *queries,
+                                 uint64_t leastlength, uint64_t maxdist,
+                                 uint64_t seedlength, int palindromic,
+                                 vsa_result **result);
+/* vmatch -l L -h K [-seedlength S] IDX (findselfmatches,
+   Vmengine/fself.c:203-300, with simpleselfmatchoutput extending every
+   maximal repeat, fself.c:95-146): the same with vsa_findmaximalrepeats. */
+int vsa_findselfmatches_hamming(const vsa_index *index, uint64_t leastlength,
+                                uint64_t maxdist, uint64_t seedlength,
+                                vsa_result **result);
+
+/*
+  The same extension on the host: what the kernels are measured against, and
+  what a caller uses beyond the limits of the device path (any K up to
+  VSA_HAMMING_MAXDISTANCE).  layout: kind VSA_SINK_QUERY -- numofqueries,
+  querystart and querylength describe where the sequences lie in
+  querysymbols (for the -p pass: the reverse complements in the same places)
+  -- or VSA_SINK_SELF (querysymbols NULL); totallength symbols at text,
+  numofchars for the E-values.  threads 0 = one per processor.  The matches go
+  to matches[0 .. capacity) in the order of their seeds, -3 if there are
+  more (capacity = numofseeds always suffices); -2 with "record %lu does not
+  fit the layout" for a seed outside the index or its query sequence.
+*/
+int vsa_extend_hamming_host(const vsa_sinkparams *layout, const uint8_t *text,
+                            const uint8_t *querysymbols,
+                            const vsa_match *seeds, uint64_t numofseeds,
+                            uint64_t leastlength, uint64_t maxdist,
+                            uint64_t seedlength, int threads,
+                            vsa_match *matches, uint64_t capacity,
+                            uint64_t *numofmatches);
+/* max(S, L / (K + 1)), Vmatch/matchlenparm.c:11-22 */
+uint64_t vsa_extend_seedlength(uint64_t leastlength, uint64_t maxdist,
+                               uint64_t seedlength);
+
 #ifdef __cplusplus
 }
 #endif

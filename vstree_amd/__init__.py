@@ -426,6 +426,17 @@ def _load():
         "vsa_queries_translate_ms": (C.c_double, [V]),
         "vsa_translated_convert": (I, [V, V, PP, V, U64]),
         "vsa_translated_convert_host": (I, [V, U64, V, U64, U64, V, V]),
+        "vsa_extend_maxdist": (U32, []),
+        "vsa_extend_lane_budget": (U32, []),
+        "vsa_extend_long_step": (U32, []),
+        "vsa_extend_seedlength": (U64, [U64, U64, U64]),
+        "vsa_extend_hamming": (I, [V, V, V, C.POINTER(SinkParams), I, U64,
+                                   U64, U64, PP]),
+        "vsa_findquerymatches_hamming": (I, [V, V, U64, U64, U64, I, PP]),
+        "vsa_findselfmatches_hamming": (I, [V, U64, U64, U64, PP]),
+        "vsa_extend_hamming_host": (I, [C.POINTER(SinkParams), V, V, V, U64,
+                                        U64, U64, U64, I, V, U64,
+                                        C.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1048,6 +1059,9 @@ SINK_COMPLETE, SINK_QUERY, SINK_SELF, SINK_APPROX_EDIST, \
 # query Multiseq of the layout is the DNA one; lines with the flags F / G
 # (_COMPLETE: the records of findcompletematches on such a batch)
 SINK_TRANSLATED, SINK_TRANSLATED_COMPLETE = 5, 6
+# vmatch -l L -h K outside -complete: records of extended seeds, the distance
+# in the top 16 bits of the length (hamming_lengths / hamming_distances)
+SINK_QUERY_HAMMING, SINK_SELF_HAMMING = 8, 9
 SHOW_ABSOLUTE, SHOW_NODIST, SHOW_NOEVALUE, SHOW_NOSCORE, SHOW_NOIDENTITY = (
     1, 2, 4, 8, 16)
 
@@ -2004,3 +2018,89 @@ def measure_stream_read(nbytes=1 << 30, device=0):
     g = C.c_double()
     _check(lib.vsa_measure_stream_read(nbytes, device, C.byref(g)))
     return g.value
+
+
+# ---- degenerate matches: vmatch -l L -h K [-seedlength S] [-q Q] IDX ---------
+
+HAMMING_LENGTHBITS = 48
+HAMMING_MAXDISTANCE = 0xFFFF
+# limits of the device path (include/vstree_amd.h); VSA_EXTEND_STAGE=lane|long
+# in the environment forces one scan stage
+EXTEND_MAXDIST = int(lib.vsa_extend_maxdist())
+EXTEND_LANE_BUDGET = int(lib.vsa_extend_lane_budget())
+EXTEND_LONG_STEP = int(lib.vsa_extend_long_step())
+
+
+def hamming_lengths(matches):
+    """the lengths of records of extended seeds"""
+    return matches["length"] & np.uint64((1 << HAMMING_LENGTHBITS) - 1)
+
+
+def hamming_distances(matches):
+    """... and their numbers of mismatches"""
+    return matches["length"] >> np.uint64(HAMMING_LENGTHBITS)
+
+
+def extend_seedlength(leastlength, maxdist, seedlength=0):
+    """max(S, L / (K + 1)), Vmatch/matchlenparm.c:11-22"""
+    return int(lib.vsa_extend_seedlength(int(leastlength), int(maxdist),
+                                         int(seedlength)))
+
+
+def extend_hamming(index, queries, seeds, leastlength, maxdist, seedlength=0,
+                   palindromic=False):
+    """hammingextend (kurtz/extendHD.c:166) for every seed of a Result:
+    queries = the forward batch of MEM seeds (palindromic: found on its
+    reverse complement), or None for the seeds of findmaximalrepeats"""
+    p = SinkParams()
+    p.kind = SINK_SELF if queries is None else SINK_QUERY
+    h = C.c_void_p()
+    _check(lib.vsa_extend_hamming(index._h,
+                                  None if queries is None else queries._h,
+                                  seeds._h, C.byref(p), int(bool(palindromic)),
+                                  int(leastlength), int(maxdist),
+                                  int(seedlength), C.byref(h)))
+    return Result(h)
+
+
+def findquerymatches_hamming(index, queries, leastlength, maxdist,
+                             seedlength=0, palindromic=False):
+    """vmatch -l L -h K [-seedlength S] [-p] -q Q IDX"""
+    h = C.c_void_p()
+    _check(lib.vsa_findquerymatches_hamming(index._h, queries._h,
+                                            int(leastlength), int(maxdist),
+                                            int(seedlength),
+                                            int(bool(palindromic)),
+                                            C.byref(h)))
+    return Result(h)
+
+
+def findselfmatches_hamming(index, leastlength, maxdist, seedlength=0):
+    """vmatch -l L -h K [-seedlength S] IDX"""
+    h = C.c_void_p()
+    _check(lib.vsa_findselfmatches_hamming(index._h, int(leastlength),
+                                           int(maxdist), int(seedlength),
+                                           C.byref(h)))
+    return Result(h)
+
+
+def extend_hamming_host(text, seeds, leastlength, maxdist, seedlength=0,
+                        queries=None, numofchars=4, threads=0):
+    """the same extension on the host, any distance bound: text = the symbols
+    of the index, queries = (symbols, start, length) of the batch the seeds
+    refer to (for -p: its reverse complement), or None for self seeds"""
+    text = np.ascontiguousarray(text, np.uint8)
+    seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
+    p, keep = sink_params(SINK_SELF if queries is None else SINK_QUERY,
+                          len(text), (), numofchars=numofchars,
+                          querystart=None if queries is None else queries[1],
+                          querylength=None if queries is None else queries[2])
+    qsym = None if queries is None else np.ascontiguousarray(queries[0],
+                                                             np.uint8)
+    out = np.zeros(len(seeds), MATCH_DTYPE)
+    n = C.c_uint64()
+    _check(lib.vsa_extend_hamming_host(
+        C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds), len(seeds),
+        int(leastlength), int(maxdist), int(seedlength), int(threads),
+        _ptr(out), len(out), C.byref(n)))
+    return out[:n.value]

@@ -755,6 +755,13 @@ extern "C" int vsa_coverage_mark(vsa_coverage *c, const vsa_result *r,
               "to mark");
     return VSA_NOT_COVERED;
   }
+  if (r->extended)
+  {
+    VSA_ERROR("vsa_coverage_mark: lists of extended seeds "
+              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
+              "covered");
+    return VSA_NOT_COVERED;
+  }
   if (p->selfpalindromic)
   {
     VSA_ERROR("vsa_coverage_mark: lists of vmatch -p IDX (selfpalindromic) "

@@ -122,6 +122,13 @@ static inline int vsa_layout_view(const vsa_sinkparams *layout,
     return vsa_fail(VSA_NOT_COVERED, "%s: lists of a six-frame translated "
                     "batch (VSA_SINK_TRANSLATED) are not covered", who);
   }
+  if (layout->kind == VSA_SINK_QUERY_HAMMING ||
+      layout->kind == VSA_SINK_SELF_HAMMING)
+  {
+    return vsa_fail(VSA_NOT_COVERED, "%s: lists of extended seeds "
+                    "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
+                    "covered", who);
+  }
   if (layout->kind < VSA_SINK_COMPLETE ||
       layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
       layout->totalquerylength + 1 > layout->totallength ||

@@ -44,6 +44,9 @@ static const double averagequot[] = {
     8.22e+02, 1.78e+03, 3.91e+03, 8.50e+03, 1.76e+04, 3.78e+04, 7.98e+04,
     1.66e+05, 3.58e+05, 7.44e+05, 1.52e+06, 3.20e+06, 6.40e+06, 1.31e+07};
 
+#define ISSELF(kind) \
+  ((kind) == VSA_SINK_SELF || (kind) == VSA_SINK_SELF_HAMMING)
+
 typedef vsa_evalues Evalues; /* evalues.h: shared with select_host.c */
 
 /* strings that depend on (distance, length) only, per formatting thread:
@@ -203,7 +206,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
   if (params->numofsequences == 0 || params->totallength == 0 ||
       params->numofchars < 2 ||
       (params->numofsequences > 1 && params->markpos == NULL) ||
-      (params->kind != VSA_SINK_SELF && params->numofqueries > 0 &&
+      (!ISSELF(params->kind) && params->numofqueries > 0 &&
        (params->querystart == NULL || params->querylength == NULL)))
   {
     return vsa_fail(-1, "vsa_sink_open: incomplete parameters");
@@ -229,7 +232,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
   {
     memcpy(s->dbmarkpos, params->markpos, nsep * 8);
   }
-  if (params->kind != VSA_SINK_SELF && params->numofqueries > 0)
+  if (!ISSELF(params->kind) && params->numofqueries > 0)
   {
     memcpy(s->qstart, params->querystart, params->numofqueries * 8);
     memcpy(s->qlength, params->querylength, params->numofqueries * 8);
@@ -246,7 +249,7 @@ int vsa_sink_open(const vsa_sinkparams *params, vsa_sink **sink)
   s->wseq1 = digitsof(params->numofsequences - params->numofquerysequences);
   s->wpos2 = s->wpos1;
   s->wseq2 = s->wseq1;
-  if (params->kind != VSA_SINK_SELF)
+  if (!ISSELF(params->kind))
   {
     s->wpos2 = digitsof(params->querytotallength);
     s->wseq2 = digitsof(params->numofqueries);
@@ -421,14 +424,18 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   uint8_t reverse = 0; /* VSA_SINK_TRANSLATED: a reverse frame, flag G */
   const int istranslated = s->p.kind == VSA_SINK_TRANSLATED ||
                            s->p.kind == VSA_SINK_TRANSLATED_COMPLETE;
-  const int isquery = s->p.kind != VSA_SINK_SELF;
+  const int isquery = !ISSELF(s->p.kind);
+  /* extended seeds: the distance travels in the top bits of the length */
+  const int isextended = s->p.kind == VSA_SINK_QUERY_HAMMING ||
+                         s->p.kind == VSA_SINK_SELF_HAMMING;
   const int iscomplete = s->p.kind == VSA_SINK_COMPLETE ||
                          s->p.kind == VSA_SINK_APPROX_EDIST ||
                          s->p.kind == VSA_SINK_APPROX_HAMMING ||
                          s->p.kind == VSA_SINK_TRANSLATED_COMPLETE;
 
   position1 = m->dbstart;
-  length1 = m->length;
+  length1 =
+      isextended ? VSA_HAMMING_LENGTH(m->length) : m->length;
   seqinfo(s, position1, &seqnum1, &start1, &len1seq);
   if (isquery)
   {
@@ -454,11 +461,12 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
       length2 = dna.length;
       relpos2 = dna.querystart;
       distance = 0;
-    } else if (s->p.kind == VSA_SINK_QUERY)
+    } else if (s->p.kind == VSA_SINK_QUERY || isextended)
     {
-      length2 = m->length;
+      /* hammingextend stores the negative (kurtz/extendHD.c:345) */
+      length2 = length1;
       relpos2 = m->querystart;
-      distance = 0;
+      distance = isextended ? -(int64_t) VSA_HAMMING_DISTANCE(m->length) : 0;
     } else
     {
       /* initcompletematchstruct, Vmengine/initcompl.c:7-21 */
@@ -485,8 +493,8 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   {
     /* self match: (length, start1, start2), Vmengine/fself.c:95-125 */
     uint64_t start2, len2seq;
-    length2 = m->length;
-    distance = 0;
+    length2 = length1;
+    distance = isextended ? -(int64_t) VSA_HAMMING_DISTANCE(m->length) : 0;
     seqinfo(s, m->queryseq, &seqnum2, &start2, &len2seq);
     relpos2 = m->queryseq - start2;
     position2 = m->queryseq;
@@ -638,6 +646,17 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
       if (matches[i].querystart > maxd)
       {
         maxd = matches[i].querystart;
+      }
+    }
+  }
+  if (s->p.kind == VSA_SINK_QUERY_HAMMING ||
+      s->p.kind == VSA_SINK_SELF_HAMMING)
+  {
+    for (i = 0; i < n; i++)
+    {
+      if (VSA_HAMMING_DISTANCE(matches[i].length) > maxd)
+      {
+        maxd = VSA_HAMMING_DISTANCE(matches[i].length);
       }
     }
   }

@@ -114,6 +114,12 @@ int gate(const char *who, const char *noun, const char *doing, const H *c,
     VSA_ERROR("%s: a packed candidate result has no records to %s", who, noun);
     return VSA_NOT_COVERED;
   }
+  if (r->extended)
+  {
+    VSA_ERROR("%s: lists of extended seeds (VSA_SINK_QUERY_HAMMING, "
+              "VSA_SINK_SELF_HAMMING) are not covered", who);
+    return VSA_NOT_COVERED;
+  }
   const char *refusal = form();
   if (refusal != nullptr)
   {

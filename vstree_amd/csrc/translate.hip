@@ -726,6 +726,13 @@ extern "C" int vsa_translated_convert(const vsa_result *result,
               "records to convert");
     return VSA_NOT_COVERED;
   }
+  if (result->extended)
+  {
+    VSA_ERROR("vsa_translated_convert: lists of extended seeds "
+              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
+              "covered");
+    return VSA_NOT_COVERED;
+  }
   if (protein->dnalength == nullptr)
   {
     VSA_ERROR("vsa_translated_convert: the batch is not a six-frame "

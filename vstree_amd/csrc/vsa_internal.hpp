@@ -238,6 +238,10 @@ struct vsa_result
   // queryseq << 16 | querystart that go with them
   uint32_t packbits;
   uint64_t *packvals;
+  // extended seeds (extend.hip): `length` carries a distance in its top 16
+  // bits (VSA_HAMMING_DISTANCE), which only fetch, copy and the sink know of;
+  // the handles that post-process lists refuse such a list
+  bool extended = false;
 };
 
 // pairs of a packed result as records on the device (esa_search.hip)
