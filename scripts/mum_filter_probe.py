@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""The MUM filter on the two paths bench.py does not take: candidate RECORDS
-(vsa_mumuniqueinquery: composite keys + index, sorted on all bits) and packed
+"""The MUM filter on the paths bench.py does not take: candidate RECORDS
+(vsa_mumuniqueinquery: composite keys + index, sorted on all bits), packed
 PAIRS with a run of equal dbstarts that is too long for the filter by runs
 (vsa_mumuniqueinquery_range_packed: sorted on dbstart, filtered, sorted on
-all bits, filtered again).
+all bits, filtered again), and WIDE records (the first list with dbstart +
+2^40 and length + 2^30, which no key holds: the records sorted twice, the
+filter on the sorted records).
 
   mum_filter_probe.py [--root TREE] [n]
 
@@ -54,6 +56,18 @@ def probe(name, call):
 dp = V.device_malloc(cand.nbytes)
 V.device_upload(dp, cand)
 probe("records", lambda: V.mumuniqueinquery(dp, n))
+wide = cand.copy()
+wide["dbstart"] += np.uint64(1 << 40)
+wide["length"] += np.uint64(1 << 30)
+
+
+def widecall():
+    V.device_upload(dp, wide)  # (the wide form sorts the records in place)
+    return V.mumuniqueinquery(dp, n)
+
+
+probe("wide records", widecall)
+del wide
 V.device_free(dp)
 
 cand["dbstart"][:200] = 3 * n // 2

@@ -1,9 +1,11 @@
 """The MUM filter (kurtz/cleanMUMcand.c:55-118) driven directly: synthetic
 candidates, no index and no search, every sorter in front of the one tiled
-filter, sizes around its tile of 1024 keys.  Expected: the CPU oracle.
+filter -- packed keys, and wide records that fit no key and go through the
+same tiles as sorted records -- sizes around its tile of 1024 candidates.
+Expected: the CPU oracle.
 
 The oracle itself was checked once, on the CPU, on every list used here (both
-carries, the wide list included) against a rendering of the rule in numpy --
+carries, the wide lists included) against a rendering of the rule in numpy --
 sort by (dbstart, length descending), exclusive running maximum of the right
 ends starting at the carry, keep a candidate iff that maximum is below its
 right end and the next candidate does not have its dbstart and length --
@@ -91,19 +93,22 @@ def rule(cand, carry):
 
 
 WIDE = dict(n=3000, planted=True, dbbase=1 << 40, lenbase=(1 << 30) - 20)
+WIDES = [WIDE] + [dict(WIDE, n=n) for n in (5000, 1, 2, 1023, 1024, 1025)]
 LISTS = ([dict(n=n, planted=True) for n in SIZES] +
-         [dict(n=5000, planted=False), WIDE])
+         [dict(n=5000, planted=False)] + WIDES)
 
 
 def test_lists_are_what_they_claim():
-    c = candidates(5000)
-    d = np.sort(c["dbstart"])
-    for b in (1024, 2048, 3072):
-        assert d[b - 1] == d[b] and (d == d[b]).sum() >= 91
+    for c in (candidates(5000), candidates(**WIDES[1])):
+        d = np.sort(c["dbstart"])
+        for b in (1024, 2048, 3072):
+            assert d[b - 1] == d[b] and (d == d[b]).sum() >= 91
     assert np.unique(candidates(5000, False)["dbstart"]).size == 5000
-    w = candidates(**WIDE)
-    assert w["dbstart"].min() >= 1 << 40 and w["length"].min() >= 1 << 30
-    assert w["length"].max() < (1 << 30) + 300
+    for kw in WIDES:
+        w = candidates(**kw)
+        assert len(w) == kw["n"]
+        assert w["dbstart"].min() >= 1 << 40 and w["length"].min() >= 1 << 30
+        assert w["length"].max() < (1 << 30) + 300
 
 
 @pytest.mark.parametrize("which", range(len(LISTS)))
@@ -181,14 +186,24 @@ def test_pairs_without_runs(V, whichcarry):
 
 
 @pytest.mark.gpu
-def test_wide_records(V):
+@pytest.mark.parametrize("whichcarry", (0, 1))
+@pytest.mark.parametrize("which", range(len(WIDES)))
+def test_wide_records(V, which, whichcarry):
     """dbstart of 41 bits and length of 31 do not fit into one key: two sorts
-    of the records, the filter on the sorted records"""
-    cand = candidates(**WIDE)
-    want = expected(WIDE["n"], True, 0, WIDE["dbbase"], WIDE["lenbase"])
+    of the records, the tiled filter on the sorted records (runs across tile
+    boundaries in the list of 5000), which sums the lengths itself"""
+    kw = WIDES[which]
+    cand = candidates(**kw)
+    n = len(cand)
+    want = expected(n, True, whichcarry, kw["dbbase"], kw["lenbase"])
     dp = V.device_malloc(cand.nbytes)
-    V.device_upload(dp, cand)
     try:
-        check(V.mumuniqueinquery(dp, len(cand)), want, len(cand))
+        V.device_upload(dp, cand)
+        check(V.mumuniqueinquery_range(dp, n, carries(cand)[whichcarry]),
+              want, n)
+        if whichcarry == 0:
+            # (the filter sorts the caller's records in place: any order in)
+            V.device_upload(dp, cand)
+            check(V.mumuniqueinquery(dp, n), want, n)
     finally:
         V.device_free(dp)

@@ -180,27 +180,6 @@ k_partition_place(const PartInput in, uint64_t n,
 #define VSA_PT_TILE (VSA_BLOCK * VSA_PT_ITEMS)
 #define VSA_PT_SMALL 8
 
-#define VSA_DPP64(old, v, ctrl, rowmask)                                      \
-  (((uint64_t) (uint32_t) __builtin_amdgcn_update_dpp(                        \
-        (int) ((old) >> 32), (int) ((v) >> 32), ctrl, rowmask, 0xF, false)    \
-    << 32) |                                                                  \
-   (uint32_t) __builtin_amdgcn_update_dpp((int) (old), (int) (v), ctrl,       \
-                                          rowmask, 0xF, false))
-
-// lane 63 receives the maximum of all 64 lanes (an inclusive scan with max;
-// lanes without a source keep their own value)
-__device__ __forceinline__ uint64_t vsa_wave_inclusive_max64(uint64_t x)
-{
-  uint64_t y;
-  y = VSA_DPP64(x, x, 0x111, 0xF); x = y > x ? y : x; // row_shr:1
-  y = VSA_DPP64(x, x, 0x112, 0xF); x = y > x ? y : x; // row_shr:2
-  y = VSA_DPP64(x, x, 0x114, 0xF); x = y > x ? y : x; // row_shr:4
-  y = VSA_DPP64(x, x, 0x118, 0xF); x = y > x ? y : x; // row_shr:8
-  y = VSA_DPP64(x, x, 0x142, 0xA); x = y > x ? y : x; // row_bcast:15
-  y = VSA_DPP64(x, x, 0x143, 0xC); x = y > x ? y : x; // row_bcast:31
-  return x;
-}
-
 // first position of part j: ceil(j (T + 1) / nparts); nothing lies in the
 // parts from nparts on
 __device__ __forceinline__ void part_bounds(uint64_t *bound, uint32_t nparts,

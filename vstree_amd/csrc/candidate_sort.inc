@@ -1,6 +1,6 @@
 // K4s: MUM candidates thrown into dbstart buckets, every bucket sorted AND
 // filtered in LDS -- kernels and their host driver; included by esa_search.hip
-// behind mum_filter.inc, whose rule (k_mumf_flags<false>) and scans it uses.
+// behind mum_filter.inc, whose rule (vsa_mum_alone_in_run) and scans it uses.
 //
 // The rule asks for the (key, value) pairs in order of dbstart = key >>
 // lenbits, in ANY order inside a run of equal dbstarts -- runs are looked at as
@@ -60,7 +60,7 @@
 // every index by VSA_CS_CAP, the bucket's count or the number of
 // candidates), and the caller backs off on an index whose batches keep doing
 // this (vsa_index::cs_skip).  A run of more than VSA_RUN_LIMIT equal dbstarts
-// raises bit 0 as k_mumf_flags does, and the caller sorts on all bits.
+// raises bit 0 (vsa_mum_alone_in_run), and the caller sorts on all bits.
 //
 // Measured on MI355X: profiles/r05/ (probe of the scatter, the sort alone)
 // and profiles/r12/ (sort and filter in one kernel); DESIGN.md section 5
@@ -74,7 +74,8 @@
 // run of up to VSA_RUN_LIMIT = 64 equal dbstarts, which the filter's first
 // attempt accepts, fits several times.)
 #define VSA_CS_BINLIMIT 256
-// bit of the filter's flag word (bit 0: "a run was too long", k_mumf_flags)
+// bit of the filter's flag word (bit 0: "a run was too long",
+// vsa_mum_alone_in_run)
 #define VSA_CS_OVERFLOW 2u
 
 struct CsGeometry
@@ -369,22 +370,8 @@ k_cs_scatter(CsSources src, CsTiles t, CsGeometry g,
   }
 }
 
-// inclusive running maximum over the 64 lanes
-__device__ __forceinline__ uint64_t vsa_wave_inclusive_max(uint64_t v)
-{
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint64_t o =
-        vsa_shfl64(v, (int) (lane >= (uint32_t) d ? lane - d : lane));
-    v = lane >= (uint32_t) d && o > v ? o : v;
-  }
-  return v;
-}
-
 // A workgroup per bucket: its pairs sorted on the `shift` low dbstart bits in
-// LDS, filtered there by the rule of k_mumf_flags<false>, and the survivors
+// LDS, filtered there by the rule (vsa_mum_alone_in_run), and the survivors
 // written back in order to the front of the bucket's staging region --
 // staging[b * VSA_CS_CAP + i], i < bsurv[b]; blen[b] = the sum of their
 // lengths.  (The workgroup owns the region and has read all of it into
@@ -593,9 +580,8 @@ k_cs_filter(typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
     {
       const uint32_t i = r * VSA_BLOCK + threadIdx.x;
       const uint64_t incl =
-          vsa_wave_inclusive_max(i < c ? rightend(keyat(i)) : 0);
-      const uint64_t prev = vsa_shfl64(incl, (int) (lane > 0 ? lane - 1 : 0));
-      before[r] = lane > 0 ? prev : 0;
+          vsa_wave_inclusive_scan<1>(i < c ? rightend(keyat(i)) : 0);
+      before[r] = vsa_wave_exclusive(incl);
       if (lane == 63)
       {
         segmax[r * (VSA_BLOCK / 64) + wave] = incl;
@@ -607,16 +593,14 @@ k_cs_filter(typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
   // from the buckets in front, the segments in front
   if (threadIdx.x < 64)
   {
-    const uint64_t incl =
-        vsa_wave_inclusive_max(lane < nsegs ? segmax[lane] : 0);
-    const uint64_t prev = vsa_shfl64(incl, (int) (lane > 0 ? lane - 1 : 0));
+    const uint64_t mine = vsa_wave_exclusive(vsa_wave_inclusive_scan<1>(
+        lane < nsegs ? segmax[lane] : 0));
     uint64_t start = bcarry[b];
     start = carry > start ? carry : start;
-    const uint64_t mine = lane > 0 ? prev : 0;
     segmax[lane] = mine > start ? mine : start;
   }
   __syncthreads();
-  // who survives: k_mumf_flags<false>, word for word, on LDS
+  // who survives
   uint32_t okbits = 0;
   uint64_t len = 0;
 #pragma unroll
@@ -633,37 +617,8 @@ k_cs_filter(typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
         const uint64_t e = rightend(kk);
         const uint64_t seg = segmax[r * (VSA_BLOCK / 64) + wave];
         const uint64_t run = seg > before[r] ? seg : before[r];
-        ok = run < e;
-        if (ok)
-        {
-          const uint64_t d = kk >> g.lenbits;
-          uint32_t steps = 0;
-          for (uint32_t j = i; j > 0 && (keyat(j - 1) >> g.lenbits) == d; j--)
-          {
-            if (rightend(keyat(j - 1)) >= e || ++steps > VSA_RUN_LIMIT)
-            {
-              ok = false;
-              break;
-            }
-          }
-          if (steps > VSA_RUN_LIMIT)
-          {
-            atomicOr(flag, 1u);
-          }
-          steps = 0;
-          for (uint32_t j = i + 1;
-               ok && j < c && (keyat(j) >> g.lenbits) == d; j++)
-          {
-            if (rightend(keyat(j)) >= e || ++steps > VSA_RUN_LIMIT)
-            {
-              ok = false;
-            }
-          }
-          if (steps > VSA_RUN_LIMIT)
-          {
-            atomicOr(flag, 1u);
-          }
-        }
+        ok = run < e && vsa_mum_alone_in_run(keyat, g.lenbits, i, c,
+                                             kk >> g.lenbits, e, flag);
       }
       const uint64_t mask = __ballot(ok);
       if (lane == 0)
@@ -679,13 +634,7 @@ k_cs_filter(typename CsForm<VAL, SMALL>::Entry *__restrict__ staging,
   if (threadIdx.x < 64)
   {
     const uint32_t v = lane < nsegs ? segcount[lane] : 0;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-      const uint32_t o = __shfl_up(incl, d, 64);
-      incl += lane >= (uint32_t) d ? o : 0;
-    }
+    const uint32_t incl = vsa_wave_inclusive_scan<0>(v);
     segcount[lane] = incl - v;
     if (lane == 63)
     {

@@ -401,7 +401,7 @@ k_cov_tilecount(CovRange r, uint64_t *__restrict__ tilecount)
     }
   }
   uint64_t total;
-  (void) tc_block_exsum(c, sh, total);
+  (void) vsa_block_exclusive_scan<0, TC_BLOCK>(c, sh, total);
   if (threadIdx.x == 0)
   {
     tilecount[tile] = total;
@@ -431,7 +431,8 @@ k_cov_emit(CovRange r, const uint64_t *__restrict__ tileoffset,
     c += (uint64_t) __popcll((unsigned long long) word[j]);
   }
   uint64_t total;
-  uint64_t o = tileoffset[tile] + tc_block_exsum(c, sh, total);
+  uint64_t o = tileoffset[tile] +
+               vsa_block_exclusive_scan<0, TC_BLOCK>(c, sh, total);
 #pragma unroll
   for (int j = 0; j < TC_IPT; j++)
   {
@@ -495,7 +496,7 @@ k_cov_popcount(const uint64_t *__restrict__ bits, uint64_t nwords,
     c += (uint64_t) __popcll((unsigned long long) bits[w]);
   }
   uint64_t total;
-  (void) tc_block_exsum(c, sh, total);
+  (void) vsa_block_exclusive_scan<0, TC_BLOCK>(c, sh, total);
   if (threadIdx.x == 0 && total != 0)
   {
     atomicAdd(sum, (unsigned long long) total);

@@ -1446,6 +1446,83 @@ __device__ __forceinline__ uint64_t vsa_shfl64(uint64_t v, int src)
   return ((uint64_t) hi << 32) | lo;
 }
 
+__device__ __forceinline__ uint32_t vsa_shfl(uint32_t v, int src)
+{
+  return __shfl(v, src, 64);
+}
+
+__device__ __forceinline__ uint64_t vsa_shfl(uint64_t v, int src)
+{
+  return vsa_shfl64(v, src);
+}
+
+// The scans of the tree.  OP: 0 sum, 1 max; T: uint32_t or uint64_t.
+template <int OP, typename T>
+__device__ __forceinline__ T vsa_scan_op(T a, T b)
+{
+  return OP == 0 ? a + b : (b > a ? b : a);
+}
+
+// inclusive scan over the 64 lanes by shuffles (Hillis-Steele).  Must be
+// reached by all 64 lanes.
+template <int OP, typename T>
+__device__ __forceinline__ T vsa_wave_inclusive_scan(T v)
+{
+  const uint32_t lane = vsa_lane();
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1)
+  {
+    const T o = vsa_shfl(v, (int) (lane >= d ? lane - d : lane));
+    if (lane >= d)
+    {
+      v = vsa_scan_op<OP>(v, o);
+    }
+  }
+  return v;
+}
+
+// what the lanes in front of this one hold, from the inclusive scan (0 for
+// lane 0: the values are unsigned)
+template <typename T>
+__device__ __forceinline__ T vsa_wave_exclusive(T incl)
+{
+  const uint32_t lane = vsa_lane();
+  const T prev = vsa_shfl(incl, (int) (lane > 0 ? lane - 1 : 0));
+  return lane > 0 ? prev : 0;
+}
+
+// exclusive scan of one value per thread of a workgroup of BLOCK threads (one
+// dimension); total = sum / max of all.  sh: BLOCK / 64 words of LDS, free
+// again when this returns.  Must be reached by the whole workgroup.
+template <int OP, int BLOCK, typename T>
+__device__ __forceinline__ T vsa_block_exclusive_scan(T v, T *sh, T &total)
+{
+  const uint32_t lane = vsa_lane(), wave = threadIdx.x >> 6;
+  const T incl = vsa_wave_inclusive_scan<OP>(v);
+  if (lane == 63)
+  {
+    sh[wave] = incl;
+  }
+  __syncthreads();
+  T before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < BLOCK / 64; w++)
+  {
+    const T x = sh[w];
+    before = w < wave ? vsa_scan_op<OP>(before, x) : before;
+    all = vsa_scan_op<OP>(all, x);
+  }
+  __syncthreads();
+  total = all;
+  if constexpr (OP == 0)
+  {
+    return before + incl - v;
+  } else
+  {
+    return vsa_scan_op<OP>(before, vsa_wave_exclusive(incl));
+  }
+}
+
 // Every lane of the wavefront brings a count c; one atomic per wavefront
 // reserves the sum in *cursor and each lane gets the start of its own range.
 // Must be reached by all 64 lanes.
@@ -1453,17 +1530,7 @@ __device__ __forceinline__ uint64_t
 vsa_wave_reserve(unsigned long long *cursor, uint32_t c)
 {
   const uint32_t lane = vsa_lane();
-  uint32_t incl = c;
-
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t) d)
-    {
-      incl += v;
-    }
-  }
+  const uint32_t incl = vsa_wave_inclusive_scan<0>(c);
   const uint32_t total = __shfl(incl, 63, 64);
   uint64_t base = 0;
   if (lane == 63 && total > 0)
@@ -1506,4 +1573,25 @@ __device__ __forceinline__ uint32_t vsa_wave_inclusive_sum(uint32_t v)
   x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false); // row_bcast:15
   x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false); // row_bcast:31
   return (uint32_t) x;
+}
+
+#define VSA_DPP64(old, v, ctrl, rowmask)                                      \
+  (((uint64_t) (uint32_t) __builtin_amdgcn_update_dpp(                        \
+        (int) ((old) >> 32), (int) ((v) >> 32), ctrl, rowmask, 0xF, false)    \
+    << 32) |                                                                  \
+   (uint32_t) __builtin_amdgcn_update_dpp((int) (old), (int) (v), ctrl,       \
+                                          rowmask, 0xF, false))
+
+// lane 63 receives the maximum of all 64 lanes (an inclusive scan with max;
+// lanes without a source keep their own value)
+__device__ __forceinline__ uint64_t vsa_wave_inclusive_max64(uint64_t x)
+{
+  uint64_t y;
+  y = VSA_DPP64(x, x, 0x111, 0xF); x = y > x ? y : x; // row_shr:1
+  y = VSA_DPP64(x, x, 0x112, 0xF); x = y > x ? y : x; // row_shr:2
+  y = VSA_DPP64(x, x, 0x114, 0xF); x = y > x ? y : x; // row_shr:4
+  y = VSA_DPP64(x, x, 0x118, 0xF); x = y > x ? y : x; // row_shr:8
+  y = VSA_DPP64(x, x, 0x142, 0xA); x = y > x ? y : x; // row_bcast:15
+  y = VSA_DPP64(x, x, 0x143, 0xC); x = y > x ? y : x; // row_bcast:31
+  return x;
 }

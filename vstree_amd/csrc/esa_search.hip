@@ -304,17 +304,27 @@ struct SortedPairs
 {
   DevBuf k2, v2, flag, keep, tmax, tcarry, tcount, toff, tsum, tsumscan;
   uint64_t n = 0, ntiles = 0;
-  // ... and the room for the MUMs
-  int alloc(uint64_t ncand, size_t valbytes, DevBuf &mums)
+  // the tiles and the room for the MUMs (all that sorted records need) ...
+  int alloc_tiles(uint64_t ncand, DevBuf &mums)
   {
     n = ncand;
     ntiles = (ncand + VSA_FT_TILE - 1) / VSA_FT_TILE;
     return tmax.alloc((ntiles + 1) * 8) || tcarry.alloc((ntiles + 1) * 8) ||
            tcount.alloc((ntiles + 1) * 8) || toff.alloc((ntiles + 1) * 8) ||
            tsum.alloc((ntiles + 1) * 8) || tsumscan.alloc((ntiles + 1) * 8) ||
-           k2.alloc(ncand * 8) || v2.alloc(ncand * valbytes) ||
            keep.alloc(ntiles * VSA_FT_TILE) || flag.alloc(8) ||
            mums.alloc(ncand * sizeof(vsa_match));
+  }
+  // ... and the pairs
+  int alloc(uint64_t ncand, size_t valbytes, DevBuf &mums)
+  {
+    return alloc_tiles(ncand, mums) || k2.alloc(ncand * 8) ||
+           v2.alloc(ncand * valbytes);
+  }
+  template <typename WRITER>
+  PackedCands<WRITER> pairs(unsigned int lenbits, WRITER write)
+  {
+    return {{k2.as<uint64_t>(), lenbits}, v2.as<typename WRITER::VAL>(), write};
   }
 };
 
@@ -324,34 +334,34 @@ struct MumCounts
   uint64_t nmums, sumlength, flags;
 };
 
-// The filter on sorted pairs: SORTED = on all bits of the keys, else on
-// dbstart alone (then bit 0 of c->flags may come back up, and the MUMs are
-// not to be used).  carry = the reference's running `dbright` when it reaches
-// the first of these candidates: 0 for a whole job, the largest right end of
-// all candidates with a smaller dbstart when the list is one dbstart range of
-// a job that is filtered in pieces (multi-GPU).
-template <bool SORTED, typename WRITER>
-int mumfilter_tiles(SortedPairs &s, unsigned int lenbits, uint64_t carry,
-                    WRITER write, hipStream_t stream, DevBuf &mums,
-                    MumCounts *c)
+// The filter on the sorted candidates `cands` (a view of mum_filter.inc on
+// the s.n candidates): SORTED = by dbstart and, inside a run, longest first,
+// else by dbstart alone (then bit 0 of c->flags may come back up, and the
+// MUMs are not to be used).  carry = the reference's running `dbright` when
+// it reaches the first of these candidates: 0 for a whole job, the largest
+// right end of all candidates with a smaller dbstart when the list is one
+// dbstart range of a job that is filtered in pieces (multi-GPU).
+template <bool SORTED, typename CANDS>
+int mumfilter_tiles(SortedPairs &s, CANDS cands, uint64_t carry,
+                    hipStream_t stream, DevBuf &mums, MumCounts *c)
 {
-  using VAL = typename WRITER::VAL;
+  using Rule = typename CANDS::Rule;
   const dim3 tg = vsa_grid(s.ntiles);
-  k_mumf_tilemax<<<tg, VSA_BLOCK, 0, stream>>>(
-      s.k2.as<uint64_t>(), s.n, lenbits, s.tmax.as<uint64_t>());
+  k_mumf_tilemax<Rule><<<tg, VSA_BLOCK, 0, stream>>>(cands, s.n,
+                                                     s.tmax.as<uint64_t>());
   k_mumf_scan<1><<<1, VSA_BLOCK, 0, stream>>>(
       s.tmax.as<uint64_t>(), s.ntiles, carry, s.tcarry.as<uint64_t>());
-  k_mumf_flags<SORTED><<<tg, VSA_BLOCK, 0, stream>>>(
-      s.k2.as<uint64_t>(), s.n, lenbits, s.tcarry.as<uint64_t>(),
-      s.keep.as<uint8_t>(), s.tcount.as<uint64_t>(), s.tsum.as<uint64_t>(),
+  k_mumf_flags<SORTED, Rule><<<tg, VSA_BLOCK, 0, stream>>>(
+      cands, s.n, s.tcarry.as<uint64_t>(), s.keep.as<uint8_t>(),
+      s.tcount.as<uint64_t>(), s.tsum.as<uint64_t>(),
       s.flag.as<unsigned int>());
   // (offsets of the tiles and, in a second workgroup, the sum of the lengths)
   k_mumf_scan<0><<<2, VSA_BLOCK, 0, stream>>>(
       s.tcount.as<uint64_t>(), s.ntiles, 0, s.toff.as<uint64_t>(),
       s.tsum.as<uint64_t>(), s.tsumscan.as<uint64_t>());
-  k_mumf_write<WRITER><<<tg, VSA_BLOCK, 0, stream>>>(
-      s.k2.as<uint64_t>(), s.v2.as<VAL>(), s.keep.as<uint8_t>(), s.n,
-      s.toff.as<uint64_t>(), write, mums.as<vsa_match>());
+  k_mumf_write<<<tg, VSA_BLOCK, 0, stream>>>(
+      cands, s.keep.as<uint8_t>(), s.n, s.toff.as<uint64_t>(),
+      mums.as<vsa_match>());
   VSA_HIP(hipGetLastError());
   const Fetch f[3] = {{s.toff.as<uint64_t>() + s.ntiles, 8},
                       {s.tsumscan.as<uint64_t>() + s.ntiles, 8},
@@ -410,7 +420,8 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
   if (!allbits)
   {
     if (sort_radix<VAL>(keys_in, vals_in, s, rec.lenbits, endbit, stream) ||
-        mumfilter_tiles<false>(s, rec.lenbits, carry, rec, stream, mums, c))
+        mumfilter_tiles<false>(s, s.pairs(rec.lenbits, rec), carry, stream,
+                               mums, c))
     {
       return -100;
     }
@@ -418,7 +429,8 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
   }
   if (allbits &&
       (sort_radix<VAL>(keys_in, vals_in, s, 0, endbit, stream) ||
-       mumfilter_tiles<true>(s, rec.lenbits, carry, rec, stream, mums, c)))
+       mumfilter_tiles<true>(s, s.pairs(rec.lenbits, rec), carry, stream,
+                             mums, c)))
   {
     return -100;
   }
@@ -427,19 +439,19 @@ int mumfilter_packed(KeyIn keys_in, ValIn vals_in, uint64_t ncand,
 
 // wide records (dbstart and length do not fit into one key, or 2^32
 // candidates and more): least significant key first (length descending), then
-// a stable sort by dbstart; the filter on the sorted records
+// a stable sort by dbstart; the tiled filter on the sorted records
 int mumfilter_wide(DevBuf &cand, uint64_t ncand, uint64_t carry,
-                   hipStream_t stream, DevBuf &mums, uint64_t *nmums)
+                   hipStream_t stream, DevBuf &mums, MumCounts *c)
 {
-  DevBuf ends, dbright, keep, temp, dcount, sorted, k1, k2, kout;
-  if (ends.alloc(ncand * 8) || dbright.alloc(ncand * 8) ||
-      keep.alloc(ncand) || dcount.alloc(8) || k1.alloc(ncand * 8) ||
+  SortedPairs s;
+  DevBuf sorted, k1, k2, kout;
+  if (s.alloc_tiles(ncand, mums) || k1.alloc(ncand * 8) ||
       k2.alloc(ncand * 8) || kout.alloc(ncand * 8) ||
-      sorted.alloc(ncand * sizeof(vsa_match)) ||
-      mums.alloc(ncand * sizeof(vsa_match)))
+      sorted.alloc(ncand * sizeof(vsa_match)))
   {
     return -100;
   }
+  VSA_HIP(hipMemsetAsync(s.flag.p, 0, 8, stream));
   k_mum_keys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
       cand.as<vsa_match>(), ncand, k1.as<uint64_t>(), k2.as<uint64_t>());
   VSA_HIP(hipGetLastError());
@@ -457,36 +469,14 @@ int mumfilter_wide(DevBuf &cand, uint64_t ncand, uint64_t carry,
   {
     return -100;
   }
-  VSA_HIP(hipMemcpyAsync(sorted.p, cand.p, ncand * sizeof(vsa_match),
-                         hipMemcpyDeviceToDevice, stream));
-  k_mum_rightends<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-      sorted.as<vsa_match>(), ncand, ends.as<uint64_t>());
-  VSA_HIP(hipGetLastError());
-  VSA_HIP(rocprim_run(temp, [&](void *p, size_t &tb) {
-    return rocprim::exclusive_scan(p, tb, ends.as<uint64_t>(),
-                                   dbright.as<uint64_t>(), carry,
-                                   (size_t) ncand, rocprim::maximum<uint64_t>(),
-                                   stream);
-  }));
-  k_mum_flags<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-      sorted.as<vsa_match>(), ends.as<uint64_t>(), dbright.as<uint64_t>(),
-      ncand, keep.as<uint8_t>());
-  VSA_HIP(hipGetLastError());
-  if (compact_matches(sorted.as<vsa_match>(), keep.as<uint8_t>(), ncand,
-                      mums.as<vsa_match>(), dcount.as<uint64_t>(), stream))
-  {
-    return -100;
-  }
-  VSA_HIP(hipMemcpyAsync(nmums, dcount.p, 8, hipMemcpyDeviceToHost, stream));
-  VSA_HIP(hipStreamSynchronize(stream));
-  return 0;
+  return mumfilter_tiles<true>(s, RecordCands{cand.as<vsa_match>()}, carry,
+                               stream, mums, c);
 }
 
 // MUMs of candidate records, any order.  carry: see mumfilter_tiles.
 // dbbound / lenbound: upper bounds of dbstart and length if the caller knows
 // them (index length, longest query), else 0: they are looked up.
-// *sumlength = sum of the lengths of the MUMs, or ~0 if this call did not
-// compute it (the wide form).
+// *sumlength = sum of the lengths of the MUMs.
 int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
                      DevBuf &mums, uint64_t *nmums, uint64_t *sumlength,
                      uint64_t carry = 0, uint64_t dbbound = 0,
@@ -522,32 +512,36 @@ int mumuniqueinquery(DevBuf &cand, uint64_t ncand, hipStream_t stream,
     VSA_HIP(hipStreamSynchronize(stream));
   }
   const unsigned int lenbits = bitsfor(mx.len), dbbits = bitsfor(mx.db);
+  MumCounts c;
   if (lenbits + dbbits > 64 || ncand >= 0xFFFFFFFFull)
   {
-    *sumlength = ~0ull;
-    return mumfilter_wide(cand, ncand, carry, stream, mums, nmums);
-  }
-  // sorter: (composite key, index) over just the bits in use; the pair list
-  // of the records
-  SortedPairs s;
-  DevBuf k1, i1;
-  MumCounts c;
-  if (s.alloc(ncand, 4, mums) || k1.alloc(ncand * 8) ||
-      i1.alloc(ncand * 4))
+    if (mumfilter_wide(cand, ncand, carry, stream, mums, &c))
+    {
+      return -100;
+    }
+  } else
   {
-    return -100;
-  }
-  k_mum_compositekeys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
-      cand.as<vsa_match>(), ncand, lenbits, k1.as<uint64_t>(),
-      i1.as<uint32_t>());
-  VSA_HIP(hipGetLastError());
-  if (sort_radix<uint32_t>(k1.as<uint64_t>(), i1.as<uint32_t>(), s, 0,
-                           lenbits + dbbits, stream) ||
-      mumfilter_tiles<true>(s, lenbits, carry,
-                            GatheredRecord{cand.as<vsa_match>()}, stream,
-                            mums, &c))
-  {
-    return -100;
+    // sorter: (composite key, index) over just the bits in use; the pair
+    // list of the records
+    SortedPairs s;
+    DevBuf k1, i1;
+    if (s.alloc(ncand, 4, mums) || k1.alloc(ncand * 8) ||
+        i1.alloc(ncand * 4))
+    {
+      return -100;
+    }
+    k_mum_compositekeys<<<gridfor(ncand), VSA_BLOCK, 0, stream>>>(
+        cand.as<vsa_match>(), ncand, lenbits, k1.as<uint64_t>(),
+        i1.as<uint32_t>());
+    VSA_HIP(hipGetLastError());
+    if (sort_radix<uint32_t>(k1.as<uint64_t>(), i1.as<uint32_t>(), s, 0,
+                             lenbits + dbbits, stream) ||
+        mumfilter_tiles<true>(
+            s, s.pairs(lenbits, GatheredRecord{cand.as<vsa_match>()}), carry,
+            stream, mums, &c))
+    {
+      return -100;
+    }
   }
   *nmums = c.nmums;
   *sumlength = c.sumlength;
@@ -1718,13 +1712,6 @@ static int mumfilter_entry(void *device_candidates, uint64_t ncandidates,
   res->stats.candidates = ncandidates;
   res->stats.total_device_ms = tall.ms();
   res->stats.sumlength = sum;
-  // (the wide form does not sum the lengths)
-  if (sum == ~0ull &&
-      sumlengths(res->matches, nm, stream, &res->stats.sumlength) != 0)
-  {
-    vsa_result_free(res);
-    return -100;
-  }
   *result = res;
   return 0;
 }

@@ -3,45 +3,51 @@
 // device functions of esa_device.hpp and the host pipelines of esa_search.hip
 // launch them).
 //
-// One filter behind every sort.  A candidate is a key dbstart << lenbits |
-// (2^lenbits - 1 - length) and a value that travels with it; the key carries
-// all the rule looks at.  With the reference's running `dbright` = the largest
-// right end in front of a candidate (carry = its value in front of the list),
-// candidate i survives iff it is not covered (dbright < its right end) and no
-// other candidate with its dbstart is at least as long.  The keys arrive
-//   sorted by dbstart ALONE (one radix pass saved): the
+// One filter behind every sort, and one statement of its rule.  With the
+// reference's running `dbright` = the largest right end in front of a
+// candidate (carry = its value in front of the list), candidate i survives
+// iff it is not covered (dbright < its right end) and no other candidate with
+// its dbstart is at least as long.  The candidates arrive
+//   sorted by dbstart ALONE (packed keys; one radix pass saved): the
 //     reference's order inside a run of equal dbstarts is "longest first", and
 //     of such a run only the longest can survive, and only if no other member
 //     is as long (the others find dbright at or beyond their right end).  That
 //     is decidable without the order: earlier members of a survivor's own run
 //     are shorter than it, so they do not disturb the running maximum, and the
-//     run itself is looked at as a run.  Runs are short (two reads starting at
-//     the same position); a run longer than VSA_RUN_LIMIT raises bit 0 of
-//     *overflow and the caller sorts on all bits instead;
-//   or sorted on ALL bits (that second attempt; records, whose values are
-//     their indices): the longer members of the run are in front and in the
-//     running maximum already, and an equal one, if any, is the next key.
+//     run itself is looked at as a run -- vsa_mum_alone_in_run.  Runs are
+//     short (two reads starting at the same position); a run longer than
+//     VSA_RUN_LIMIT raises bit 0 of *overflow and the caller sorts on all bits
+//     instead;
+//   or sorted by dbstart and, inside a run, longest first (that second
+//     attempt; records): the longer members of the run are in front and in
+//     the running maximum already, and an equal one, if any, is the next
+//     candidate -- vsa_mum_twin_follows.
 // Either way the filter is five launches over tiles: a tile of VSA_FT_TILE
-// keys knows the maximum of its right ends without knowing anything else
-// (pass A), one workgroup turns the tile maxima into the running maximum in
-// front of each tile (S1), every tile then decides its candidates for good,
-// counts the survivors and sums their lengths (pass B), one workgroup turns
-// the counts into offsets (S2), and the survivors are written in order (pass
-// C) -- from the pair, or gathered from the caller's 32-byte records, which
-// are touched only there.  (Until round 3: rocPRIM max-scan, flags, rocPRIM
-// sum-scan, writer, reduce -- 0.3 ms for 11.6 M candidates, each pass paying
-// its launch and a look-back chain over thousands of workgroups.)
+// candidates knows the maximum of its right ends without knowing anything
+// else (pass A), one workgroup turns the tile maxima into the running maximum
+// in front of each tile (S1), every tile then decides its candidates for
+// good, counts the survivors and sums their lengths (pass B), one workgroup
+// turns the counts into offsets (S2), and the survivors are written in order
+// (pass C).  (Until round 3: rocPRIM max-scan, flags, rocPRIM sum-scan,
+// writer, reduce -- 0.3 ms for 11.6 M candidates, each pass paying its launch
+// and a look-back chain over thousands of workgroups.)
 //
-// The bucket path (candidate_sort.inc) does not come through these tiles
-// since round 12: k_cs_filter applies the rule of k_mumf_flags<false> to a
-// bucket where its sort left it in LDS -- the running maximum in front of a
-// bucket is what the scatter found reaching into it -- and k_mumf_scan<0>
-// turns its survivors per bucket into offsets as it does for tiles.  Whoever
-// changes the rule changes it there as well; tests/test_gpu_bucket_filter.py
-// and test_gpu_candidate_sort.py hold both to the oracle's list.
+// The tiles read the candidates through a view, of which there are two:
+//   PackedCands  a key dbstart << lenbits | (2^lenbits - 1 - length), which
+//                carries all the rule looks at, and a value that travels with
+//                it; a survivor is written from the pair (PairRecord) or
+//                gathered from the caller's 32-byte records (GatheredRecord),
+//                which are touched only there;
+//   RecordCands  32-byte records in the sorted order themselves, for lists
+//                whose dbstart and length do not fit into one key or that
+//                have 2^32 members and more (mumfilter_wide sorts them with
+//                the keys of k_mum_keys, at the end of this file).
 //
-// At the end of the file: the three kernels of the wide form, for records
-// whose dbstart and length do not fit into one key.
+// The bucket path (candidate_sort.inc) does not come through these tiles:
+// k_cs_filter calls vsa_mum_alone_in_run on a bucket where its sort left it
+// in LDS -- the running maximum in front of a bucket is what the scatter
+// found reaching into it -- and k_mumf_scan<0> turns its survivors per bucket
+// into offsets as it does for tiles.
 
 // right end of a candidate from its sort key
 struct KeyToRightEnd
@@ -58,59 +64,176 @@ struct KeyToRightEnd
 #define VSA_FT_ITEMS 4
 #define VSA_FT_TILE (VSA_BLOCK * VSA_FT_ITEMS)
 
+// ---- the rule
+
+// Candidates sorted by dbstart alone: is candidate i, of dbstart d and right
+// end e, the one longest member of its run of equal dbstarts?  keyat(j) = the
+// key of candidate j, of which this looks at j < n only.  Both walks end
+// after VSA_RUN_LIMIT steps at the latest, whatever the keys are, and then
+// raise bit 0 of *overflow (the answer is "no", and not to be used).
+template <typename KEYAT, typename IDX>
+__device__ __forceinline__ bool
+vsa_mum_alone_in_run(KEYAT keyat, unsigned int lenbits, IDX i, IDX n,
+                     uint64_t d, uint64_t e, unsigned int *overflow)
+{
+  const KeyToRightEnd rightend = {lenbits};
+  bool ok = true;
+  uint32_t steps = 0;
+  for (IDX j = i; j > 0 && (keyat(j - 1) >> lenbits) == d; j--)
+  {
+    if (rightend(keyat(j - 1)) >= e || ++steps > VSA_RUN_LIMIT)
+    {
+      ok = false;
+      break;
+    }
+  }
+  if (steps > VSA_RUN_LIMIT)
+  {
+    atomicOr(overflow, 1u);
+  }
+  steps = 0;
+  for (IDX j = i + 1; ok && j < n && (keyat(j) >> lenbits) == d; j++)
+  {
+    if (rightend(keyat(j)) >= e || ++steps > VSA_RUN_LIMIT)
+    {
+      ok = false;
+    }
+  }
+  if (steps > VSA_RUN_LIMIT)
+  {
+    atomicOr(overflow, 1u);
+  }
+  return ok;
+}
+
+// Candidates sorted by dbstart and, inside a run, longest first: does the
+// next candidate have the dbstart and the length of candidate i?
+template <typename CANDS>
+__device__ __forceinline__ bool
+vsa_mum_twin_follows(const CANDS &cands, uint64_t i, uint64_t n)
+{
+  return i + 1 < n && cands.twin(i, i + 1);
+}
+
+// ---- the views
+
+// What pass C makes of a survivor of packed keys.  From its pair -- VAL =
+// uint64_t: value = queryseq << 16 | querystart; uint32_t: value = query
+// number in the batch << valbits | querystart, queryseq = that number +
+// seqoffset:
+template <typename V>
+struct PairRecord
+{
+  using VAL = V;
+  unsigned int lenbits, valbits;
+  uint64_t seqoffset;
+  __device__ void operator()(uint64_t kkey, uint64_t v, vsa_match *dst) const
+  {
+    const uint64_t lenmask = (1ull << lenbits) - 1;
+    vsa_match m;
+    m.length = lenmask - (kkey & lenmask);
+    m.dbstart = kkey >> lenbits;
+    if (sizeof(VAL) == 4)
+    {
+      m.queryseq = (v >> valbits) + seqoffset;
+      m.querystart = v & ((1ull << valbits) - 1);
+    } else
+    {
+      m.queryseq = v >> 16;
+      m.querystart = v & 0xFFFFu;
+    }
+    *dst = m;
+  }
+};
+
+__device__ __forceinline__ void vsa_copy_record(const vsa_match *from,
+                                                vsa_match *dst)
+{
+  const uint4 *src = reinterpret_cast<const uint4 *>(from);
+  const uint4 lo = src[0], hi = src[1];
+  reinterpret_cast<uint4 *>(dst)[0] = lo;
+  reinterpret_cast<uint4 *>(dst)[1] = hi;
+}
+
+// ... or the caller's record whose index the value is
+struct GatheredRecord
+{
+  using VAL = uint32_t;
+  const vsa_match *cand;
+  __device__ void operator()(uint64_t, uint64_t v, vsa_match *dst) const
+  {
+    vsa_copy_record(cand + v, dst);
+  }
+};
+
+// (Rule: the part of a view that passes A and B read -- one instance of
+// their kernels for all writers)
+struct PackedKeys
+{
+  const uint64_t *__restrict__ key;
+  unsigned int lenbits;
+  __device__ uint64_t dbstart(uint64_t i) const { return key[i] >> lenbits; }
+  __device__ uint64_t length(uint64_t i) const
+  {
+    const uint64_t lenmask = (1ull << lenbits) - 1;
+    return lenmask - (key[i] & lenmask);
+  }
+  // (same dbstart and same length = same key)
+  __device__ bool twin(uint64_t i, uint64_t j) const
+  {
+    return key[i] == key[j];
+  }
+};
+
+template <typename WRITER>
+struct PackedCands : PackedKeys
+{
+  using Rule = PackedKeys;
+  const typename WRITER::VAL *__restrict__ value;
+  WRITER rec;
+  __device__ void write(uint64_t i, vsa_match *dst) const
+  {
+    rec(key[i], value[i], dst);
+  }
+};
+
+struct RecordCands
+{
+  using Rule = RecordCands;
+  const vsa_match *__restrict__ rec;
+  __device__ uint64_t dbstart(uint64_t i) const { return rec[i].dbstart; }
+  __device__ uint64_t length(uint64_t i) const { return rec[i].length; }
+  __device__ bool twin(uint64_t i, uint64_t j) const
+  {
+    return rec[i].dbstart == rec[j].dbstart && rec[i].length == rec[j].length;
+  }
+  __device__ void write(uint64_t i, vsa_match *dst) const
+  {
+    vsa_copy_record(rec + i, dst);
+  }
+};
+
+// ---- the tiles
+
 // workgroup-wide exclusive scan of one value per thread; total = sum / max of
-// all.  OP: 0 sum, 1 max.  sh: VSA_BLOCK / 64 + 1 words of LDS.
+// all.  OP: 0 sum, 1 max.  sh: VSA_BLOCK / 64 words of LDS.
 template <int OP>
 __device__ __forceinline__ uint64_t vsa_block_exscan(uint64_t v, uint64_t *sh,
                                                      uint64_t &total)
 {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint64_t o = vsa_shfl64(incl, (int) (lane >= (uint32_t) d ? lane - d : lane));
-    if (lane >= (uint32_t) d)
-    {
-      incl = OP == 0 ? incl + o : (o > incl ? o : incl);
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < VSA_BLOCK / 64; w++)
-  {
-    const uint64_t x = sh[w];
-    if (w < wave)
-    {
-      before = OP == 0 ? before + x : (x > before ? x : before);
-    }
-    all = OP == 0 ? all + x : (x > all ? x : all);
-  }
-  __syncthreads();
-  total = all;
-  // exclusive: what the lanes in front of this one hold
-  const uint64_t prev = vsa_shfl64(incl, (int) (lane > 0 ? lane - 1 : 0));
-  uint64_t mine = lane > 0 ? prev : 0;
-  mine = OP == 0 ? mine + before : (before > mine ? before : mine);
-  return mine;
+  return vsa_block_exclusive_scan<OP, VSA_BLOCK>(v, sh, total);
 }
 
 // pass A: the largest right end of every tile
+template <typename CANDS>
 __global__ void __launch_bounds__(VSA_BLOCK)
-k_mumf_tilemax(const uint64_t *__restrict__ key, uint64_t n,
-               unsigned int lenbits, uint64_t *__restrict__ tilemax)
+k_mumf_tilemax(CANDS cands, uint64_t n, uint64_t *__restrict__ tilemax)
 {
   if (vsa_bid() * VSA_FT_TILE >= n) // (a launch folded into two dimensions)
   {
     return;
   }
   __shared__ uint64_t sh[VSA_BLOCK / 64 + 1];
-  const KeyToRightEnd rightend = {lenbits};
   const uint64_t i0 = (vsa_bid() * VSA_BLOCK + threadIdx.x) * VSA_FT_ITEMS;
   uint64_t m = 0;
 #pragma unroll
@@ -118,7 +241,7 @@ k_mumf_tilemax(const uint64_t *__restrict__ key, uint64_t n,
   {
     if (i0 + k < n)
     {
-      const uint64_t e = rightend(key[i0 + k]);
+      const uint64_t e = cands.dbstart(i0 + k) + cands.length(i0 + k) - 1;
       m = e > m ? e : m;
     }
   }
@@ -180,14 +303,14 @@ k_mumf_scan(const uint64_t *__restrict__ in, uint64_t count, uint64_t start,
   }
 }
 
-// pass B: keep flags (the running maximum from the tile's carry and the keys
-// in front inside the tile; SORTED: keys sorted on all bits, else on dbstart
-// alone, see above), the number of survivors and the sum of their lengths per
-// tile.  The SORTED form does not touch *overflow.
-template <bool SORTED>
+// pass B: keep flags (the running maximum from the tile's carry and the
+// candidates in front inside the tile; SORTED: longest first inside a run,
+// else any order there and packed keys, see above), the number of survivors
+// and the sum of their lengths per tile.  The SORTED form does not touch
+// *overflow.
+template <bool SORTED, typename CANDS>
 __global__ void __launch_bounds__(VSA_BLOCK)
-k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
-             unsigned int lenbits, const uint64_t *__restrict__ tilecarry,
+k_mumf_flags(CANDS cands, uint64_t n, const uint64_t *__restrict__ tilecarry,
              uint8_t *__restrict__ keep, uint64_t *__restrict__ tilecount,
              uint64_t *__restrict__ tilelen,
              unsigned int *__restrict__ overflow)
@@ -197,14 +320,14 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
     return;
   }
   __shared__ uint64_t sh[VSA_BLOCK / 64 + 1];
-  const KeyToRightEnd rightend = {lenbits};
   const uint64_t i0 = (vsa_bid() * VSA_BLOCK + threadIdx.x) * VSA_FT_ITEMS;
-  uint64_t kk[VSA_FT_ITEMS], e[VSA_FT_ITEMS], m = 0;
+  uint64_t d[VSA_FT_ITEMS], l[VSA_FT_ITEMS], e[VSA_FT_ITEMS], m = 0;
 #pragma unroll
   for (int k = 0; k < VSA_FT_ITEMS; k++)
   {
-    kk[k] = i0 + k < n ? key[i0 + k] : 0;
-    e[k] = i0 + k < n ? rightend(kk[k]) : 0;
+    d[k] = i0 + k < n ? cands.dbstart(i0 + k) : 0;
+    l[k] = i0 + k < n ? cands.length(i0 + k) : 0;
+    e[k] = i0 + k < n ? d[k] + l[k] - 1 : 0;
     m = e[k] > m ? e[k] : m;
   }
   uint64_t total;
@@ -213,44 +336,19 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
   run = carry > run ? carry : run;
   uint32_t kept = 0, bits = 0;
   uint64_t len = 0;
-  const uint64_t lenmask = (1ull << lenbits) - 1;
 #pragma unroll
   for (int k = 0; k < VSA_FT_ITEMS; k++)
   {
     const uint64_t i = i0 + k;
     bool ok = i < n && run < e[k];
-    if (SORTED)
+    if constexpr (SORTED)
     {
-      // (same dbstart and same length = same key)
-      ok = ok && !(i + 1 < n && key[i + 1] == kk[k]);
+      ok = ok && !vsa_mum_twin_follows(cands, i, n);
     } else if (ok)
     {
-      const uint64_t d = kk[k] >> lenbits;
-      uint32_t steps = 0;
-      for (uint64_t j = i; j > 0 && (key[j - 1] >> lenbits) == d; j--)
-      {
-        if (rightend(key[j - 1]) >= e[k] || ++steps > VSA_RUN_LIMIT)
-        {
-          ok = false;
-          break;
-        }
-      }
-      if (steps > VSA_RUN_LIMIT)
-      {
-        atomicOr(overflow, 1u);
-      }
-      steps = 0;
-      for (uint64_t j = i + 1; ok && j < n && (key[j] >> lenbits) == d; j++)
-      {
-        if (rightend(key[j]) >= e[k] || ++steps > VSA_RUN_LIMIT)
-        {
-          ok = false;
-        }
-      }
-      if (steps > VSA_RUN_LIMIT)
-      {
-        atomicOr(overflow, 1u);
-      }
+      ok = vsa_mum_alone_in_run(
+          [&](uint64_t j) { return cands.key[j]; }, cands.lenbits, i, n, d[k],
+          e[k], overflow);
     }
     if (i < n)
     {
@@ -258,7 +356,7 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
     }
     bits |= ok ? 1u << (8 * k) : 0u;
     kept += ok ? 1u : 0u;
-    len += ok ? lenmask - (kk[k] & lenmask) : 0;
+    len += ok ? l[k] : 0;
   }
   // (n is padded to whole words of flags by the caller's allocation)
   *reinterpret_cast<uint32_t *>(keep + i0) = bits;
@@ -272,60 +370,15 @@ k_mumf_flags(const uint64_t *__restrict__ key, uint64_t n,
   }
 }
 
-// What pass C makes of a survivor.  From its pair -- VAL = uint64_t: value =
-// queryseq << 16 | querystart; uint32_t: value = query number in the batch <<
-// valbits | querystart, queryseq = that number + seqoffset:
-template <typename V>
-struct PairRecord
-{
-  using VAL = V;
-  unsigned int lenbits, valbits;
-  uint64_t seqoffset;
-  __device__ void operator()(uint64_t kkey, uint64_t v, vsa_match *dst) const
-  {
-    const uint64_t lenmask = (1ull << lenbits) - 1;
-    vsa_match m;
-    m.length = lenmask - (kkey & lenmask);
-    m.dbstart = kkey >> lenbits;
-    if (sizeof(VAL) == 4)
-    {
-      m.queryseq = (v >> valbits) + seqoffset;
-      m.querystart = v & ((1ull << valbits) - 1);
-    } else
-    {
-      m.queryseq = v >> 16;
-      m.querystart = v & 0xFFFFu;
-    }
-    *dst = m;
-  }
-};
-
-// ... or the caller's record whose index the value is
-struct GatheredRecord
-{
-  using VAL = uint32_t;
-  const vsa_match *cand;
-  __device__ void operator()(uint64_t, uint64_t v, vsa_match *dst) const
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(cand + v);
-    const uint4 lo = src[0], hi = src[1];
-    reinterpret_cast<uint4 *>(dst)[0] = lo;
-    reinterpret_cast<uint4 *>(dst)[1] = hi;
-  }
-};
-
 // pass C: the survivors as records, in order.  A tile is walked in rows of
 // VSA_BLOCK consecutive candidates, one per thread, so that the records of
 // neighbouring lanes lie next to each other in the output (four consecutive
 // candidates per thread wrote 32 bytes per lane 128 bytes apart: 188 us
 // instead of 100 for the 11 M records of the headline batch)
-template <typename WRITER>
+template <typename CANDS>
 __global__ void __launch_bounds__(VSA_BLOCK)
-k_mumf_write(const uint64_t *__restrict__ key,
-             const typename WRITER::VAL *__restrict__ value,
-             const uint8_t *__restrict__ keep, uint64_t n,
-             const uint64_t *__restrict__ tileoff, WRITER write,
-             vsa_match *__restrict__ out)
+k_mumf_write(CANDS cands, const uint8_t *__restrict__ keep, uint64_t n,
+             const uint64_t *__restrict__ tileoff, vsa_match *__restrict__ out)
 {
   if (vsa_bid() * VSA_FT_TILE >= n) // (a launch folded into two dimensions)
   {
@@ -344,13 +397,14 @@ k_mumf_write(const uint64_t *__restrict__ key,
     base += total;
     if (k)
     {
-      write(key[i], value[i], out + slot);
+      cands.write(i, out + slot);
     }
   }
 }
 
-// ---- wide records: dbstart and length as two sort keys, the filter on the
-// sorted records themselves (mumfilter_wide)
+// ---- wide records: dbstart and length as the keys of two stable sorts
+// (mumfilter_wide); the sorted records then go through the tiles as
+// RecordCands
 
 __global__ void __launch_bounds__(VSA_BLOCK)
 k_mum_keys(const vsa_match *__restrict__ cand, uint64_t n,
@@ -362,43 +416,4 @@ k_mum_keys(const vsa_match *__restrict__ cand, uint64_t n,
     keylen[i] = ~cand[i].length; // decreasing length
     keydb[i] = cand[i].dbstart;
   }
-}
-
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_rightends(const vsa_match *__restrict__ cand, uint64_t n,
-                uint64_t *__restrict__ rightend)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i < n)
-  {
-    rightend[i] = cand[i].dbstart + cand[i].length - 1;
-  }
-}
-
-// dbright[i] = max(0, rightend[0..i)) is what the reference's running
-// variable holds when it looks at candidate i.  Candidate i survives iff it
-// is not covered (dbright < rightend) and its successor does not end at the
-// same position with the same start.
-__global__ void __launch_bounds__(VSA_BLOCK)
-k_mum_flags(const vsa_match *__restrict__ cand,
-            const uint64_t *__restrict__ rightend,
-            const uint64_t *__restrict__ dbright, uint64_t n,
-            uint8_t *__restrict__ keep)
-{
-  const uint64_t i = vsa_bid() * VSA_BLOCK + threadIdx.x;
-  if (i >= n)
-  {
-    return;
-  }
-  bool k = dbright[i] < rightend[i];
-  if (k && i + 1 < n)
-  {
-    // dbright[i+1] = rightend[i] here
-    if (rightend[i + 1] == rightend[i] &&
-        cand[i + 1].dbstart == cand[i].dbstart)
-    {
-      k = false;
-    }
-  }
-  keep[i] = k ? 1 : 0;
 }

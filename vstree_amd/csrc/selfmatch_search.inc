@@ -111,33 +111,13 @@ k_lcpsel_write(const uint8_t *__restrict__ lcp, uint64_t n, uint32_t lmin,
   {
     return;
   }
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t first =
       (vsa_bid() * VSA_BLOCK + threadIdx.x) * VSA_SEL_PER;
   uint32_t mask = lcpsel_mask<SUPERMAX>(lcp, n, first, lmin);
-  const uint32_t c = (uint32_t) __builtin_popcount(mask);
-  uint32_t incl = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t) d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    wavesum[wave] = incl;
-  }
-  __syncthreads();
-  uint32_t wavebase = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < VSA_BLOCK / 64; w++)
-  {
-    wavebase += (w < wave) ? wavesum[w] : 0;
-  }
-  uint64_t slot = blockoffset[vsa_bid()] + wavebase + incl - c;
+  uint32_t total;
+  uint64_t slot = blockoffset[vsa_bid()] +
+                  vsa_block_exclusive_scan<0, VSA_BLOCK>(
+                      (uint32_t) __builtin_popcount(mask), wavesum, total);
   while (mask != 0)
   {
     const uint32_t k = (uint32_t) __builtin_ctz(mask);

@@ -26,50 +26,6 @@ static_assert(TC_TILE == VSA_SELECT_TILE, "the header names the tile");
 namespace
 {
 
-__device__ __forceinline__ uint32_t tc_shfl(uint32_t v, int src)
-{
-  return __shfl(v, src, 64);
-}
-
-__device__ __forceinline__ uint64_t tc_shfl(uint64_t v, int src)
-{
-  return vsa_shfl64(v, src);
-}
-
-// exclusive sum of one value per thread of a workgroup of TC_BLOCK threads
-// (T: uint32_t or uint64_t); sh: TC_BLOCK / 64 words of LDS
-template <typename T>
-__device__ __forceinline__ T tc_block_exsum(T v, T *sh, T &total)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  T incl = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1)
-  {
-    const T o = tc_shfl(incl, (int) (lane >= d ? lane - d : lane));
-    if (lane >= d)
-    {
-      incl += o;
-    }
-  }
-  if (lane == 63)
-  {
-    sh[wave] = incl;
-  }
-  __syncthreads();
-  T before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < TC_BLOCK / 64; w++)
-  {
-    const T x = sh[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  __syncthreads();
-  total = all;
-  return before + incl - v;
-}
-
 template <int NE, int NC, class F>
 __global__ void __launch_bounds__(TC_BLOCK)
 k_tc_count(F f, uint64_t n, uint64_t *__restrict__ tilecount, uint64_t nt,
@@ -106,7 +62,7 @@ k_tc_count(F f, uint64_t n, uint64_t *__restrict__ tilecount, uint64_t nt,
   for (int q = 0; q < NC; q++)
   {
     uint32_t total;
-    (void) tc_block_exsum(c[q], sh, total);
+    (void) vsa_block_exclusive_scan<0, TC_BLOCK>(c[q], sh, total);
     if (threadIdx.x == 0)
     {
       if (q < NE)
@@ -156,7 +112,8 @@ k_tc_emit(F f, uint64_t n, const uint64_t *__restrict__ tileoffset,
   for (int q = 0; q < NE; q++)
   {
     uint32_t total;
-    const uint32_t ex = tc_block_exsum(c[q], sh, total);
+    const uint32_t ex =
+        vsa_block_exclusive_scan<0, TC_BLOCK>(c[q], sh, total);
     o[q] = tileoffset[(uint64_t) q * (nt + 1) + tile] + ex;
   }
 #pragma unroll
