@@ -1845,7 +1845,45 @@ int vsa_extend_hamming_host(const vsa_sinkparams *layout, const uint8_t *text,
 uint64_t vsa_extend_seedlength(uint64_t leastlength, uint64_t maxdist,
                                uint64_t seedlength);
 
+/* ---- degenerate matches: vmatch -l L -e K [-seedlength S] [-p] [-q Q] IDX ---
+   The same seeds extended over at most K edit operations (editextend,
+   kurtz/extendED.c:78-355; callgenericextend picks it or hammingextend by one
+   flag, Vmengine/extendgen.c:24-87).  The two instances of such a match
+   differ in length, so the record of a match carries both, beside the
+   distance (which editextend stores as it is, not negated):
+     bits 0-47  length1
+     bits 48-55 the distance
+     bits 56-63 length2 - length1 as a signed byte (its absolute value is at
+                most the distance plus two trimmed separators, so the record
+                carries distances up to VSA_EDIST_MAXDISTANCE)
+   dbstart = position1; queryseq, querystart = the query sequence and the
+   position in it, or (self layout) queryseq = position2.  The entries are
+   declared in vstree_amd_edist.h, which this header includes. */
+#define VSA_EDIST_MAXDISTANCE 125u
+#define VSA_EDIST_LENGTH1(lengthfield) \
+  ((uint64_t) (lengthfield) & (((uint64_t) 1 << 48) - 1))
+#define VSA_EDIST_DISTANCE(lengthfield) \
+  (((uint64_t) (lengthfield) >> 48) & 0xFFu)
+#define VSA_EDIST_LENGTH2(lengthfield) \
+  ((uint64_t) ((int64_t) VSA_EDIST_LENGTH1(lengthfield) + \
+               (int64_t) (int8_t) ((uint64_t) (lengthfield) >> 56)))
+#define VSA_EDIST_PACK(length1, length2, distance) \
+  ((uint64_t) (length1) | (uint64_t) (distance) << 48 | \
+   (((uint64_t) (length2) - (uint64_t) (length1)) & 0xFFu) << 56)
+
+/* layouts of such lists for the sink: the lines of vmatch -l L -e K -q Q IDX
+   (with palindromic: of its -p pass) and of vmatch -l L -e K IDX, byte for
+   byte; the post-processing handles answer VSA_NOT_COVERED for them as for
+   the two Hamming kinds */
+#define VSA_SINK_QUERY_EDIST 10
+#define VSA_SINK_SELF_EDIST  11
+
+/* the cap of the device path: 2 K + 1 diagonals are the lanes of one
+   wavefront */
+#define VSA_EXTEND_EDIST_MAXDIST 31u
+
 #ifdef __cplusplus
 }
 #endif
+#include "vstree_amd_edist.h"
 #endif

@@ -438,13 +438,21 @@ def _load():
                                         U64, U64, U64, I, V, U64,
                                         C.POINTER(U64)]),
     }
-    for name, (res, args) in sig.items():
+    # the entries of include/vstree_amd_edist.h
+    edist = {
+        "vsa_extend_edist_maxdist": (U32, []),
+        "vsa_extend_edist": sig["vsa_extend_hamming"],
+        "vsa_findquerymatches_edist": sig["vsa_findquerymatches_hamming"],
+        "vsa_findselfmatches_edist": sig["vsa_findselfmatches_hamming"],
+        "vsa_extend_edist_host": sig["vsa_extend_hamming_host"],
+    }
+    for name, (res, args) in list(sig.items()) + list(edist.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    return lib, sorted(sig)
+    return lib, sorted(sig), sorted(edist)
 
 
-lib, ABI_SYMBOLS = _load()
+lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS = _load()
 
 
 def messagespace():
@@ -2100,6 +2108,93 @@ def extend_hamming_host(text, seeds, leastlength, maxdist, seedlength=0,
     out = np.zeros(len(seeds), MATCH_DTYPE)
     n = C.c_uint64()
     _check(lib.vsa_extend_hamming_host(
+        C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds), len(seeds),
+        int(leastlength), int(maxdist), int(seedlength), int(threads),
+        _ptr(out), len(out), C.byref(n)))
+    return out[:n.value]
+
+
+# ---- degenerate matches: vmatch -l L -e K [-seedlength S] [-p] [-q Q] IDX ----
+# (include/vstree_amd_edist.h; the record: length1 in bits 0-47 of the length,
+# the distance in bits 48-55, length2 - length1 as a signed byte above)
+
+SINK_QUERY_EDIST, SINK_SELF_EDIST = 10, 11
+EDIST_MAXDISTANCE = 125
+EXTEND_EDIST_MAXDIST = int(lib.vsa_extend_edist_maxdist())
+
+
+def edist_lengths1(matches):
+    return matches["length"] & np.uint64((1 << 48) - 1)
+
+
+def edist_distances(matches):
+    return (matches["length"] >> np.uint64(48)) & np.uint64(0xFF)
+
+
+def edist_lengths2(matches):
+    diff = (matches["length"] >> np.uint64(56)).astype(np.uint8)
+    return (edist_lengths1(matches).astype(np.int64) +
+            diff.astype(np.int8).astype(np.int64)).astype(np.uint64)
+
+
+def edist_pack(length1, length2, distance):
+    length1 = np.asarray(length1, np.uint64)
+    diff = (np.asarray(length2, np.uint64) - length1) & np.uint64(0xFF)
+    return (length1 | np.asarray(distance, np.uint64) << np.uint64(48) |
+            diff << np.uint64(56))
+
+
+def extend_edist(index, queries, seeds, leastlength, maxdist, seedlength=0,
+                 palindromic=False):
+    """editextend (kurtz/extendED.c:78) for every seed of a Result; arguments
+    as for extend_hamming"""
+    p = SinkParams()
+    p.kind = SINK_SELF if queries is None else SINK_QUERY
+    h = C.c_void_p()
+    _check(lib.vsa_extend_edist(index._h,
+                                None if queries is None else queries._h,
+                                seeds._h, C.byref(p), int(bool(palindromic)),
+                                int(leastlength), int(maxdist),
+                                int(seedlength), C.byref(h)))
+    return Result(h)
+
+
+def findquerymatches_edist(index, queries, leastlength, maxdist,
+                           seedlength=0, palindromic=False):
+    """vmatch -l L -e K [-seedlength S] [-p] -q Q IDX"""
+    h = C.c_void_p()
+    _check(lib.vsa_findquerymatches_edist(index._h, queries._h,
+                                          int(leastlength), int(maxdist),
+                                          int(seedlength),
+                                          int(bool(palindromic)),
+                                          C.byref(h)))
+    return Result(h)
+
+
+def findselfmatches_edist(index, leastlength, maxdist, seedlength=0):
+    """vmatch -l L -e K [-seedlength S] IDX"""
+    h = C.c_void_p()
+    _check(lib.vsa_findselfmatches_edist(index._h, int(leastlength),
+                                         int(maxdist), int(seedlength),
+                                         C.byref(h)))
+    return Result(h)
+
+
+def extend_edist_host(text, seeds, leastlength, maxdist, seedlength=0,
+                      queries=None, numofchars=4, threads=0):
+    """the same extension on the host, any distance bound the record carries;
+    arguments as for extend_hamming_host"""
+    text = np.ascontiguousarray(text, np.uint8)
+    seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
+    p, keep = sink_params(SINK_SELF if queries is None else SINK_QUERY,
+                          len(text), (), numofchars=numofchars,
+                          querystart=None if queries is None else queries[1],
+                          querylength=None if queries is None else queries[2])
+    qsym = None if queries is None else np.ascontiguousarray(queries[0],
+                                                             np.uint8)
+    out = np.zeros(len(seeds), MATCH_DTYPE)
+    n = C.c_uint64()
+    _check(lib.vsa_extend_edist_host(
         C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds), len(seeds),
         int(leastlength), int(maxdist), int(seedlength), int(threads),
         _ptr(out), len(out), C.byref(n)))

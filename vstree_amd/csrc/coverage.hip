@@ -759,8 +759,8 @@ extern "C" int vsa_coverage_mark(vsa_coverage *c, const vsa_result *r,
   if (r->extended)
   {
     VSA_ERROR("vsa_coverage_mark: lists of extended seeds "
-              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
-              "covered");
+              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING, "
+              "VSA_SINK_QUERY_EDIST, VSA_SINK_SELF_EDIST) are not covered");
     return VSA_NOT_COVERED;
   }
   if (p->selfpalindromic)

@@ -319,38 +319,8 @@ k_ext_choose(ExtParams p, vsa_selrules ev, vsa_match *__restrict__ out,
   }
 }
 
-// the kept records, in order
-struct KeptRecords
-{
-  typedef NoPayload Payload;
-  const uint8_t *keep;
-  const vsa_match *in;
-  vsa_match *out;
-
-  __device__ int cls(uint64_t i, Payload &) const
-  {
-    return keep[i] != 0 ? 0 : -1;
-  }
-  __device__ void put(int, uint64_t rank, uint64_t i, const Payload &) const
-  {
-    out[rank] = in[i];
-  }
-};
-
-// VSA_EXTEND_STAGE: the symbols a lane looks at before it hands a side over
-uint32_t lanebudget()
-{
-  const char *e = getenv("VSA_EXTEND_STAGE");
-  if (e != nullptr && strcmp(e, "lane") == 0)
-  {
-    return 0xFFFFFFFFu;
-  }
-  if (e != nullptr && strcmp(e, "long") == 0)
-  {
-    return 0;
-  }
-  return VSA_EXTEND_LANE_BUDGET;
-}
+// lanebudget() of VSA_EXTEND_STAGE and the compaction functor KeptRecords
+#include "extend_shared.hpp"
 
 // what every entry refuses before anything is run or kept
 int checkbounds(const char *who, const vsa_index *index,

@@ -123,10 +123,13 @@ static inline int vsa_layout_view(const vsa_sinkparams *layout,
                     "batch (VSA_SINK_TRANSLATED) are not covered", who);
   }
   if (layout->kind == VSA_SINK_QUERY_HAMMING ||
-      layout->kind == VSA_SINK_SELF_HAMMING)
+      layout->kind == VSA_SINK_SELF_HAMMING ||
+      layout->kind == VSA_SINK_QUERY_EDIST ||
+      layout->kind == VSA_SINK_SELF_EDIST)
   {
     return vsa_fail(VSA_NOT_COVERED, "%s: lists of extended seeds "
-                    "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
+                    "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING, "
+                    "VSA_SINK_QUERY_EDIST, VSA_SINK_SELF_EDIST) are not "
                     "covered", who);
   }
   if (layout->kind < VSA_SINK_COMPLETE ||

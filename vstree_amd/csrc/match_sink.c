@@ -45,7 +45,8 @@ static const double averagequot[] = {
     1.66e+05, 3.58e+05, 7.44e+05, 1.52e+06, 3.20e+06, 6.40e+06, 1.31e+07};
 
 #define ISSELF(kind) \
-  ((kind) == VSA_SINK_SELF || (kind) == VSA_SINK_SELF_HAMMING)
+  ((kind) == VSA_SINK_SELF || (kind) == VSA_SINK_SELF_HAMMING || \
+   (kind) == VSA_SINK_SELF_EDIST)
 
 typedef vsa_evalues Evalues; /* evalues.h: shared with select_host.c */
 
@@ -428,14 +429,19 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   /* extended seeds: the distance travels in the top bits of the length */
   const int isextended = s->p.kind == VSA_SINK_QUERY_HAMMING ||
                          s->p.kind == VSA_SINK_SELF_HAMMING;
+  /* ... by edit distance: both lengths and the distance as it is
+     (editextend stores dist, kurtz/extendED.c:321) */
+  const int isedist = s->p.kind == VSA_SINK_QUERY_EDIST ||
+                      s->p.kind == VSA_SINK_SELF_EDIST;
   const int iscomplete = s->p.kind == VSA_SINK_COMPLETE ||
                          s->p.kind == VSA_SINK_APPROX_EDIST ||
                          s->p.kind == VSA_SINK_APPROX_HAMMING ||
                          s->p.kind == VSA_SINK_TRANSLATED_COMPLETE;
 
   position1 = m->dbstart;
-  length1 =
-      isextended ? VSA_HAMMING_LENGTH(m->length) : m->length;
+  length1 = isextended ? VSA_HAMMING_LENGTH(m->length)
+            : isedist  ? VSA_EDIST_LENGTH1(m->length)
+                       : m->length;
   seqinfo(s, position1, &seqnum1, &start1, &len1seq);
   if (isquery)
   {
@@ -461,6 +467,11 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
       length2 = dna.length;
       relpos2 = dna.querystart;
       distance = 0;
+    } else if (isedist)
+    {
+      length2 = VSA_EDIST_LENGTH2(m->length);
+      relpos2 = m->querystart;
+      distance = (int64_t) VSA_EDIST_DISTANCE(m->length);
     } else if (s->p.kind == VSA_SINK_QUERY || isextended)
     {
       /* hammingextend stores the negative (kurtz/extendHD.c:345) */
@@ -493,8 +504,10 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   {
     /* self match: (length, start1, start2), Vmengine/fself.c:95-125 */
     uint64_t start2, len2seq;
-    length2 = length1;
-    distance = isextended ? -(int64_t) VSA_HAMMING_DISTANCE(m->length) : 0;
+    length2 = isedist ? VSA_EDIST_LENGTH2(m->length) : length1;
+    distance = isextended ? -(int64_t) VSA_HAMMING_DISTANCE(m->length)
+               : isedist  ? (int64_t) VSA_EDIST_DISTANCE(m->length)
+                          : 0;
     seqinfo(s, m->queryseq, &seqnum2, &start2, &len2seq);
     relpos2 = m->queryseq - start2;
     position2 = m->queryseq;
@@ -657,6 +670,16 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
       if (VSA_HAMMING_DISTANCE(matches[i].length) > maxd)
       {
         maxd = VSA_HAMMING_DISTANCE(matches[i].length);
+      }
+    }
+  }
+  if (s->p.kind == VSA_SINK_QUERY_EDIST || s->p.kind == VSA_SINK_SELF_EDIST)
+  {
+    for (i = 0; i < n; i++)
+    {
+      if (VSA_EDIST_DISTANCE(matches[i].length) > maxd)
+      {
+        maxd = VSA_EDIST_DISTANCE(matches[i].length);
       }
     }
   }

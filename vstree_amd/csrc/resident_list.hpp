@@ -117,7 +117,8 @@ int gate(const char *who, const char *noun, const char *doing, const H *c,
   if (r->extended)
   {
     VSA_ERROR("%s: lists of extended seeds (VSA_SINK_QUERY_HAMMING, "
-              "VSA_SINK_SELF_HAMMING) are not covered", who);
+              "VSA_SINK_SELF_HAMMING, VSA_SINK_QUERY_EDIST, "
+              "VSA_SINK_SELF_EDIST) are not covered", who);
     return VSA_NOT_COVERED;
   }
   const char *refusal = form();

@@ -729,8 +729,8 @@ extern "C" int vsa_translated_convert(const vsa_result *result,
   if (result->extended)
   {
     VSA_ERROR("vsa_translated_convert: lists of extended seeds "
-              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING) are not "
-              "covered");
+              "(VSA_SINK_QUERY_HAMMING, VSA_SINK_SELF_HAMMING, "
+              "VSA_SINK_QUERY_EDIST, VSA_SINK_SELF_EDIST) are not covered");
     return VSA_NOT_COVERED;
   }
   if (protein->dnalength == nullptr)
