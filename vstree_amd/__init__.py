@@ -2055,63 +2055,77 @@ def extend_seedlength(leastlength, maxdist, seedlength=0):
                                          int(seedlength)))
 
 
-def extend_hamming(index, queries, seeds, leastlength, maxdist, seedlength=0,
-                   palindromic=False):
-    """hammingextend (kurtz/extendHD.c:166) for every seed of a Result:
+def _extension(kind, docs):
+    """the four wrappers of one kind of extension of exact seeds, `kind` as in
+    the names of its entries: (extend_KIND, findquerymatches_KIND,
+    findselfmatches_KIND, extend_KIND_host) with the docstrings `docs`"""
+    c_extend = getattr(lib, "vsa_extend_" + kind)
+    c_query = getattr(lib, "vsa_findquerymatches_" + kind)
+    c_self = getattr(lib, "vsa_findselfmatches_" + kind)
+    c_host = getattr(lib, "vsa_extend_%s_host" % kind)
+
+    def extend(index, queries, seeds, leastlength, maxdist, seedlength=0,
+               palindromic=False):
+        p = SinkParams()
+        p.kind = SINK_SELF if queries is None else SINK_QUERY
+        h = C.c_void_p()
+        _check(c_extend(index._h, None if queries is None else queries._h,
+                        seeds._h, C.byref(p), int(bool(palindromic)),
+                        int(leastlength), int(maxdist), int(seedlength),
+                        C.byref(h)))
+        return Result(h)
+
+    def findquerymatches(index, queries, leastlength, maxdist, seedlength=0,
+                         palindromic=False):
+        h = C.c_void_p()
+        _check(c_query(index._h, queries._h, int(leastlength), int(maxdist),
+                       int(seedlength), int(bool(palindromic)), C.byref(h)))
+        return Result(h)
+
+    def findselfmatches(index, leastlength, maxdist, seedlength=0):
+        h = C.c_void_p()
+        _check(c_self(index._h, int(leastlength), int(maxdist),
+                      int(seedlength), C.byref(h)))
+        return Result(h)
+
+    def extend_host(text, seeds, leastlength, maxdist, seedlength=0,
+                    queries=None, numofchars=4, threads=0):
+        text = np.ascontiguousarray(text, np.uint8)
+        seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
+        p, keep = sink_params(
+            SINK_SELF if queries is None else SINK_QUERY, len(text), (),
+            numofchars=numofchars,
+            querystart=None if queries is None else queries[1],
+            querylength=None if queries is None else queries[2])
+        qsym = None if queries is None else np.ascontiguousarray(queries[0],
+                                                                 np.uint8)
+        out = np.zeros(len(seeds), MATCH_DTYPE)
+        n = C.c_uint64()
+        _check(c_host(C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds),
+                      len(seeds), int(leastlength), int(maxdist),
+                      int(seedlength), int(threads), _ptr(out), len(out),
+                      C.byref(n)))
+        return out[:n.value]
+
+    made = (extend, findquerymatches, findselfmatches, extend_host)
+    for fn, name, doc in zip(made, ("extend_%s", "findquerymatches_%s",
+                                    "findselfmatches_%s", "extend_%s_host"),
+                             docs):
+        fn.__name__ = fn.__qualname__ = name % kind
+        fn.__doc__ = doc
+    return made
+
+
+(extend_hamming, findquerymatches_hamming, findselfmatches_hamming,
+ extend_hamming_host) = _extension("hamming", (
+     """hammingextend (kurtz/extendHD.c:166) for every seed of a Result:
     queries = the forward batch of MEM seeds (palindromic: found on its
-    reverse complement), or None for the seeds of findmaximalrepeats"""
-    p = SinkParams()
-    p.kind = SINK_SELF if queries is None else SINK_QUERY
-    h = C.c_void_p()
-    _check(lib.vsa_extend_hamming(index._h,
-                                  None if queries is None else queries._h,
-                                  seeds._h, C.byref(p), int(bool(palindromic)),
-                                  int(leastlength), int(maxdist),
-                                  int(seedlength), C.byref(h)))
-    return Result(h)
-
-
-def findquerymatches_hamming(index, queries, leastlength, maxdist,
-                             seedlength=0, palindromic=False):
-    """vmatch -l L -h K [-seedlength S] [-p] -q Q IDX"""
-    h = C.c_void_p()
-    _check(lib.vsa_findquerymatches_hamming(index._h, queries._h,
-                                            int(leastlength), int(maxdist),
-                                            int(seedlength),
-                                            int(bool(palindromic)),
-                                            C.byref(h)))
-    return Result(h)
-
-
-def findselfmatches_hamming(index, leastlength, maxdist, seedlength=0):
-    """vmatch -l L -h K [-seedlength S] IDX"""
-    h = C.c_void_p()
-    _check(lib.vsa_findselfmatches_hamming(index._h, int(leastlength),
-                                           int(maxdist), int(seedlength),
-                                           C.byref(h)))
-    return Result(h)
-
-
-def extend_hamming_host(text, seeds, leastlength, maxdist, seedlength=0,
-                        queries=None, numofchars=4, threads=0):
-    """the same extension on the host, any distance bound: text = the symbols
+    reverse complement), or None for the seeds of findmaximalrepeats""",
+     """vmatch -l L -h K [-seedlength S] [-p] -q Q IDX""",
+     """vmatch -l L -h K [-seedlength S] IDX""",
+     """the same extension on the host, any distance bound: text = the symbols
     of the index, queries = (symbols, start, length) of the batch the seeds
-    refer to (for -p: its reverse complement), or None for self seeds"""
-    text = np.ascontiguousarray(text, np.uint8)
-    seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
-    p, keep = sink_params(SINK_SELF if queries is None else SINK_QUERY,
-                          len(text), (), numofchars=numofchars,
-                          querystart=None if queries is None else queries[1],
-                          querylength=None if queries is None else queries[2])
-    qsym = None if queries is None else np.ascontiguousarray(queries[0],
-                                                             np.uint8)
-    out = np.zeros(len(seeds), MATCH_DTYPE)
-    n = C.c_uint64()
-    _check(lib.vsa_extend_hamming_host(
-        C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds), len(seeds),
-        int(leastlength), int(maxdist), int(seedlength), int(threads),
-        _ptr(out), len(out), C.byref(n)))
-    return out[:n.value]
+    refer to (for -p: its reverse complement), or None for self seeds"""))
 
 
 # ---- degenerate matches: vmatch -l L -e K [-seedlength S] [-p] [-q Q] IDX ----
@@ -2144,58 +2158,11 @@ def edist_pack(length1, length2, distance):
             diff << np.uint64(56))
 
 
-def extend_edist(index, queries, seeds, leastlength, maxdist, seedlength=0,
-                 palindromic=False):
-    """editextend (kurtz/extendED.c:78) for every seed of a Result; arguments
-    as for extend_hamming"""
-    p = SinkParams()
-    p.kind = SINK_SELF if queries is None else SINK_QUERY
-    h = C.c_void_p()
-    _check(lib.vsa_extend_edist(index._h,
-                                None if queries is None else queries._h,
-                                seeds._h, C.byref(p), int(bool(palindromic)),
-                                int(leastlength), int(maxdist),
-                                int(seedlength), C.byref(h)))
-    return Result(h)
-
-
-def findquerymatches_edist(index, queries, leastlength, maxdist,
-                           seedlength=0, palindromic=False):
-    """vmatch -l L -e K [-seedlength S] [-p] -q Q IDX"""
-    h = C.c_void_p()
-    _check(lib.vsa_findquerymatches_edist(index._h, queries._h,
-                                          int(leastlength), int(maxdist),
-                                          int(seedlength),
-                                          int(bool(palindromic)),
-                                          C.byref(h)))
-    return Result(h)
-
-
-def findselfmatches_edist(index, leastlength, maxdist, seedlength=0):
-    """vmatch -l L -e K [-seedlength S] IDX"""
-    h = C.c_void_p()
-    _check(lib.vsa_findselfmatches_edist(index._h, int(leastlength),
-                                         int(maxdist), int(seedlength),
-                                         C.byref(h)))
-    return Result(h)
-
-
-def extend_edist_host(text, seeds, leastlength, maxdist, seedlength=0,
-                      queries=None, numofchars=4, threads=0):
-    """the same extension on the host, any distance bound the record carries;
-    arguments as for extend_hamming_host"""
-    text = np.ascontiguousarray(text, np.uint8)
-    seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
-    p, keep = sink_params(SINK_SELF if queries is None else SINK_QUERY,
-                          len(text), (), numofchars=numofchars,
-                          querystart=None if queries is None else queries[1],
-                          querylength=None if queries is None else queries[2])
-    qsym = None if queries is None else np.ascontiguousarray(queries[0],
-                                                             np.uint8)
-    out = np.zeros(len(seeds), MATCH_DTYPE)
-    n = C.c_uint64()
-    _check(lib.vsa_extend_edist_host(
-        C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds), len(seeds),
-        int(leastlength), int(maxdist), int(seedlength), int(threads),
-        _ptr(out), len(out), C.byref(n)))
-    return out[:n.value]
+(extend_edist, findquerymatches_edist, findselfmatches_edist,
+ extend_edist_host) = _extension("edist", (
+     """editextend (kurtz/extendED.c:78) for every seed of a Result; arguments
+    as for extend_hamming""",
+     """vmatch -l L -e K [-seedlength S] [-p] -q Q IDX""",
+     """vmatch -l L -e K [-seedlength S] IDX""",
+     """the same extension on the host, any distance bound the record carries;
+    arguments as for extend_hamming_host"""))

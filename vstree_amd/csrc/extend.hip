@@ -36,12 +36,9 @@ namespace
 
 #define EXT_MISFIT 0xFFFFFFFFu
 #define EXT_BLOCK 256
-// words of the counters: items on the long list, seeds that do not fit, sum
-// of the lengths of the matches
-#define EXT_NLONG 0
-#define EXT_NMISFIT 1
-#define EXT_SUMLENGTH 2
-#define EXT_NCOUNTERS 3
+// the driver, the word load and the words of the counters; EXT_NSTAGE
+// counts the items on the long list
+#include "extend_shared.hpp"
 
 struct ExtParams
 {
@@ -91,17 +88,6 @@ __device__ __forceinline__ bool ext_views(const ExtParams &p,
   v2.atend = q + 1 == p.q.nq;
   pos2 = m.querystart;
   return pos2 <= qlen && m.length <= qlen - pos2;
-}
-
-// vsa_ext_word for `valid` >= 8 as one load
-__device__ __forceinline__ uint64_t ext_word(const uint8_t *p, int left,
-                                             uint64_t t0, uint64_t valid)
-{
-  if (valid < 8)
-  {
-    return vsa_ext_word(p, left, t0, valid);
-  }
-  return left ? __builtin_bswap64(vsa_load8(p - t0 - 7)) : vsa_load8(p + t0);
 }
 
 // sixteen symbols at t0 .. t0 + 15 as two such words
@@ -183,7 +169,7 @@ __global__ void __launch_bounds__(EXT_BLOCK) k_ext_scan(ExtParams p)
       }
     }
   }
-  const uint64_t slot = vsa_wave_reserve01(p.counters + EXT_NLONG, tolong);
+  const uint64_t slot = vsa_wave_reserve01(p.counters + EXT_NSTAGE, tolong);
   if (tolong)
   {
     p.longlist[slot] = (uint32_t) item;
@@ -194,7 +180,7 @@ __global__ void __launch_bounds__(EXT_BLOCK) k_ext_long(ExtParams p)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t nwaves = vsa_nblocks() * (EXT_BLOCK / 64),
-                 nlong = p.counters[EXT_NLONG];
+                 nlong = p.counters[EXT_NSTAGE];
 
   for (uint64_t w = vsa_bid() * (EXT_BLOCK / 64) + (threadIdx.x >> 6);
        w < nlong; w += nwaves)
@@ -298,7 +284,9 @@ k_ext_choose(ExtParams p, vsa_selrules ev, vsa_match *__restrict__ out,
     }
     keep[i] = k;
   }
-  // one atomic per wavefront for each of the two counts
+  // one atomic per wavefront for each of the two counts (stated in both
+  // choice kernels: as a shared inline function the sum below came out with
+  // the operands of one addition swapped in the device listing)
   const unsigned long long bad = __ballot(misfit);
   uint64_t sum = len;
 #pragma unroll
@@ -319,216 +307,87 @@ k_ext_choose(ExtParams p, vsa_selrules ev, vsa_match *__restrict__ out,
   }
 }
 
-// lanebudget() of VSA_EXTEND_STAGE and the compaction functor KeptRecords
-#include "extend_shared.hpp"
-
-// what every entry refuses before anything is run or kept
-int checkbounds(const char *who, const vsa_index *index,
-                const vsa_queries *queries, uint64_t leastlength,
-                uint64_t maxdist)
+// what the driver of extend_shared.hpp is given
+struct Hamming
 {
-  if (leastlength == 0 || maxdist == 0)
+  static constexpr uint32_t cap = VSA_EXTEND_MAXDIST;
+  static constexpr bool hequot = false;
+  static void hosttakes(char *buf, size_t n)
   {
-    VSA_ERROR("%s: a least length and a distance bound of at least 1", who);
-    return -2;
+    snprintf(buf, n, "vsa_extend_hamming_host takes any");
   }
-  if (maxdist > VSA_EXTEND_MAXDIST)
-  {
-    VSA_ERROR("%s: distance bound %lu: up to %u are covered on the device "
-              "(vsa_extend_hamming_host takes any)", who,
-              (unsigned long) maxdist, VSA_EXTEND_MAXDIST);
-    return VSA_NOT_COVERED;
-  }
-  if (index->n >= 0xFFFFFFF0ull ||
-      (queries != nullptr && queries->maxlength >= 0xFFFFFFF0ull))
-  {
-    VSA_ERROR("%s: texts and query sequences below 2^32 - 16 symbols are "
-              "covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (queries != nullptr && queries->device != index->device)
-  {
-    VSA_ERROR("%s: queries on device %d, index on device %d", who,
-              queries->device, index->device);
-    return -2;
-  }
-  return 0;
-}
 
-// the seeds of `seeds` extended in the index and -- self == 0 -- in the batch
-// they refer to; the arguments have been checked
-int extend(const char *who, const vsa_index *index,
-           const vsa_queries *queries, const vsa_result *seeds, int self,
-           uint64_t leastlength, uint64_t maxdist, uint64_t seedlength,
-           vsa_result **result)
-{
-  if (seeds->packbits != 0)
+  struct Stage
   {
-    VSA_ERROR("%s: a packed candidate result has no records to extend", who);
-    return VSA_NOT_COVERED;
-  }
-  if (seeds->extended)
-  {
-    VSA_ERROR("%s: the list holds extended seeds already", who);
-    return VSA_NOT_COVERED;
-  }
-  if (seeds->count >= (1ull << 31))
-  {
-    VSA_ERROR("%s: %lu seeds: fewer than 2^31 are covered", who,
-              (unsigned long) seeds->count);
-    return VSA_NOT_COVERED;
-  }
-  if (seeds->device != index->device)
-  {
-    VSA_ERROR("%s: seeds on device %d, index on device %d", who,
-              seeds->device, index->device);
-    return -2;
-  }
-  if (enter(index->device) != 0)
-  {
-    return -100;
-  }
-  vsa_result *res = newresult(index->device);
-  ResultGuard guard = {res};
-  res->extended = true;
-  res->stats.candidates = seeds->count;
-  if (seeds->count == 0)
-  {
-    guard.r = nullptr;
-    *result = res;
-    return 0;
-  }
-  if (!self && vsa_queries_bytes(queries, nullptr) != 0)
-  {
-    return -100;
-  }
-  // the E-value table up to line K (kurtz/evalues.c:315-364), as the sink
-  // and the selection make it
-  vsa_evalues hev;
-  vsa_evalues_init(&hev, index->numofchars);
-  if (vsa_evalues_extend(&hev, (int64_t) maxdist) != 0)
-  {
-    vsa_evalues_free(&hev);
-    VSA_ERROR("out of memory");
-    return -101;
-  }
-  DevBuf dtable, dlines;
-  const size_t tbytes = (size_t) hev.nexttab * 8,
-               lbytes = (size_t) (maxdist + 2) * 8;
-  int rc = (dtable.alloc(tbytes) != 0 || dlines.alloc(lbytes) != 0) ? -100 : 0;
-  if (rc == 0 &&
-      (hipMemcpy(dtable.p, hev.table, tbytes, hipMemcpyHostToDevice) !=
-           hipSuccess ||
-       hipMemcpy(dlines.p, hev.linestart, lbytes, hipMemcpyHostToDevice) !=
-           hipSuccess))
-  {
-    VSA_ERROR("%s: upload of the E-value table failed", who);
-    rc = -100;
-  }
-  vsa_evalues_free(&hev);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_selrules ev;
-  memset(&ev, 0, sizeof ev);
-  ev.table = dtable.as<double>();
-  ev.linestart = dlines.as<int64_t>();
-  ev.nlines = (int64_t) maxdist + 1;
+    // (the timers first: what is made behind a member whose constructor may
+    // throw is destroyed out of line, and DevBuf's destructor would become a
+    // symbol of the library)
+    Timer tscan{nullptr}, tlong{nullptr};
+    ExtParams p;
+    DevBuf look, hout, longlist;
 
-  ExtParams p;
-  memset(&p, 0, sizeof p);
-  p.tis = index->tis_alloc + VSA_TIS_FRONTPAD;
-  p.n = index->n;
-  p.self = self;
-  if (!self)
-  {
-    p.q = devqueries(queries);
-  }
-  p.seeds = seeds->matches;
-  p.nseeds = seeds->count;
-  p.nitems = 2 * seeds->count;
-  p.leastlength = leastlength;
-  p.seedlength = vsa_ext_seedlength(leastlength, maxdist, seedlength);
-  p.maxdist = (uint32_t) maxdist;
-  p.budget = lanebudget();
-  DevBuf look, hout, longlist, counters, recs, keep, offsets, out;
-  if (look.alloc((maxdist + 1) * p.nitems * 4) != 0 ||
-      hout.alloc(p.nitems * 4) != 0 || longlist.alloc(p.nitems * 4) != 0 ||
-      counters.alloc(EXT_NCOUNTERS * 8) != 0 ||
-      recs.alloc(p.nseeds * sizeof(vsa_match)) != 0 ||
-      keep.alloc(p.nseeds) != 0)
-  {
-    return -100;
-  }
-  p.look = look.as<uint32_t>();
-  p.hout = hout.as<uint32_t>();
-  p.longlist = longlist.as<uint32_t>();
-  p.counters = counters.as<unsigned long long>();
-
-  Timer tall(nullptr), tsearch(nullptr), tscan(nullptr), tlong(nullptr);
-  tall.start();
-  VSA_HIP(hipMemsetAsync(counters.p, 0, EXT_NCOUNTERS * 8, nullptr));
-  tsearch.start();
-  tscan.start();
-  k_ext_scan<<<vsa_grid((p.nitems + EXT_BLOCK - 1) / EXT_BLOCK), EXT_BLOCK, 0,
-               nullptr>>>(p);
-  VSA_HIP(hipGetLastError());
-  tscan.stop();
-  // (a wavefront per item at most, and no more than fill the device a few
-  // times over: the wavefronts take items until the list is done)
-  const uint64_t longblocks = std::min<uint64_t>(
-      (p.nitems + EXT_BLOCK / 64 - 1) / (EXT_BLOCK / 64), 8192);
-  tlong.start();
-  k_ext_long<<<vsa_grid(longblocks), EXT_BLOCK, 0, nullptr>>>(p);
-  VSA_HIP(hipGetLastError());
-  tlong.stop();
-  k_ext_choose<<<vsa_grid((p.nseeds + EXT_BLOCK - 1) / EXT_BLOCK), EXT_BLOCK,
-                 0, nullptr>>>(p, ev, recs.as<vsa_match>(),
-                               keep.as<uint8_t>());
-  VSA_HIP(hipGetLastError());
-  tsearch.stop();
-  KeptRecords f = {keep.as<uint8_t>(), recs.as<vsa_match>(), nullptr};
-  uint64_t nout = 0;
-  if (tc_count<1, 1>(f, p.nseeds, offsets, &nout) != 0)
-  {
-    return -100;
-  }
-  uint64_t words[EXT_NCOUNTERS];
-  VSA_HIP(hipMemcpy(words, counters.p, sizeof words, hipMemcpyDeviceToHost));
-  if (words[EXT_NMISFIT] != 0)
-  {
-    VSA_ERROR("%s: %lu seeds do not fit the index or their query sequence",
-              who, (unsigned long) words[EXT_NMISFIT]);
-    return -2;
-  }
-  if (nout > 0)
-  {
-    if (out.alloc(nout * sizeof(vsa_match)) != 0)
+    int prepare(const ExtCall &c, Timer &)
     {
-      return -100;
+      memset(&p, 0, sizeof p);
+      p.tis = c.index->tis_alloc + VSA_TIS_FRONTPAD;
+      p.n = c.index->n;
+      p.self = c.self;
+      if (!c.self)
+      {
+        p.q = devqueries(c.queries);
+      }
+      p.seeds = c.seeds->matches;
+      p.nseeds = c.seeds->count;
+      p.nitems = 2 * c.seeds->count;
+      p.leastlength = c.leastlength;
+      p.seedlength = c.seedlength;
+      p.maxdist = (uint32_t) c.maxdist;
+      p.budget = lanebudget();
+      if (look.alloc((c.maxdist + 1) * p.nitems * 4) != 0 ||
+          hout.alloc(p.nitems * 4) != 0 || longlist.alloc(p.nitems * 4) != 0)
+      {
+        return -100;
+      }
+      p.look = look.as<uint32_t>();
+      p.hout = hout.as<uint32_t>();
+      p.longlist = longlist.as<uint32_t>();
+      return 0;
     }
-    f.out = out.as<vsa_match>();
-    if (tc_emit<1>(f, p.nseeds, offsets) != 0)
+
+    int run(const ExtCall &c, vsa_match *recs, uint8_t *keep,
+            unsigned long long *counters, Timer &tall, Timer &tsearch)
     {
-      return -100;
+      p.counters = counters;
+      tall.start();
+      VSA_HIP(hipMemsetAsync(counters, 0, EXT_NCOUNTERS * 8, nullptr));
+      tsearch.start();
+      tscan.start();
+      k_ext_scan<<<vsa_grid((p.nitems + EXT_BLOCK - 1) / EXT_BLOCK),
+                   EXT_BLOCK, 0, nullptr>>>(p);
+      VSA_HIP(hipGetLastError());
+      tscan.stop();
+      // (a wavefront per item at most, and no more than fill the device a
+      // few times over: the wavefronts take items until the list is done)
+      const uint64_t longblocks = std::min<uint64_t>(
+          (p.nitems + EXT_BLOCK / 64 - 1) / (EXT_BLOCK / 64), 8192);
+      tlong.start();
+      k_ext_long<<<vsa_grid(longblocks), EXT_BLOCK, 0, nullptr>>>(p);
+      VSA_HIP(hipGetLastError());
+      tlong.stop();
+      k_ext_choose<<<vsa_grid((p.nseeds + EXT_BLOCK - 1) / EXT_BLOCK),
+                     EXT_BLOCK, 0, nullptr>>>(p, c.ev, recs, keep);
+      VSA_HIP(hipGetLastError());
+      tsearch.stop();
+      return 0;
     }
-  }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(nullptr));
-  res->count = nout;
-  res->matches = nout > 0 ? (vsa_match *) out.release() : nullptr;
-  res->stats.count = nout;
-  res->stats.sumlength = words[EXT_SUMLENGTH];
-  res->stats.searches = words[EXT_NLONG];
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.first_kernel_ms = tscan.ms();
-  res->stats.anchor_ms = tlong.ms();
-  res->stats.total_device_ms = tall.ms();
-  guard.r = nullptr;
-  *result = res;
-  return 0;
-}
+
+    void stats(vsa_stats &st)
+    {
+      st.first_kernel_ms = tscan.ms();
+      st.anchor_ms = tlong.ms();
+    }
+  };
+};
 
 } // namespace
 
@@ -562,38 +421,9 @@ extern "C" int vsa_extend_hamming(const vsa_index *index,
                                   uint64_t maxdist, uint64_t seedlength,
                                   vsa_result **result)
 {
-  const char *who = "vsa_extend_hamming";
-  if (index == nullptr || seeds == nullptr || layout == nullptr ||
-      result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  const bool self = layout->kind == VSA_SINK_SELF;
-  if ((!self && layout->kind != VSA_SINK_QUERY) ||
-      self != (queries == nullptr) || (self && palindromic))
-  {
-    VSA_ERROR("%s: the seeds of a query layout (VSA_SINK_QUERY, with their "
-              "batch) or of a self layout (VSA_SINK_SELF, no batch, not "
-              "palindromic) are extended", who);
-    return -2;
-  }
-  int rc = checkbounds(who, index, queries, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_queries *rcq = nullptr;
-  if (palindromic &&
-      (rc = vsa_queries_reverse_complement(queries, &rcq)) != 0)
-  {
-    return rc;
-  }
-  rc = extend(who, index, palindromic ? rcq : queries, seeds, self,
-              leastlength, maxdist, seedlength, result);
-  vsa_queries_free(rcq);
-  return rc;
+  return extend_list<Hamming>("vsa_extend_hamming", index, queries, seeds,
+                              layout, palindromic, leastlength, maxdist,
+                              seedlength, result);
 }
 
 extern "C" int vsa_findquerymatches_hamming(const vsa_index *index,
@@ -604,37 +434,9 @@ extern "C" int vsa_findquerymatches_hamming(const vsa_index *index,
                                             int palindromic,
                                             vsa_result **result)
 {
-  const char *who = "vsa_findquerymatches_hamming";
-  if (index == nullptr || queries == nullptr || result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  int rc = checkbounds(who, index, queries, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_queries *rcq = nullptr;
-  if (palindromic &&
-      (rc = vsa_queries_reverse_complement(queries, &rcq)) != 0)
-  {
-    return rc;
-  }
-  const vsa_queries *batch = palindromic ? rcq : queries;
-  vsa_result *seeds = nullptr;
-  rc = vsa_findquerymatches(
-      index, batch, 0, 0, vsa_ext_seedlength(leastlength, maxdist, seedlength),
-      &seeds);
-  if (rc == 0)
-  {
-    rc = extend(who, index, batch, seeds, 0, leastlength, maxdist, seedlength,
-                result);
-  }
-  vsa_result_free(seeds);
-  vsa_queries_free(rcq);
-  return rc;
+  return extend_queries<Hamming>("vsa_findquerymatches_hamming", index,
+                                 queries, leastlength, maxdist, seedlength,
+                                 palindromic, result);
 }
 
 extern "C" int vsa_findselfmatches_hamming(const vsa_index *index,
@@ -643,26 +445,6 @@ extern "C" int vsa_findselfmatches_hamming(const vsa_index *index,
                                            uint64_t seedlength,
                                            vsa_result **result)
 {
-  const char *who = "vsa_findselfmatches_hamming";
-  if (index == nullptr || result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  int rc = checkbounds(who, index, nullptr, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_result *seeds = nullptr;
-  rc = vsa_findmaximalrepeats(
-      index, vsa_ext_seedlength(leastlength, maxdist, seedlength), &seeds);
-  if (rc == 0)
-  {
-    rc = extend(who, index, nullptr, seeds, 1, leastlength, maxdist,
-                seedlength, result);
-  }
-  vsa_result_free(seeds);
-  return rc;
+  return extend_self<Hamming>("vsa_findselfmatches_hamming", index,
+                              leastlength, maxdist, seedlength, result);
 }

@@ -39,16 +39,13 @@
 namespace
 {
 
+// the driver, the word load and the words of the counters; EXT_NSTAGE
+// counts the sides with a slide the group finished, EXT_SUMLENGTH sums
+// length1 of the matches
 #include "extend_shared.hpp"
 
 #define ED_MISFIT 0xFFFFFFFFu
 #define ED_BLOCK 256
-// words of the counters: sides with a slide the group finished, seeds that
-// do not fit, sum of length1 of the matches
-#define ED_NCOOP 0
-#define ED_NMISFIT 1
-#define ED_SUMLENGTH 2
-#define ED_NCOUNTERS 3
 // device scratch of the fronts of one piece of the seed list
 #define ED_SCRATCH ((uint64_t) 256 << 20)
 
@@ -130,17 +127,6 @@ k_ed_flatten(EdParams p, uint8_t *__restrict__ out)
   }
 }
 
-// vsa_ext_word for `valid` >= 8 as one load
-__device__ __forceinline__ uint64_t ed_word(const uint8_t *p, int left,
-                                            uint64_t t0, uint64_t valid)
-{
-  if (valid < 8)
-  {
-    return vsa_ext_word(p, left, t0, valid);
-  }
-  return left ? __builtin_bswap64(vsa_load8(p - t0 - 7)) : vsa_load8(p + t0);
-}
-
 // the marks of the words at offset `at` of a slide from (t, t + k) of which
 // `valid` symbols are below the bounds; a, c: the words
 __device__ __forceinline__ uint32_t ed_marks(const vsa_ed_side &s, int64_t t,
@@ -152,8 +138,8 @@ __device__ __forceinline__ uint32_t ed_marks(const vsa_ed_side &s, int64_t t,
                 *pv = s.s2 + (s.left ? s.o2 - (t + k) : s.o2 + (t + k));
   uint32_t sep;
 
-  a = ed_word(pu, s.left, (uint64_t) at, (uint64_t) valid);
-  c = ed_word(pv, s.left, (uint64_t) at, (uint64_t) valid);
+  a = ext_word(pu, s.left, (uint64_t) at, (uint64_t) valid);
+  c = ext_word(pv, s.left, (uint64_t) at, (uint64_t) valid);
   const uint32_t marks = vsa_ext_marks8(a, c, &sep);
   return valid < 8 ? marks & ((1u << valid) - 1u) : marks;
 }
@@ -385,7 +371,7 @@ __global__ void __launch_bounds__(ED_BLOCK) k_ed_fronts(EdParams p)
   }
   if (coop && gl == 0)
   {
-    atomicAdd(p.counters + ED_NCOOP, 1ull);
+    atomicAdd(p.counters + EXT_NSTAGE, 1ull);
   }
 }
 
@@ -428,7 +414,9 @@ k_ed_choose(EdParams p, vsa_selrules ev, vsa_match *__restrict__ out,
     }
     keep[p.first + i] = kept;
   }
-  // one atomic per wavefront for each of the two counts
+  // one atomic per wavefront for each of the two counts (stated in both
+  // choice kernels: as a shared inline function the sum below came out with
+  // the operands of one addition swapped in the device listing)
   const unsigned long long bad = __ballot(misfit);
   uint64_t sum = len;
 #pragma unroll
@@ -440,11 +428,11 @@ k_ed_choose(EdParams p, vsa_selrules ev, vsa_match *__restrict__ out,
   {
     if (bad != 0)
     {
-      atomicAdd(p.counters + ED_NMISFIT, (unsigned long long) __popcll(bad));
+      atomicAdd(p.counters + EXT_NMISFIT, (unsigned long long) __popcll(bad));
     }
     if (sum != 0)
     {
-      atomicAdd(p.counters + ED_SUMLENGTH, (unsigned long long) sum);
+      atomicAdd(p.counters + EXT_SUMLENGTH, (unsigned long long) sum);
     }
   }
 }
@@ -457,40 +445,6 @@ uint64_t scratchbudget()
   return v != 0 ? v : ED_SCRATCH;
 }
 
-// what every entry refuses before anything is run or kept
-int checkbounds(const char *who, const vsa_index *index,
-                const vsa_queries *queries, uint64_t leastlength,
-                uint64_t maxdist)
-{
-  if (leastlength == 0 || maxdist == 0)
-  {
-    VSA_ERROR("%s: a least length and a distance bound of at least 1", who);
-    return -2;
-  }
-  if (maxdist > VSA_EXTEND_EDIST_MAXDIST)
-  {
-    VSA_ERROR("%s: distance bound %lu: up to %u are covered on the device "
-              "(vsa_extend_edist_host takes up to %u)", who,
-              (unsigned long) maxdist, VSA_EXTEND_EDIST_MAXDIST,
-              VSA_EDIST_MAXDISTANCE);
-    return VSA_NOT_COVERED;
-  }
-  if (index->n >= 0xFFFFFFF0ull ||
-      (queries != nullptr && queries->maxlength >= 0xFFFFFFF0ull))
-  {
-    VSA_ERROR("%s: texts and query sequences below 2^32 - 16 symbols are "
-              "covered", who);
-    return VSA_NOT_COVERED;
-  }
-  if (queries != nullptr && queries->device != index->device)
-  {
-    VSA_ERROR("%s: queries on device %d, index on device %d", who,
-              queries->device, index->device);
-    return -2;
-  }
-  return 0;
-}
-
 template <int W>
 int launchfronts(const EdParams &p)
 {
@@ -501,235 +455,133 @@ int launchfronts(const EdParams &p)
   return 0;
 }
 
-// the seeds of `seeds` extended in the index and -- self == 0 -- in the batch
-// they refer to; the arguments have been checked
-int extend(const char *who, const vsa_index *index,
-           const vsa_queries *queries, const vsa_result *seeds, int self,
-           uint64_t leastlength, uint64_t maxdist, uint64_t seedlength,
-           vsa_result **result)
+// what the driver of extend_shared.hpp is given
+struct Edist
 {
-  if (seeds->packbits != 0)
+  static constexpr uint32_t cap = VSA_EXTEND_EDIST_MAXDIST;
+  static constexpr bool hequot = true;
+  static void hosttakes(char *buf, size_t n)
   {
-    VSA_ERROR("%s: a packed candidate result has no records to extend", who);
-    return VSA_NOT_COVERED;
+    snprintf(buf, n, "vsa_extend_edist_host takes up to %u",
+             VSA_EDIST_MAXDISTANCE);
   }
-  if (seeds->extended)
-  {
-    VSA_ERROR("%s: the list holds extended seeds already", who);
-    return VSA_NOT_COVERED;
-  }
-  if (seeds->count >= (1ull << 31))
-  {
-    VSA_ERROR("%s: %lu seeds: fewer than 2^31 are covered", who,
-              (unsigned long) seeds->count);
-    return VSA_NOT_COVERED;
-  }
-  if (seeds->device != index->device)
-  {
-    VSA_ERROR("%s: seeds on device %d, index on device %d", who,
-              seeds->device, index->device);
-    return -2;
-  }
-  if (enter(index->device) != 0)
-  {
-    return -100;
-  }
-  vsa_result *res = newresult(index->device);
-  ResultGuard guard = {res};
-  res->extended = true;
-  res->stats.candidates = seeds->count;
-  if (seeds->count == 0)
-  {
-    guard.r = nullptr;
-    *result = res;
-    return 0;
-  }
-  if (!self && vsa_queries_bytes(queries, nullptr) != 0)
-  {
-    return -100;
-  }
-  // the E-value table up to line K with the factors of the edit distances
-  // (kurtz/evalues.c:315-420), as the sink and the selection make them
-  vsa_evalues hev;
-  vsa_evalues_init(&hev, index->numofchars);
-  if (vsa_evalues_extend(&hev, (int64_t) maxdist) != 0)
-  {
-    vsa_evalues_free(&hev);
-    VSA_ERROR("out of memory");
-    return -101;
-  }
-  double hequot[VSA_EXTEND_EDIST_MAXDIST + 1];
-  for (uint64_t d = 0; d <= maxdist; d++)
-  {
-    hequot[d] = vsa_evalues_hequot((int64_t) d);
-  }
-  DevBuf dtable, dlines, dquot;
-  const size_t tbytes = (size_t) hev.nexttab * 8,
-               lbytes = (size_t) (maxdist + 2) * 8,
-               qbytes = (size_t) (maxdist + 1) * 8;
-  int rc = (dtable.alloc(tbytes) != 0 || dlines.alloc(lbytes) != 0 ||
-            dquot.alloc(qbytes) != 0)
-               ? -100
-               : 0;
-  if (rc == 0 &&
-      (hipMemcpy(dtable.p, hev.table, tbytes, hipMemcpyHostToDevice) !=
-           hipSuccess ||
-       hipMemcpy(dlines.p, hev.linestart, lbytes, hipMemcpyHostToDevice) !=
-           hipSuccess ||
-       hipMemcpy(dquot.p, hequot, qbytes, hipMemcpyHostToDevice) !=
-           hipSuccess))
-  {
-    VSA_ERROR("%s: upload of the E-value table failed", who);
-    rc = -100;
-  }
-  vsa_evalues_free(&hev);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_selrules ev;
-  memset(&ev, 0, sizeof ev);
-  ev.table = dtable.as<double>();
-  ev.linestart = dlines.as<int64_t>();
-  ev.hequot = dquot.as<double>();
-  ev.nlines = (int64_t) maxdist + 1;
 
-  EdParams p;
-  memset(&p, 0, sizeof p);
-  p.s1 = index->tis_alloc + VSA_TIS_FRONTPAD;
-  p.n1 = index->n;
-  p.self = self;
-  p.seeds = seeds->matches;
-  p.leastlength = leastlength;
-  p.seedlength = vsa_ext_seedlength(leastlength, maxdist, seedlength);
-  p.maxdist = (uint32_t) maxdist;
-  p.budget = lanebudget();
-  DevBuf flat, abs2, fronts, hout, counters, recs, keep, offsets, out;
-  Timer tall(nullptr), tsearch(nullptr);
-  tall.start();
-  if (self)
+  struct Stage
   {
-    p.s2 = p.s1;
-    p.n2 = p.n1;
-  } else
-  {
-    p.q = devqueries(queries);
-    const uint64_t nq = queries->nq;
-    uint64_t total = 0;
-    if (p.q.uniformlen != 0)
+    EdParams p;
+    DevBuf flat, abs2, fronts, hout;
+    uint64_t piece = 0;
+    float frontsms = 0.0f;
+
+    // the query Multiseq and the fronts of one piece of the seed list
+    int prepare(const ExtCall &c, Timer &tall)
     {
-      total = nq * ((uint64_t) p.q.uniformlen + 1) - (nq > 0 ? 1 : 0);
-    } else
-    {
-      if (queries->hlength.size() != nq)
+      memset(&p, 0, sizeof p);
+      p.s1 = c.index->tis_alloc + VSA_TIS_FRONTPAD;
+      p.n1 = c.index->n;
+      p.self = c.self;
+      p.seeds = c.seeds->matches;
+      p.leastlength = c.leastlength;
+      p.seedlength = c.seedlength;
+      p.maxdist = (uint32_t) c.maxdist;
+      p.budget = lanebudget();
+      tall.start();
+      if (c.self)
       {
-        VSA_ERROR("%s: the batch has no host copy of its lengths", who);
-        return -2;
-      }
-      std::vector<uint64_t> starts(nq);
-      for (uint64_t i = 0; i < nq; i++)
+        p.s2 = p.s1;
+        p.n2 = p.n1;
+      } else
       {
-        starts[i] = total + (i > 0 ? 1 : 0);
-        total = starts[i] + queries->hlength[i];
+        p.q = devqueries(c.queries);
+        const uint64_t nq = c.queries->nq;
+        uint64_t total = 0;
+        if (p.q.uniformlen != 0)
+        {
+          total = nq * ((uint64_t) p.q.uniformlen + 1) - (nq > 0 ? 1 : 0);
+        } else
+        {
+          if (c.queries->hlength.size() != nq)
+          {
+            VSA_ERROR("%s: the batch has no host copy of its lengths", c.who);
+            return -2;
+          }
+          std::vector<uint64_t> starts(nq);
+          for (uint64_t i = 0; i < nq; i++)
+          {
+            starts[i] = total + (i > 0 ? 1 : 0);
+            total = starts[i] + c.queries->hlength[i];
+          }
+          if (abs2.alloc(nq * 8) != 0)
+          {
+            return -100;
+          }
+          VSA_HIP(hipMemcpy(abs2.p, starts.data(), nq * 8,
+                            hipMemcpyHostToDevice));
+          p.abs2 = abs2.as<uint64_t>();
+        }
+        if (flat.alloc(total + 16) != 0)
+        {
+          return -100;
+        }
+        const uint64_t blocks = std::min<uint64_t>(
+            (nq + ED_BLOCK / 64 - 1) / (ED_BLOCK / 64), 65536);
+        k_ed_flatten<<<vsa_grid(blocks), ED_BLOCK, 0, nullptr>>>(
+            p, flat.as<uint8_t>());
+        VSA_HIP(hipGetLastError());
+        p.s2 = flat.as<uint8_t>();
+        p.n2 = total;
       }
-      if (abs2.alloc(nq * 8) != 0)
+      const uint64_t words = vsa_ed_frontwords(c.maxdist);
+      piece = std::min<uint64_t>(
+          c.seeds->count,
+          std::max<uint64_t>(scratchbudget() / (2 * words * 4), 1));
+      if (fronts.alloc(piece * 2 * words * 4) != 0 ||
+          hout.alloc(piece * 2 * 4) != 0)
       {
         return -100;
       }
-      VSA_HIP(hipMemcpy(abs2.p, starts.data(), nq * 8,
-                        hipMemcpyHostToDevice));
-      p.abs2 = abs2.as<uint64_t>();
+      p.fronts = fronts.as<uint32_t>();
+      p.hout = hout.as<uint32_t>();
+      return 0;
     }
-    if (flat.alloc(total + 16) != 0)
+
+    int run(const ExtCall &c, vsa_match *recs, uint8_t *keep,
+            unsigned long long *counters, Timer &, Timer &tsearch)
     {
-      return -100;
+      const uint64_t nseeds = c.seeds->count;
+      p.counters = counters;
+      VSA_HIP(hipMemsetAsync(counters, 0, EXT_NCOUNTERS * 8, nullptr));
+      tsearch.start();
+      for (uint64_t first = 0; first < nseeds; first += piece)
+      {
+        p.first = first;
+        p.count = std::min<uint64_t>(piece, nseeds - first);
+        Timer tf(nullptr);
+        tf.start();
+        const int rc = c.maxdist <= 7    ? launchfronts<16>(p)
+                       : c.maxdist <= 15 ? launchfronts<32>(p)
+                                         : launchfronts<64>(p);
+        if (rc != 0)
+        {
+          return rc;
+        }
+        tf.stop();
+        k_ed_choose<<<vsa_grid((p.count + ED_BLOCK - 1) / ED_BLOCK), ED_BLOCK,
+                      0, nullptr>>>(p, c.ev, recs, keep);
+        VSA_HIP(hipGetLastError());
+        VSA_HIP(hipStreamSynchronize(nullptr));
+        frontsms += tf.ms();
+      }
+      tsearch.stop();
+      return 0;
     }
-    const uint64_t blocks = std::min<uint64_t>(
-        (nq + ED_BLOCK / 64 - 1) / (ED_BLOCK / 64), 65536);
-    k_ed_flatten<<<vsa_grid(blocks), ED_BLOCK, 0, nullptr>>>(
-        p, flat.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    p.s2 = flat.as<uint8_t>();
-    p.n2 = total;
-  }
-  const uint64_t nseeds = seeds->count, words = vsa_ed_frontwords(maxdist);
-  const uint64_t piece = std::min<uint64_t>(
-      nseeds, std::max<uint64_t>(scratchbudget() / (2 * words * 4), 1));
-  if (fronts.alloc(piece * 2 * words * 4) != 0 ||
-      hout.alloc(piece * 2 * 4) != 0 ||
-      counters.alloc(ED_NCOUNTERS * 8) != 0 ||
-      recs.alloc(nseeds * sizeof(vsa_match)) != 0 || keep.alloc(nseeds) != 0)
-  {
-    return -100;
-  }
-  p.fronts = fronts.as<uint32_t>();
-  p.hout = hout.as<uint32_t>();
-  p.counters = counters.as<unsigned long long>();
-  VSA_HIP(hipMemsetAsync(counters.p, 0, ED_NCOUNTERS * 8, nullptr));
-  tsearch.start();
-  float frontsms = 0.0f;
-  for (uint64_t first = 0; first < nseeds; first += piece)
-  {
-    p.first = first;
-    p.count = std::min<uint64_t>(piece, nseeds - first);
-    Timer tf(nullptr);
-    tf.start();
-    rc = maxdist <= 7    ? launchfronts<16>(p)
-         : maxdist <= 15 ? launchfronts<32>(p)
-                         : launchfronts<64>(p);
-    if (rc != 0)
+
+    void stats(vsa_stats &st)
     {
-      return rc;
+      st.first_kernel_ms = frontsms;
     }
-    tf.stop();
-    k_ed_choose<<<vsa_grid((p.count + ED_BLOCK - 1) / ED_BLOCK), ED_BLOCK, 0,
-                  nullptr>>>(p, ev, recs.as<vsa_match>(), keep.as<uint8_t>());
-    VSA_HIP(hipGetLastError());
-    VSA_HIP(hipStreamSynchronize(nullptr));
-    frontsms += tf.ms();
-  }
-  tsearch.stop();
-  KeptRecords f = {keep.as<uint8_t>(), recs.as<vsa_match>(), nullptr};
-  uint64_t nout = 0;
-  if (tc_count<1, 1>(f, nseeds, offsets, &nout) != 0)
-  {
-    return -100;
-  }
-  uint64_t cwords[ED_NCOUNTERS];
-  VSA_HIP(hipMemcpy(cwords, counters.p, sizeof cwords,
-                    hipMemcpyDeviceToHost));
-  if (cwords[ED_NMISFIT] != 0)
-  {
-    VSA_ERROR("%s: %lu seeds do not fit the index or their query sequence",
-              who, (unsigned long) cwords[ED_NMISFIT]);
-    return -2;
-  }
-  if (nout > 0)
-  {
-    if (out.alloc(nout * sizeof(vsa_match)) != 0)
-    {
-      return -100;
-    }
-    f.out = out.as<vsa_match>();
-    if (tc_emit<1>(f, nseeds, offsets) != 0)
-    {
-      return -100;
-    }
-  }
-  tall.stop();
-  VSA_HIP(hipStreamSynchronize(nullptr));
-  res->count = nout;
-  res->matches = nout > 0 ? (vsa_match *) out.release() : nullptr;
-  res->stats.count = nout;
-  res->stats.sumlength = cwords[ED_SUMLENGTH];
-  res->stats.searches = cwords[ED_NCOOP];
-  res->stats.search_kernel_ms = tsearch.ms();
-  res->stats.first_kernel_ms = frontsms;
-  res->stats.total_device_ms = tall.ms();
-  guard.r = nullptr;
-  *result = res;
-  return 0;
-}
+  };
+};
 
 } // namespace
 
@@ -745,38 +597,9 @@ extern "C" int vsa_extend_edist(const vsa_index *index,
                                 uint64_t leastlength, uint64_t maxdist,
                                 uint64_t seedlength, vsa_result **result)
 {
-  const char *who = "vsa_extend_edist";
-  if (index == nullptr || seeds == nullptr || layout == nullptr ||
-      result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  const bool self = layout->kind == VSA_SINK_SELF;
-  if ((!self && layout->kind != VSA_SINK_QUERY) ||
-      self != (queries == nullptr) || (self && palindromic))
-  {
-    VSA_ERROR("%s: the seeds of a query layout (VSA_SINK_QUERY, with their "
-              "batch) or of a self layout (VSA_SINK_SELF, no batch, not "
-              "palindromic) are extended", who);
-    return -2;
-  }
-  int rc = checkbounds(who, index, queries, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_queries *rcq = nullptr;
-  if (palindromic &&
-      (rc = vsa_queries_reverse_complement(queries, &rcq)) != 0)
-  {
-    return rc;
-  }
-  rc = extend(who, index, palindromic ? rcq : queries, seeds, self,
-              leastlength, maxdist, seedlength, result);
-  vsa_queries_free(rcq);
-  return rc;
+  return extend_list<Edist>("vsa_extend_edist", index, queries, seeds, layout,
+                            palindromic, leastlength, maxdist, seedlength,
+                            result);
 }
 
 extern "C" int vsa_findquerymatches_edist(const vsa_index *index,
@@ -787,37 +610,9 @@ extern "C" int vsa_findquerymatches_edist(const vsa_index *index,
                                           int palindromic,
                                           vsa_result **result)
 {
-  const char *who = "vsa_findquerymatches_edist";
-  if (index == nullptr || queries == nullptr || result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  int rc = checkbounds(who, index, queries, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_queries *rcq = nullptr;
-  if (palindromic &&
-      (rc = vsa_queries_reverse_complement(queries, &rcq)) != 0)
-  {
-    return rc;
-  }
-  const vsa_queries *batch = palindromic ? rcq : queries;
-  vsa_result *seeds = nullptr;
-  rc = vsa_findquerymatches(
-      index, batch, 0, 0, vsa_ext_seedlength(leastlength, maxdist, seedlength),
-      &seeds);
-  if (rc == 0)
-  {
-    rc = extend(who, index, batch, seeds, 0, leastlength, maxdist, seedlength,
-                result);
-  }
-  vsa_result_free(seeds);
-  vsa_queries_free(rcq);
-  return rc;
+  return extend_queries<Edist>("vsa_findquerymatches_edist", index, queries,
+                               leastlength, maxdist, seedlength, palindromic,
+                               result);
 }
 
 extern "C" int vsa_findselfmatches_edist(const vsa_index *index,
@@ -826,26 +621,6 @@ extern "C" int vsa_findselfmatches_edist(const vsa_index *index,
                                          uint64_t seedlength,
                                          vsa_result **result)
 {
-  const char *who = "vsa_findselfmatches_edist";
-  if (index == nullptr || result == nullptr)
-  {
-    VSA_ERROR("%s: NULL argument", who);
-    return -1;
-  }
-  *result = nullptr;
-  int rc = checkbounds(who, index, nullptr, leastlength, maxdist);
-  if (rc != 0)
-  {
-    return rc;
-  }
-  vsa_result *seeds = nullptr;
-  rc = vsa_findmaximalrepeats(
-      index, vsa_ext_seedlength(leastlength, maxdist, seedlength), &seeds);
-  if (rc == 0)
-  {
-    rc = extend(who, index, nullptr, seeds, 1, leastlength, maxdist,
-                seedlength, result);
-  }
-  vsa_result_free(seeds);
-  return rc;
+  return extend_self<Edist>("vsa_findselfmatches_edist", index, leastlength,
+                            maxdist, seedlength, result);
 }

@@ -7,100 +7,55 @@
    the seeds.  The query batch is laid out as the reference's Multiseq first,
    one array with a separator between two sequences, wherever its sequences
    lie in querysymbols. */
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 #include "vstree_amd.h"
-#include "host_common.h"
+#include "extend_host_common.h"
 #include "extend_edist_rules.h"
 
 #define WHO "vsa_extend_edist_host"
 
 typedef struct
 {
-  const vsa_sinkparams *layout;
   const uint8_t *text, *seq2; /* the two Multiseqs */
-  uint64_t n2;
+  uint64_t n, n2;
   const uint64_t *abs2; /* where the query sequences begin in seq2 */
-  const vsa_match *seeds;
+  int self;
   uint64_t leastlength, maxdist, seedlength;
   int bytewise;
   const vsa_selrules *ev;
-  vsa_match *out; /* out[i]: the match of seed i, where keep[i] */
-  uint8_t *keep;
 } Job;
 
-typedef struct
+/* vsa_exthost_seed: scratch is the fronts of the two sides */
+static int extendseed(const void *job, void *scratch, const vsa_match *m,
+                      uint64_t where, vsa_match *out)
 {
-  const Job *job;
-  uint64_t first, last;
-  int64_t misfit; /* the first seed that does not fit the layout, or -1 */
-  int nomem;
-} Piece;
+  const Job *j = (const Job *) job;
+  const uint64_t pos2 = j->self ? where : j->abs2[where] + m->querystart;
+  uint64_t *lf = (uint64_t *) scratch,
+           *rf = lf + vsa_ed_frontwords(j->maxdist);
+  vsa_ed_side ls, rs;
+  vsa_ed_match best = {0, 0, 0, 0, 0};
+  uint32_t hleft, hright;
 
-static void *extendpiece(void *arg)
+  vsa_ed_side_init(&ls, j->text, j->n, j->seq2, j->n2, j->self, m->dbstart,
+                   pos2, m->length, 1, j->maxdist, j->seedlength);
+  vsa_ed_side_init(&rs, j->text, j->n, j->seq2, j->n2, j->self, m->dbstart,
+                   pos2, m->length, 0, j->maxdist, j->seedlength);
+  hleft = vsa_ed_fronts(&ls, lf, j->bytewise);
+  hright = vsa_ed_fronts(&rs, rf, j->bytewise);
+  if (!vsa_ed_choose(j->ev, &ls, &rs, j->self, m->dbstart, pos2, m->length,
+                     j->leastlength, lf, hleft, rf, hright, &best))
+  {
+    return 0;
+  }
+  vsa_ed_record(m, j->self, pos2, &best, out);
+  return 1;
+}
+
+static void *extendpiece(void *piece)
 {
-  Piece *p = (Piece *) arg;
-  const Job *j = p->job;
-  const vsa_sinkparams *lay = j->layout;
-  const int self = lay->kind == VSA_SINK_SELF;
-  const uint64_t n = lay->totallength, words = vsa_ed_frontwords(j->maxdist);
-  uint64_t *lf = (uint64_t *) malloc(2 * words * sizeof *lf);
-  uint64_t *rf = lf + words, i;
-
-  if (lf == NULL)
-  {
-    p->nomem = 1;
-    return NULL;
-  }
-  for (i = p->first; i < p->last; i++)
-  {
-    const vsa_match *m = j->seeds + i;
-    uint64_t pos2 = m->queryseq;
-    vsa_ed_side ls, rs;
-    vsa_ed_match best = {0, 0, 0, 0, 0};
-    uint32_t hleft, hright;
-
-    j->keep[i] = 0;
-    if (m->length == 0 || m->dbstart > n || m->length > n - m->dbstart)
-    {
-      p->misfit = (int64_t) i;
-      break;
-    }
-    if (self)
-    {
-      if (pos2 > n || m->length > n - pos2)
-      {
-        p->misfit = (int64_t) i;
-        break;
-      }
-    } else
-    {
-      const uint64_t q = m->queryseq;
-      if (q >= lay->numofqueries || m->querystart > lay->querylength[q] ||
-          m->length > lay->querylength[q] - m->querystart)
-      {
-        p->misfit = (int64_t) i;
-        break;
-      }
-      pos2 = j->abs2[q] + m->querystart;
-    }
-    vsa_ed_side_init(&ls, j->text, n, j->seq2, j->n2, self, m->dbstart, pos2,
-                     m->length, 1, j->maxdist, j->seedlength);
-    vsa_ed_side_init(&rs, j->text, n, j->seq2, j->n2, self, m->dbstart, pos2,
-                     m->length, 0, j->maxdist, j->seedlength);
-    hleft = vsa_ed_fronts(&ls, lf, j->bytewise);
-    hright = vsa_ed_fronts(&rs, rf, j->bytewise);
-    if (vsa_ed_choose(j->ev, &ls, &rs, self, m->dbstart, pos2, m->length,
-                      j->leastlength, lf, hleft, rf, hright, &best))
-    {
-      vsa_ed_record(m, self, pos2, &best, j->out + i);
-      j->keep[i] = 1;
-    }
-  }
-  free(lf);
-  return NULL;
+  return vsa_exthost_dopiece(piece, extendseed);
 }
 
 int vsa_extend_edist_host(const vsa_sinkparams *layout, const uint8_t *text,
@@ -110,9 +65,6 @@ int vsa_extend_edist_host(const vsa_sinkparams *layout, const uint8_t *text,
                           vsa_match *matches, uint64_t capacity,
                           uint64_t *numofmatches)
 {
-  enum { MAXTHREADS = 256 };
-  pthread_t tid[MAXTHREADS];
-  Piece piece[MAXTHREADS];
   vsa_evalues ev;
   vsa_selrules evrules;
   Job job;
@@ -120,47 +72,21 @@ int vsa_extend_edist_host(const vsa_sinkparams *layout, const uint8_t *text,
   uint64_t *abs2 = NULL;
   double *hequot = NULL;
   const char *scalar = getenv("VSA_EXTEND_EDIST_SCALAR");
-  uint64_t i, kept = 0;
-  int t, nt, started = 0, rc = 0;
+  uint64_t i;
+  int rc = vsa_exthost_check(WHO, layout, text, querysymbols, seeds,
+                             numofseeds, leastlength, maxdist,
+                             VSA_EDIST_MAXDISTANCE, matches, capacity,
+                             numofmatches);
 
-  if (layout == NULL || text == NULL || numofmatches == NULL ||
-      (matches == NULL && capacity > 0))
+  if (rc != 0 || numofseeds == 0)
   {
-    return vsa_fail(-1, WHO ": NULL argument");
-  }
-  *numofmatches = 0;
-  if (vsa_list_check(WHO, NULL, seeds, numofseeds) != 0)
-  {
-    return -1;
-  }
-  if ((layout->kind != VSA_SINK_QUERY && layout->kind != VSA_SINK_SELF) ||
-      layout->totallength == 0 || layout->numofchars < 2 ||
-      (layout->kind == VSA_SINK_QUERY &&
-       (querysymbols == NULL ||
-        (layout->numofqueries > 0 &&
-         (layout->querystart == NULL || layout->querylength == NULL)))))
-  {
-    return vsa_fail(-2, WHO ": the seeds of a query layout "
-                    "(VSA_SINK_QUERY, with the query symbols) or of a self "
-                    "layout (VSA_SINK_SELF) are extended");
-  }
-  if (maxdist == 0 || maxdist > VSA_EDIST_MAXDISTANCE || leastlength == 0)
-  {
-    return vsa_fail(-2, WHO ": a least length and a distance bound from 1 "
-                    "to %u", (unsigned) VSA_EDIST_MAXDISTANCE);
-  }
-  if (numofseeds == 0)
-  {
-    return 0;
+    return rc;
   }
   vsa_evalues_init(&ev, layout->numofchars);
   memset(&evrules, 0, sizeof evrules);
   memset(&job, 0, sizeof job);
-  job.out = (vsa_match *) malloc(numofseeds * sizeof *job.out);
-  job.keep = (uint8_t *) malloc(numofseeds);
   hequot = (double *) malloc((maxdist + 1) * sizeof *hequot);
-  if (vsa_evalues_extend(&ev, (int64_t) maxdist) != 0 || job.out == NULL ||
-      job.keep == NULL || hequot == NULL)
+  if (vsa_evalues_extend(&ev, (int64_t) maxdist) != 0 || hequot == NULL)
   {
     rc = vsa_fail(-101, "out of memory");
     goto done;
@@ -213,75 +139,19 @@ int vsa_extend_edist_host(const vsa_sinkparams *layout, const uint8_t *text,
   evrules.linestart = ev.linestart;
   evrules.hequot = hequot;
   evrules.nlines = (int64_t) maxdist + 1;
-  job.layout = layout;
   job.text = text;
-  job.seeds = seeds;
+  job.n = layout->totallength;
+  job.self = layout->kind == VSA_SINK_SELF;
   job.leastlength = leastlength;
   job.maxdist = maxdist;
   job.seedlength = vsa_ext_seedlength(leastlength, maxdist, seedlength);
   job.bytewise = scalar != NULL && *scalar != '\0' && *scalar != '0';
   job.ev = &evrules;
-  nt = threads > 0 ? threads : (int) sysconf(_SC_NPROCESSORS_ONLN);
-  nt = nt < 1 ? 1 : nt > MAXTHREADS ? MAXTHREADS : nt;
-  if ((uint64_t) nt > (numofseeds + 63) / 64)
-  {
-    nt = (int) ((numofseeds + 63) / 64);
-  }
-  for (t = 0; t < nt; t++)
-  {
-    piece[t].job = &job;
-    piece[t].first = numofseeds * (uint64_t) t / (uint64_t) nt;
-    piece[t].last = numofseeds * (uint64_t) (t + 1) / (uint64_t) nt;
-    piece[t].misfit = -1;
-    piece[t].nomem = 0;
-  }
-  for (t = 1; t < nt; t++)
-  {
-    if (pthread_create(tid + t, NULL, extendpiece, piece + t) != 0)
-    {
-      break;
-    }
-    started = t;
-  }
-  (void) extendpiece(piece);
-  for (t = started + 1; t < nt; t++) /* the pieces no thread took */
-  {
-    (void) extendpiece(piece + t);
-  }
-  for (t = 1; t <= started; t++)
-  {
-    (void) pthread_join(tid[t], NULL);
-  }
-  for (t = 0; t < nt && rc == 0; t++)
-  {
-    if (piece[t].nomem)
-    {
-      rc = vsa_fail(-101, "out of memory");
-    } else if (piece[t].misfit >= 0)
-    {
-      rc = vsa_list_misfit(WHO, (uint64_t) piece[t].misfit);
-    }
-  }
-  for (i = 0; i < numofseeds && rc == 0; i++)
-  {
-    if (job.keep[i])
-    {
-      if (kept == capacity)
-      {
-        rc = vsa_fail(-3, WHO ": more than %lu matches",
-                      (unsigned long) capacity);
-        break;
-      }
-      matches[kept++] = job.out[i];
-    }
-  }
-  if (rc == 0)
-  {
-    *numofmatches = kept;
-  }
+  rc = vsa_exthost_extend(WHO, layout, seeds, numofseeds, threads, 64,
+                          extendpiece, &job,
+                          2 * vsa_ed_frontwords(maxdist) * sizeof(uint64_t),
+                          matches, capacity, numofmatches);
 done:
-  free(job.out);
-  free(job.keep);
   free(hequot);
   free(seq2);
   free(abs2);
