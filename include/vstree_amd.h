@@ -1882,8 +1882,42 @@ uint64_t vsa_extend_seedlength(uint64_t leastlength, uint64_t maxdist,
    wavefront */
 #define VSA_EXTEND_EDIST_MAXDIST 31u
 
+/* ---- X-drop extension: vmatch -l L -hxdrop X | -exdrop X [-seedlength S] [-p]
+   [-q Q] IDX.  The same seeds, of length S (30 if none is given), each
+   extended to the left and right until the score -- match +2, mismatch -1,
+   with -exdrop insertion and deletion -2 -- falls X below the best one seen
+   (xdropseedextend, Vmengine/xdropext.c:39-221); one match per seed, kept if
+   both instances have L symbols.  No distance bound exists, and the two
+   lengths differ freely, so the record carries
+     length      length1 in bits 0-31, length2 in bits 32-63
+     querystart  bits 0-31 the position in the query sequence (0 in a self
+                 layout), bits 32-63 the magnitude of the distance; the kind
+                 gives its sign: negative for -hxdrop, positive for -exdrop
+   dbstart = position1; queryseq as for -e K.  Texts and query sequences of
+   2^32 - 16 symbols or more are VSA_NOT_COVERED on every entry.  The entries
+   are declared in vstree_amd_xdrop.h, which this header includes. */
+#define VSA_XDROP_MAXDROP 255u /* FLAGXDROP, Vmatch/parsevm.c:974-990 */
+#define VSA_XDROP_LENGTH1(lengthfield) ((uint64_t) (lengthfield) & 0xFFFFFFFFull)
+#define VSA_XDROP_LENGTH2(lengthfield) ((uint64_t) (lengthfield) >> 32)
+#define VSA_XDROP_PACKLENGTHS(length1, length2) \
+  ((uint64_t) (length1) | (uint64_t) (length2) << 32)
+#define VSA_XDROP_START(startfield) ((uint64_t) (startfield) & 0xFFFFFFFFull)
+#define VSA_XDROP_DISTANCE(startfield) ((uint64_t) (startfield) >> 32)
+#define VSA_XDROP_PACKSTART(start, distance) \
+  ((uint64_t) (start) | (uint64_t) (distance) << 32)
+
+/* layouts of such lists for the sink: the lines of vmatch -l L -hxdrop X and
+   -l L -exdrop X with -q Q (with palindromic: of the -p pass) and without,
+   byte for byte; the post-processing handles answer VSA_NOT_COVERED for them
+   as for the other kinds of extended seeds */
+#define VSA_SINK_QUERY_HXDROP 12
+#define VSA_SINK_SELF_HXDROP  13
+#define VSA_SINK_QUERY_EXDROP 14
+#define VSA_SINK_SELF_EXDROP  15
+
 #ifdef __cplusplus
 }
 #endif
 #include "vstree_amd_edist.h"
+#include "vstree_amd_xdrop.h"
 #endif

@@ -446,13 +446,26 @@ def _load():
         "vsa_findselfmatches_edist": sig["vsa_findselfmatches_hamming"],
         "vsa_extend_edist_host": sig["vsa_extend_hamming_host"],
     }
-    for name, (res, args) in list(sig.items()) + list(edist.items()):
+    # the entries of include/vstree_amd_xdrop.h: the flag `hamming` follows
+    # the bound X
+    xdrop = {
+        "vsa_extend_xdrop_seedlength": (U64, [U64]),
+        "vsa_extend_xdrop": (I, [V, V, V, C.POINTER(SinkParams), I, U64, U64,
+                                 I, U64, PP]),
+        "vsa_findquerymatches_xdrop": (I, [V, V, U64, U64, I, U64, I, PP]),
+        "vsa_findselfmatches_xdrop": (I, [V, U64, U64, I, U64, PP]),
+        "vsa_extend_xdrop_host": (I, [C.POINTER(SinkParams), V, V, V, U64,
+                                      U64, U64, I, U64, I, V, U64,
+                                      C.POINTER(U64)]),
+    }
+    for name, (res, args) in list(sig.items()) + list(edist.items()) + \
+            list(xdrop.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    return lib, sorted(sig), sorted(edist)
+    return lib, sorted(sig), sorted(edist), sorted(xdrop)
 
 
-lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS = _load()
+lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS, XDROP_ABI_SYMBOLS = _load()
 
 
 def messagespace():
@@ -2055,41 +2068,50 @@ def extend_seedlength(leastlength, maxdist, seedlength=0):
                                          int(seedlength)))
 
 
-def _extension(kind, docs):
+def _extension(kind, docs, flag=None):
     """the four wrappers of one kind of extension of exact seeds, `kind` as in
     the names of its entries: (extend_KIND, findquerymatches_KIND,
-    findselfmatches_KIND, extend_KIND_host) with the docstrings `docs`"""
+    findselfmatches_KIND, extend_KIND_host) with the docstrings `docs`.
+    flag: the name of a keyword argument every wrapper requires, a truth
+    value that follows the bound in the entries of the kind"""
+    def own(kw):
+        if set(kw) != ({flag} if flag else set()):
+            raise TypeError("%s: keyword arguments %s" % (
+                kind, sorted(kw) if not flag else "need `%s` only" % flag))
+        return tuple(int(bool(v)) for v in kw.values())
+
     c_extend = getattr(lib, "vsa_extend_" + kind)
     c_query = getattr(lib, "vsa_findquerymatches_" + kind)
     c_self = getattr(lib, "vsa_findselfmatches_" + kind)
     c_host = getattr(lib, "vsa_extend_%s_host" % kind)
 
     def extend(index, queries, seeds, leastlength, maxdist, seedlength=0,
-               palindromic=False):
+               palindromic=False, **kw):
         p = SinkParams()
         p.kind = SINK_SELF if queries is None else SINK_QUERY
         h = C.c_void_p()
         _check(c_extend(index._h, None if queries is None else queries._h,
                         seeds._h, C.byref(p), int(bool(palindromic)),
-                        int(leastlength), int(maxdist), int(seedlength),
-                        C.byref(h)))
+                        int(leastlength), int(maxdist), *own(kw),
+                        int(seedlength), C.byref(h)))
         return Result(h)
 
     def findquerymatches(index, queries, leastlength, maxdist, seedlength=0,
-                         palindromic=False):
+                         palindromic=False, **kw):
         h = C.c_void_p()
         _check(c_query(index._h, queries._h, int(leastlength), int(maxdist),
-                       int(seedlength), int(bool(palindromic)), C.byref(h)))
+                       *own(kw), int(seedlength), int(bool(palindromic)),
+                       C.byref(h)))
         return Result(h)
 
-    def findselfmatches(index, leastlength, maxdist, seedlength=0):
+    def findselfmatches(index, leastlength, maxdist, seedlength=0, **kw):
         h = C.c_void_p()
-        _check(c_self(index._h, int(leastlength), int(maxdist),
+        _check(c_self(index._h, int(leastlength), int(maxdist), *own(kw),
                       int(seedlength), C.byref(h)))
         return Result(h)
 
     def extend_host(text, seeds, leastlength, maxdist, seedlength=0,
-                    queries=None, numofchars=4, threads=0):
+                    queries=None, numofchars=4, threads=0, **kw):
         text = np.ascontiguousarray(text, np.uint8)
         seeds = np.ascontiguousarray(seeds, MATCH_DTYPE)
         p, keep = sink_params(
@@ -2102,7 +2124,7 @@ def _extension(kind, docs):
         out = np.zeros(len(seeds), MATCH_DTYPE)
         n = C.c_uint64()
         _check(c_host(C.byref(p), _ptr(text), _ptr(qsym), _ptr(seeds),
-                      len(seeds), int(leastlength), int(maxdist),
+                      len(seeds), int(leastlength), int(maxdist), *own(kw),
                       int(seedlength), int(threads), _ptr(out), len(out),
                       C.byref(n)))
         return out[:n.value]
@@ -2166,3 +2188,46 @@ def edist_pack(length1, length2, distance):
      """vmatch -l L -e K [-seedlength S] IDX""",
      """the same extension on the host, any distance bound the record carries;
     arguments as for extend_hamming_host"""))
+
+
+# ---- X-drop extension: vmatch -l L -hxdrop X | -exdrop X [-seedlength S] -----
+# (include/vstree_amd_xdrop.h; the record: length1 in bits 0-31 of the length,
+# length2 above; the start in the query sequence in bits 0-31 of querystart,
+# the magnitude of the distance above -- negative for -hxdrop)
+
+SINK_QUERY_HXDROP, SINK_SELF_HXDROP, SINK_QUERY_EXDROP, SINK_SELF_EXDROP = \
+    12, 13, 14, 15
+XDROP_MAXDROP = 255
+
+
+def xdrop_lengths1(matches):
+    return matches["length"] & np.uint64(0xFFFFFFFF)
+
+
+def xdrop_lengths2(matches):
+    return matches["length"] >> np.uint64(32)
+
+
+def xdrop_starts(matches):
+    return matches["querystart"] & np.uint64(0xFFFFFFFF)
+
+
+def xdrop_distances(matches):
+    """the magnitudes; the kind gives the sign"""
+    return matches["querystart"] >> np.uint64(32)
+
+
+def extend_xdrop_seedlength(seedlength=0):
+    """S, or 30 (Vmatch/matchlenparm.c:40-46)"""
+    return int(lib.vsa_extend_xdrop_seedlength(int(seedlength)))
+
+
+(extend_xdrop, findquerymatches_xdrop, findselfmatches_xdrop,
+ extend_xdrop_host) = _extension("xdrop", (
+     """xdropseedextend (Vmengine/xdropext.c:39) for every seed of a Result;
+    arguments as for extend_hamming with X for the bound, and hamming=True
+    for -hxdrop, False for -exdrop""",
+     """vmatch -l L -hxdrop X | -exdrop X [-seedlength S] [-p] -q Q IDX""",
+     """vmatch -l L -hxdrop X | -exdrop X [-seedlength S] IDX""",
+     """the same extension on the host; arguments as for extend_hamming_host
+    and hamming as above"""), flag="hamming")

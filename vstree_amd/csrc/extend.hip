@@ -311,10 +311,19 @@ k_ext_choose(ExtParams p, vsa_selrules ev, vsa_match *__restrict__ out,
 struct Hamming
 {
   static constexpr uint32_t cap = VSA_EXTEND_MAXDIST;
-  static constexpr bool hequot = false;
+  static constexpr bool evalues = true, hequot = false;
   static void hosttakes(char *buf, size_t n)
   {
     snprintf(buf, n, "vsa_extend_hamming_host takes any");
+  }
+  static int checkbound(const char *who, uint64_t maxdist)
+  {
+    return capbound<Hamming>(who, maxdist);
+  }
+  static uint64_t seedlength(uint64_t leastlength, uint64_t maxdist,
+                             uint64_t seedlength)
+  {
+    return vsa_ext_seedlength(leastlength, maxdist, seedlength);
   }
 
   struct Stage

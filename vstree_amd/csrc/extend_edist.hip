@@ -4,9 +4,9 @@
 // kurtz/extendED.c:78-355).  The rules are extend_edist_rules.h's, which
 // extend_edist_host.c reads too; here is how the fronts are made.
 //
-//   flatten k_ed_flatten: the query batch as the reference's Multiseq, one
-//           array with a separator between two sequences (the rules say why
-//           the fronts need it), one wavefront per sequence.
+//   flatten k_flatten (extend_flat.hpp): the query batch as the reference's
+//           Multiseq, one array with a separator between two sequences (the
+//           rules say why the fronts need it), one wavefront per sequence.
 //   fronts  k_ed_fronts<W>: one group of W = 16, 32 or 64 lanes per (seed,
 //           side), chosen by 2 K + 1; lane l is the diagonal l - K.  Per
 //           front: the rows of the neighbouring diagonals by shuffles, the
@@ -43,6 +43,8 @@ namespace
 // counts the sides with a slide the group finished, EXT_SUMLENGTH sums
 // length1 of the matches
 #include "extend_shared.hpp"
+// the query Multiseq (k_flatten)
+#include "extend_flat.hpp"
 
 #define ED_MISFIT 0xFFFFFFFFu
 #define ED_BLOCK 256
@@ -68,18 +70,6 @@ struct EdParams
   unsigned long long *counters;
 };
 
-__device__ __forceinline__ uint64_t ed_qlength(const DevQueries &q, uint64_t i)
-{
-  return q.uniformlen != 0 ? q.uniformlen : q.length[i];
-}
-
-// where sequence i of the batch begins in the query Multiseq
-__device__ __forceinline__ uint64_t ed_qabs(const EdParams &p, uint64_t i)
-{
-  return p.q.uniformlen != 0 ? i * ((uint64_t) p.q.uniformlen + 1)
-                             : p.abs2[i];
-}
-
 // the place of a seed in the second Multiseq; false: it does not fit
 __device__ __forceinline__ bool ed_place(const EdParams &p, const vsa_match &m,
                                          uint64_t &pos2)
@@ -98,33 +88,9 @@ __device__ __forceinline__ bool ed_place(const EdParams &p, const vsa_match &m,
   {
     return false;
   }
-  const uint64_t qlen = ed_qlength(p.q, q);
-  pos2 = ed_qabs(p, q) + m.querystart;
+  const uint64_t qlen = flat_qlength(p, q);
+  pos2 = flat_qabs(p, q) + m.querystart;
   return m.querystart <= qlen && m.length <= qlen - m.querystart;
-}
-
-__global__ void __launch_bounds__(ED_BLOCK)
-k_ed_flatten(EdParams p, uint8_t *__restrict__ out)
-{
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t nwaves = vsa_nblocks() * (ED_BLOCK / 64);
-
-  for (uint64_t i = vsa_bid() * (ED_BLOCK / 64) + (threadIdx.x >> 6);
-       i < p.q.nq; i += nwaves)
-  {
-    const uint64_t len = ed_qlength(p.q, i);
-    const uint8_t *src =
-        p.q.symbols + (p.q.dense ? i * p.q.uniformlen : p.q.start[i]);
-    uint8_t *dst = out + ed_qabs(p, i);
-    for (uint64_t x = lane; x < len; x += 64)
-    {
-      dst[x] = src[x];
-    }
-    if (lane == 0 && i + 1 < p.q.nq)
-    {
-      dst[len] = (uint8_t) VSA_SEPARATOR;
-    }
-  }
 }
 
 // the marks of the words at offset `at` of a slide from (t, t + k) of which
@@ -459,11 +425,20 @@ int launchfronts(const EdParams &p)
 struct Edist
 {
   static constexpr uint32_t cap = VSA_EXTEND_EDIST_MAXDIST;
-  static constexpr bool hequot = true;
+  static constexpr bool evalues = true, hequot = true;
   static void hosttakes(char *buf, size_t n)
   {
     snprintf(buf, n, "vsa_extend_edist_host takes up to %u",
              VSA_EDIST_MAXDISTANCE);
+  }
+  static int checkbound(const char *who, uint64_t maxdist)
+  {
+    return capbound<Edist>(who, maxdist);
+  }
+  static uint64_t seedlength(uint64_t leastlength, uint64_t maxdist,
+                             uint64_t seedlength)
+  {
+    return vsa_ext_seedlength(leastlength, maxdist, seedlength);
   }
 
   struct Stage
@@ -492,44 +467,11 @@ struct Edist
         p.n2 = p.n1;
       } else
       {
-        p.q = devqueries(c.queries);
-        const uint64_t nq = c.queries->nq;
-        uint64_t total = 0;
-        if (p.q.uniformlen != 0)
+        const int rc = flatten_batch(c.who, c.queries, p, flat, abs2);
+        if (rc != 0)
         {
-          total = nq * ((uint64_t) p.q.uniformlen + 1) - (nq > 0 ? 1 : 0);
-        } else
-        {
-          if (c.queries->hlength.size() != nq)
-          {
-            VSA_ERROR("%s: the batch has no host copy of its lengths", c.who);
-            return -2;
-          }
-          std::vector<uint64_t> starts(nq);
-          for (uint64_t i = 0; i < nq; i++)
-          {
-            starts[i] = total + (i > 0 ? 1 : 0);
-            total = starts[i] + c.queries->hlength[i];
-          }
-          if (abs2.alloc(nq * 8) != 0)
-          {
-            return -100;
-          }
-          VSA_HIP(hipMemcpy(abs2.p, starts.data(), nq * 8,
-                            hipMemcpyHostToDevice));
-          p.abs2 = abs2.as<uint64_t>();
+          return rc;
         }
-        if (flat.alloc(total + 16) != 0)
-        {
-          return -100;
-        }
-        const uint64_t blocks = std::min<uint64_t>(
-            (nq + ED_BLOCK / 64 - 1) / (ED_BLOCK / 64), 65536);
-        k_ed_flatten<<<vsa_grid(blocks), ED_BLOCK, 0, nullptr>>>(
-            p, flat.as<uint8_t>());
-        VSA_HIP(hipGetLastError());
-        p.s2 = flat.as<uint8_t>();
-        p.n2 = total;
       }
       const uint64_t words = vsa_ed_frontwords(c.maxdist);
       piece = std::min<uint64_t>(

@@ -78,7 +78,8 @@ static inline int vsa_exthost_fits(const vsa_sinkparams *lay,
 }
 
 /* the worker of a kind for one seed that fits: scratch is the thread's own,
-   `where` what vsa_exthost_fits gave; 1 and the match in *out, or 0 */
+   `where` what vsa_exthost_fits gave; 1 and the match in *out, or 0 (below
+   0: out of memory) */
 typedef int vsa_exthost_seed(const void *job, void *scratch,
                              const vsa_match *m, uint64_t where,
                              vsa_match *out);
@@ -126,8 +127,13 @@ static inline void *vsa_exthost_dopiece(void *arg, vsa_exthost_seed *seed)
       p->misfit = (int64_t) i;
       break;
     }
-    r->keep[i] = (uint8_t) seed(r->job, scratch, r->seeds + i, where,
-                                r->out + i);
+    const int kept = seed(r->job, scratch, r->seeds + i, where, r->out + i);
+    if (kept < 0) /* the worker found no memory of its own */
+    {
+      p->nomem = 1;
+      break;
+    }
+    r->keep[i] = (uint8_t) kept;
   }
   free(scratch);
   return NULL;

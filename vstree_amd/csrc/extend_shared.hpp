@@ -1,5 +1,6 @@
-// The driver of the two extensions of exact seeds (extend.hip: -h K,
-// extend_edist.hip: -e K), stated ONCE: what an entry refuses, the seed list
+// The driver of the extensions of exact seeds (extend.hip: -h K,
+// extend_edist.hip: -e K, extend_xdrop.hip: -hxdrop X / -exdrop X), stated
+// ONCE: what an entry refuses, the seed list
 // it takes, the result it keeps, the E-value table on the device, the stable
 // compaction of the kept records and the three forms of an entry -- a seed
 // list, the seeds of a query batch, the seeds of the index against itself.
@@ -7,11 +8,15 @@
 // tile_compact.inc and the rules, so there is no object file and no symbol
 // of its own.  A unit defines its kind, a struct with
 //
-//   cap                 the largest distance bound of the device path
-//   hosttakes(buf, n)   what the refusal of a larger bound says of the host
-//                       entry, "vsa_..._host takes ..."
-//   hequot              do the factors of the edit distances go up with the
-//                       E-value table?
+//   cap                 the largest bound (distance, or X) of the device path
+//   checkbound(who, b)  what the kind refuses of a bound b >= 1; a kind whose
+//                       device path has a cap below what its host entry takes
+//                       answers capbound<Kind>, which says so through
+//   hosttakes(buf, n)   "vsa_..._host takes ..."
+//   seedlength(L, b, S) the seed length rule of the kind
+//   evalues             does the choice of the kind read the E-value table
+//                       (is it made and uploaded)?
+//   hequot              do the factors of the edit distances go up with it?
 //   Stage               the scratch and the kernels between the seed list and
 //                       the kept records, with
 //     prepare(c, tall)            what comes before the buffers of the driver
@@ -86,9 +91,25 @@ struct ExtCall
   const vsa_result *seeds;    // count > 0
   int self;
   uint64_t leastlength, maxdist;
-  uint64_t seedlength; // vsa_ext_seedlength of the call
-  vsa_selrules ev;     // the E-value table up to line maxdist
+  uint64_t seedlength; // by the seed length rule of the kind
+  vsa_selrules ev;     // the E-value table up to line maxdist, where the
+                       // kind reads one
 };
+
+// a bound above the cap of the device path, where the host entry takes more
+template <class Kind>
+int capbound(const char *who, uint64_t maxdist)
+{
+  if (maxdist > Kind::cap)
+  {
+    char host[64];
+    Kind::hosttakes(host, sizeof host);
+    VSA_ERROR("%s: distance bound %lu: up to %u are covered on the device "
+              "(%s)", who, (unsigned long) maxdist, Kind::cap, host);
+    return VSA_NOT_COVERED;
+  }
+  return 0;
+}
 
 // what every entry refuses before anything is run or kept
 template <class Kind>
@@ -101,13 +122,10 @@ int checkbounds(const char *who, const vsa_index *index,
     VSA_ERROR("%s: a least length and a distance bound of at least 1", who);
     return -2;
   }
-  if (maxdist > Kind::cap)
+  const int rc = Kind::checkbound(who, maxdist);
+  if (rc != 0)
   {
-    char host[64];
-    Kind::hosttakes(host, sizeof host);
-    VSA_ERROR("%s: distance bound %lu: up to %u are covered on the device "
-              "(%s)", who, (unsigned long) maxdist, Kind::cap, host);
-    return VSA_NOT_COVERED;
+    return rc;
   }
   if (index->n >= 0xFFFFFFF0ull ||
       (queries != nullptr && queries->maxlength >= 0xFFFFFFF0ull))
@@ -123,6 +141,54 @@ int checkbounds(const char *who, const vsa_index *index,
     return -2;
   }
   return 0;
+}
+
+// the E-value table up to line K on the device, with the factors of the edit
+// distances where the kind reads them (kurtz/evalues.c:315-420), as the sink
+// and the selection make them
+template <class Kind>
+int evaluetable(const char *who, const vsa_index *index, uint64_t maxdist,
+                DevBuf &dtable, DevBuf &dlines, DevBuf &dquot,
+                vsa_selrules &ev)
+{
+  vsa_evalues hev;
+  vsa_evalues_init(&hev, index->numofchars);
+  if (vsa_evalues_extend(&hev, (int64_t) maxdist) != 0)
+  {
+    vsa_evalues_free(&hev);
+    VSA_ERROR("out of memory");
+    return -101;
+  }
+  double hequot[Kind::cap + 1];
+  for (uint64_t d = 0; Kind::hequot && d <= maxdist; d++)
+  {
+    hequot[d] = vsa_evalues_hequot((int64_t) d);
+  }
+  const size_t tbytes = (size_t) hev.nexttab * 8,
+               lbytes = (size_t) (maxdist + 2) * 8,
+               qbytes = Kind::hequot ? (size_t) (maxdist + 1) * 8 : 0;
+  int rc = (dtable.alloc(tbytes) != 0 || dlines.alloc(lbytes) != 0 ||
+            (qbytes > 0 && dquot.alloc(qbytes) != 0))
+               ? -100
+               : 0;
+  if (rc == 0 &&
+      (hipMemcpy(dtable.p, hev.table, tbytes, hipMemcpyHostToDevice) !=
+           hipSuccess ||
+       hipMemcpy(dlines.p, hev.linestart, lbytes, hipMemcpyHostToDevice) !=
+           hipSuccess ||
+       (qbytes > 0 &&
+        hipMemcpy(dquot.p, hequot, qbytes, hipMemcpyHostToDevice) !=
+            hipSuccess)))
+  {
+    VSA_ERROR("%s: upload of the E-value table failed", who);
+    rc = -100;
+  }
+  vsa_evalues_free(&hev);
+  ev.table = dtable.as<double>();
+  ev.linestart = dlines.as<int64_t>();
+  ev.hequot = dquot.as<double>();
+  ev.nlines = (int64_t) maxdist + 1;
+  return rc;
 }
 
 // the seeds of `seeds` extended in the index and -- self == 0 -- in the batch
@@ -173,49 +239,19 @@ int extend(const char *who, const vsa_index *index,
   {
     return -100;
   }
-  // the E-value table up to line K, with the factors of the edit distances
-  // where the kind reads them (kurtz/evalues.c:315-420), as the sink and the
-  // selection make them
-  vsa_evalues hev;
-  vsa_evalues_init(&hev, index->numofchars);
-  if (vsa_evalues_extend(&hev, (int64_t) maxdist) != 0)
-  {
-    vsa_evalues_free(&hev);
-    VSA_ERROR("out of memory");
-    return -101;
-  }
-  double hequot[Kind::cap + 1];
-  for (uint64_t d = 0; Kind::hequot && d <= maxdist; d++)
-  {
-    hequot[d] = vsa_evalues_hequot((int64_t) d);
-  }
   DevBuf dtable, dlines, dquot;
-  const size_t tbytes = (size_t) hev.nexttab * 8,
-               lbytes = (size_t) (maxdist + 2) * 8,
-               qbytes = Kind::hequot ? (size_t) (maxdist + 1) * 8 : 0;
-  int rc = (dtable.alloc(tbytes) != 0 || dlines.alloc(lbytes) != 0 ||
-            (qbytes > 0 && dquot.alloc(qbytes) != 0))
-               ? -100
-               : 0;
-  if (rc == 0 &&
-      (hipMemcpy(dtable.p, hev.table, tbytes, hipMemcpyHostToDevice) !=
-           hipSuccess ||
-       hipMemcpy(dlines.p, hev.linestart, lbytes, hipMemcpyHostToDevice) !=
-           hipSuccess ||
-       (qbytes > 0 &&
-        hipMemcpy(dquot.p, hequot, qbytes, hipMemcpyHostToDevice) !=
-            hipSuccess)))
-  {
-    VSA_ERROR("%s: upload of the E-value table failed", who);
-    rc = -100;
-  }
-  vsa_evalues_free(&hev);
-  if (rc != 0)
-  {
-    return rc;
-  }
   ExtCall c;
   memset(&c, 0, sizeof c);
+  if (Kind::evalues)
+  {
+    const int rc = evaluetable<Kind>(who, index, maxdist, dtable, dlines,
+                                     dquot, c.ev);
+    if (rc != 0)
+    {
+      return rc;
+    }
+  }
+  int rc = 0;
   c.who = who;
   c.index = index;
   c.queries = queries;
@@ -223,11 +259,7 @@ int extend(const char *who, const vsa_index *index,
   c.self = self;
   c.leastlength = leastlength;
   c.maxdist = maxdist;
-  c.seedlength = vsa_ext_seedlength(leastlength, maxdist, seedlength);
-  c.ev.table = dtable.as<double>();
-  c.ev.linestart = dlines.as<int64_t>();
-  c.ev.hequot = dquot.as<double>();
-  c.ev.nlines = (int64_t) maxdist + 1;
+  c.seedlength = Kind::seedlength(leastlength, maxdist, seedlength);
 
   const uint64_t nseeds = seeds->count;
   typename Kind::Stage stage;
@@ -364,7 +396,7 @@ int extend_queries(const char *who, const vsa_index *index,
         vsa_result *seeds = nullptr;
         int rc = vsa_findquerymatches(
             index, batch, 0, 0,
-            vsa_ext_seedlength(leastlength, maxdist, seedlength), &seeds);
+            Kind::seedlength(leastlength, maxdist, seedlength), &seeds);
         if (rc == 0)
         {
           rc = extend<Kind>(who, index, batch, seeds, 0, leastlength, maxdist,
@@ -393,7 +425,7 @@ int extend_self(const char *who, const vsa_index *index, uint64_t leastlength,
   }
   vsa_result *seeds = nullptr;
   rc = vsa_findmaximalrepeats(
-      index, vsa_ext_seedlength(leastlength, maxdist, seedlength), &seeds);
+      index, Kind::seedlength(leastlength, maxdist, seedlength), &seeds);
   if (rc == 0)
   {
     rc = extend<Kind>(who, index, nullptr, seeds, 1, leastlength, maxdist,

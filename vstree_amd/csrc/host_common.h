@@ -132,6 +132,14 @@ static inline int vsa_layout_view(const vsa_sinkparams *layout,
                     "VSA_SINK_QUERY_EDIST, VSA_SINK_SELF_EDIST) are not "
                     "covered", who);
   }
+  if (layout->kind >= VSA_SINK_QUERY_HXDROP &&
+      layout->kind <= VSA_SINK_SELF_EXDROP)
+  {
+    return vsa_fail(VSA_NOT_COVERED, "%s: lists of extended seeds "
+                    "(VSA_SINK_QUERY_HXDROP, VSA_SINK_SELF_HXDROP, "
+                    "VSA_SINK_QUERY_EXDROP, VSA_SINK_SELF_EXDROP) are not "
+                    "covered", who);
+  }
   if (layout->kind < VSA_SINK_COMPLETE ||
       layout->kind > VSA_SINK_APPROX_HAMMING || layout->totallength == 0 ||
       layout->totalquerylength + 1 > layout->totallength ||

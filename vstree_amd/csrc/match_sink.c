@@ -46,7 +46,16 @@ static const double averagequot[] = {
 
 #define ISSELF(kind) \
   ((kind) == VSA_SINK_SELF || (kind) == VSA_SINK_SELF_HAMMING || \
-   (kind) == VSA_SINK_SELF_EDIST)
+   (kind) == VSA_SINK_SELF_EDIST || (kind) == VSA_SINK_SELF_HXDROP || \
+   (kind) == VSA_SINK_SELF_EXDROP)
+/* X-drop extended seeds: both lengths in the length, the magnitude of the
+   distance above the start in the query sequence (xdropext.c:202-217) */
+#define ISXDROP(kind) \
+  ((kind) >= VSA_SINK_QUERY_HXDROP && (kind) <= VSA_SINK_SELF_EXDROP)
+#define XDROPDISTANCE(kind, m) \
+  (((kind) == VSA_SINK_QUERY_HXDROP || (kind) == VSA_SINK_SELF_HXDROP) \
+       ? -(int64_t) VSA_XDROP_DISTANCE((m)->querystart) \
+       : (int64_t) VSA_XDROP_DISTANCE((m)->querystart))
 
 typedef vsa_evalues Evalues; /* evalues.h: shared with select_host.c */
 
@@ -433,6 +442,7 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
      (editextend stores dist, kurtz/extendED.c:321) */
   const int isedist = s->p.kind == VSA_SINK_QUERY_EDIST ||
                       s->p.kind == VSA_SINK_SELF_EDIST;
+  const int isxdrop = ISXDROP(s->p.kind);
   const int iscomplete = s->p.kind == VSA_SINK_COMPLETE ||
                          s->p.kind == VSA_SINK_APPROX_EDIST ||
                          s->p.kind == VSA_SINK_APPROX_HAMMING ||
@@ -441,6 +451,7 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   position1 = m->dbstart;
   length1 = isextended ? VSA_HAMMING_LENGTH(m->length)
             : isedist  ? VSA_EDIST_LENGTH1(m->length)
+            : isxdrop  ? VSA_XDROP_LENGTH1(m->length)
                        : m->length;
   seqinfo(s, position1, &seqnum1, &start1, &len1seq);
   if (isquery)
@@ -472,6 +483,11 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
       length2 = VSA_EDIST_LENGTH2(m->length);
       relpos2 = m->querystart;
       distance = (int64_t) VSA_EDIST_DISTANCE(m->length);
+    } else if (isxdrop)
+    {
+      length2 = VSA_XDROP_LENGTH2(m->length);
+      relpos2 = VSA_XDROP_START(m->querystart);
+      distance = XDROPDISTANCE(s->p.kind, m);
     } else if (s->p.kind == VSA_SINK_QUERY || isextended)
     {
       /* hammingextend stores the negative (kurtz/extendHD.c:345) */
@@ -504,9 +520,12 @@ static char *formatmatch(const vsa_sink *s, Fcache *cache,
   {
     /* self match: (length, start1, start2), Vmengine/fself.c:95-125 */
     uint64_t start2, len2seq;
-    length2 = isedist ? VSA_EDIST_LENGTH2(m->length) : length1;
+    length2 = isedist   ? VSA_EDIST_LENGTH2(m->length)
+              : isxdrop ? VSA_XDROP_LENGTH2(m->length)
+                        : length1;
     distance = isextended ? -(int64_t) VSA_HAMMING_DISTANCE(m->length)
                : isedist  ? (int64_t) VSA_EDIST_DISTANCE(m->length)
+               : isxdrop  ? XDROPDISTANCE(s->p.kind, m)
                           : 0;
     seqinfo(s, m->queryseq, &seqnum2, &start2, &len2seq);
     relpos2 = m->queryseq - start2;
@@ -680,6 +699,16 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
       if (VSA_EDIST_DISTANCE(matches[i].length) > maxd)
       {
         maxd = VSA_EDIST_DISTANCE(matches[i].length);
+      }
+    }
+  }
+  if (ISXDROP(s->p.kind))
+  {
+    for (i = 0; i < n; i++)
+    {
+      if (VSA_XDROP_DISTANCE(matches[i].querystart) > maxd)
+      {
+        maxd = VSA_XDROP_DISTANCE(matches[i].querystart);
       }
     }
   }
