@@ -619,6 +619,13 @@ int vsa_findtandems_cb(const vsa_index *index, uint64_t searchlength,
    kurtz/cleanMUMcand.c:55-118 runs once, in vsa_pipeline_finish).  queryseq
    of a match counts over all batches (Vmengine/fquery.c:1010
    onlinequerynumoffset).
+   Jobs: vsa_pipeline_finish and vsa_pipeline_finish16 end a -mum job, also
+   when they report that a batch of it failed: the candidates are dropped and
+   the reads of the next job are numbered from 0 again.  Modes 0 to 2 have no
+   job end; their numbering goes on until vsa_pipeline_set_offset(p, 0).
+   VSA_PIPELINE_ROW_SLACK in the environment of vsa_pipeline_open (tests): the
+   device buffer of the -mum candidates grows to the rows it must hold and
+   that many more, instead of twice the rows and 2^20 more.
 
      vsa_pipeline_open(index, 3, 20, 100, 10000000, &p);
      while (more reads) {
@@ -679,7 +686,8 @@ void vsa_pipeline_close(vsa_pipeline *pipeline);
    taken): the candidate rows of the job where they lie in device memory -- 16
    bytes each, sort key dbstart << lengthbits | (2^lengthbits - 1 - length) and
    value queryseq << 16 | querystart, valid until the next batch is submitted
-   -- instead of vsa_pipeline_finish; ends the job.
+   -- instead of vsa_pipeline_finish; ends the job, but leaves the numbering
+   of the next one to the caller (vsa_pipeline_set_offset).
    vsa_rows_partition_device: such rows grouped by the range of the index
    their dbstart falls into, like vsa_result_partition_device (same stream
    contract: the device's default stream). */

@@ -134,7 +134,10 @@ int vsa_multi_findmatches_device(vsa_multi *multi, int mode,
   list r (ascending dbstart; the lists in replica order are the reference's
   list) in page-locked host memory that stays valid until the next finish or
   close: lists[r], counts[r] for r < vsa_multi_ndevices.  The counters of the
-  job take the one ncclAllReduce.
+  job take the one ncclAllReduce.  While a submitted batch has not been taken
+  with vsa_multi_pipeline_next the call is refused (-1) and changes nothing:
+  take the batches, call it again.  It ends the job; the reads of the next
+  one are numbered from 0.
 */
 typedef struct vsa_multi_pipeline vsa_multi_pipeline;
 int vsa_multi_pipeline_open(vsa_multi *multi, int mode, uint64_t searchlength,

@@ -1541,6 +1541,13 @@ extern "C" int vsa_multi_pipeline_finish(vsa_multi_pipeline *p,
     lists[r] = nullptr;
     counts[r] = 0;
   }
+  if (!p->order.empty())
+  {
+    // (a replica with a batch outstanding would refuse to hand its rows over
+    // after the others have given theirs up: nothing is touched before)
+    seterror("vsa_multi_pipeline_finish: batches are still outstanding");
+    return -1;
+  }
   p->submitted = 0;
   p->batches = 0;
   // phase 1: every replica groups the candidates of its batches by range

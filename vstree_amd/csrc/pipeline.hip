@@ -91,6 +91,7 @@ struct vsa_pipeline
   // -mum: candidate rows (key, value) of all batches, one device buffer
   uint64_t *rows = nullptr;
   uint64_t nrows = 0, rowcap = 0, candidates = 0;
+  uint64_t rowslack = 0; // VSA_PIPELINE_ROW_SLACK (0: not set)
   vsa_match *hostmums = nullptr; // page-locked, kept between jobs
   uint64_t hostmumscap = 0;
   int failed = 0;
@@ -123,13 +124,24 @@ int growhost(Slot &s, uint64_t need)
   return 0;
 }
 
+// vsa_pipeline_finish, _finish16 and the report of a failed job end a -mum
+// job: no candidates are kept, the reads of the next job count from 0
+void endjob(vsa_pipeline *p)
+{
+  p->nrows = 0;
+  p->candidates = 0;
+  p->submitted = 0;
+}
+
 // candidate rows of one batch behind those of the batches before
 int keeprows(vsa_pipeline *p, vsa_result *res)
 {
   const uint64_t c = vsa_result_count(res);
   if (p->nrows + c > p->rowcap)
   {
-    const uint64_t cap = (p->nrows + c) * 2 + (1u << 20);
+    const uint64_t cap = p->rowslack != 0
+                             ? p->nrows + c + p->rowslack
+                             : (p->nrows + c) * 2 + (1u << 20);
     uint64_t *bigger = nullptr;
     if (vsa_hip_malloc((void **) &bigger, cap * 16) != hipSuccess)
     {
@@ -319,6 +331,12 @@ int pipeline_open(const vsa_index *index, int mode, uint64_t searchlength,
   p->packed = packed;
   p->roww = vsa_rowwords(querylength);
   p->maxspecial = maxspecial;
+  // VSA_PIPELINE_ROW_SLACK: the -mum candidate buffer grows to the rows it
+  // must hold and that many more, instead of twice the rows and 2^20 more
+  if (const char *e = getenv("VSA_PIPELINE_ROW_SLACK"))
+  {
+    p->rowslack = strtoull(e, nullptr, 10);
+  }
   while ((querylength >> p->lengthbits) != 0)
   {
     p->lengthbits++;
@@ -668,8 +686,7 @@ int pipeline_finish(vsa_pipeline *p, bool compact, const void **matches,
                 p->failure.c_str());
       p->failed = 0;
       p->failure.clear();
-      p->nrows = 0;
-      p->candidates = 0;
+      endjob(p);
       return frc;
     }
   }
@@ -690,8 +707,7 @@ int pipeline_finish(vsa_pipeline *p, bool compact, const void **matches,
       &res);
   if (rc != 0)
   {
-    p->nrows = 0; // (whatever the outcome, the next job starts afresh)
-    p->candidates = 0;
+    endjob(p); // (whatever the outcome, the next job starts afresh)
     return rc;
   }
   const uint64_t c = vsa_result_count(res);
@@ -756,8 +772,7 @@ int pipeline_finish(vsa_pipeline *p, bool compact, const void **matches,
     *matches = p->hostmums;
     *count = c;
   }
-  p->nrows = 0; // the next job starts afresh
-  p->candidates = 0;
+  endjob(p); // the next job starts afresh
   return out;
 }
 
