@@ -110,6 +110,15 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AlignStats(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("words", C.c_uint64),
+                ("edist", C.c_uint64), ("staged", C.c_uint64),
+                ("kernel_ms", C.c_double), ("total_device_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CoverageParams(C.Structure):
     _fields_ = [(k, C.c_int) for k in
                 ("layout", "side", "palindromic", "selfpalindromic",
@@ -458,14 +467,28 @@ def _load():
                                       U64, U64, I, U64, I, V, U64,
                                       C.POINTER(U64)]),
     }
+    # the entries of include/vstree_amd_align.h
+    align = {
+        "vsa_align_maxdist": (U32, []),
+        "vsa_align": (I, [V, V, V, C.POINTER(SinkParams), I, PP]),
+        "vsa_alignments_info": (I, [V, C.POINTER(AlignStats)]),
+        "vsa_alignments_fetch": (I, [V, V, V]),
+        "vsa_alignments_free": (None, [V]),
+        "vsa_align_host": (I, [C.POINTER(SinkParams), V, V, V, U64, I, I, V,
+                               V, U64]),
+        "vsa_align_format": (C.c_int64, [V, V, U64, V, V, V, V, V, V, U32, V,
+                                         U64]),
+        "vsa_align_write": (I, [V, V, U64, V, V, V, V, V, V, U32, V]),
+    }
     for name, (res, args) in list(sig.items()) + list(edist.items()) + \
-            list(xdrop.items()):
+            list(xdrop.items()) + list(align.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    return lib, sorted(sig), sorted(edist), sorted(xdrop)
+    return lib, sorted(sig), sorted(edist), sorted(xdrop), sorted(align)
 
 
-lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS, XDROP_ABI_SYMBOLS = _load()
+(lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS, XDROP_ABI_SYMBOLS,
+ ALIGN_ABI_SYMBOLS) = _load()
 
 
 def messagespace():
@@ -2231,3 +2254,110 @@ def extend_xdrop_seedlength(seedlength=0):
      """vmatch -l L -hxdrop X | -exdrop X [-seedlength S] IDX""",
      """the same extension on the host; arguments as for extend_hamming_host
     and hamming as above"""), flag="hamming")
+
+
+# ---- alignments: vmatch -s [W] ------------------------------------------------
+# (include/vstree_amd_align.h; a script: 16-bit words, last operation first)
+
+ALIGN_MAXRUN, ALIGN_DELETION, ALIGN_INSERTION, ALIGN_MISMATCH = (
+    16383, 0x4000, 0x8000, 0xC000)
+ALIGN_MAXDIST = int(lib.vsa_align_maxdist())
+
+
+class Alignments:
+    """The edit scripts of a match list, resident in HBM (vsa_alignments)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def stats(self):
+        s = AlignStats()
+        _check(lib.vsa_alignments_info(self._h, C.byref(s)))
+        return s
+
+    def fetch(self):
+        """-> (offsets[count + 1], words): the script of record i is
+        words[offsets[i]:offsets[i + 1]]"""
+        s = self.stats()
+        offsets = np.zeros(s.count + 1, np.uint64)
+        words = np.zeros(s.words, np.uint16)
+        _check(lib.vsa_alignments_fetch(self._h, _ptr(offsets), _ptr(words)))
+        return offsets, words
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_alignments_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def align(index, queries, matches, kind, palindromic=False):
+    """the scripts of a Result whose records have the layout `kind`
+    (SINK_...); queries: the forward batch, or None for a self kind"""
+    p = SinkParams()
+    p.kind = int(kind)
+    h = C.c_void_p()
+    _check(lib.vsa_align(index._h, None if queries is None else queries._h,
+                         matches._h, C.byref(p), int(bool(palindromic)),
+                         C.byref(h)))
+    return Alignments(h)
+
+
+def align_host(kind, text, matches, queries=None, palindromic=False,
+               threads=0):
+    """the same scripts on the host, any distance a record carries: text = the
+    symbols of the index, queries = (symbols, start, length) of the forward
+    batch, or None for a self kind -> (offsets, words)"""
+    text = np.ascontiguousarray(text, np.uint8)
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    p, keep = sink_params(
+        kind, len(text), (),
+        querystart=None if queries is None else queries[1],
+        querylength=None if queries is None else queries[2])
+    qsym = None if queries is None else np.ascontiguousarray(queries[0],
+                                                             np.uint8)
+    offsets = np.zeros(len(matches) + 1, np.uint64)
+    args = (C.byref(p), _ptr(text), _ptr(qsym), _ptr(matches), len(matches),
+            int(bool(palindromic)), int(threads), _ptr(offsets))
+    # the offsets come with the refusal of a buffer that is too small
+    words = np.zeros(16 * len(matches) + 16, np.uint16)
+    rc = lib.vsa_align_host(*args, _ptr(words), len(words))
+    if rc == -3:
+        words = np.zeros(int(offsets[-1]), np.uint16)
+        rc = lib.vsa_align_host(*args, _ptr(words), len(words))
+    _check(rc)
+    return offsets, words[:int(offsets[-1])]
+
+
+def align_format(sink, matches, offsets, words, text, origtext, queries=None,
+                 queryorig=None, linewidth=0):
+    """the match lines of `sink` (a Sink) with what vmatch -s W prints behind
+    each: origtext / queryorig are the original characters of text /
+    queries[0] -> bytes"""
+    matches = np.ascontiguousarray(matches, MATCH_DTYPE)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    words = np.ascontiguousarray(words, np.uint16)
+    text = np.ascontiguousarray(text, np.uint8)
+    origtext = np.ascontiguousarray(origtext, np.uint8)
+    qsym = None if queries is None else np.ascontiguousarray(queries[0],
+                                                             np.uint8)
+    qorig = None if queryorig is None else np.ascontiguousarray(queryorig,
+                                                                np.uint8)
+    assert len(offsets) == len(matches) + 1
+    width = int(linewidth) or 60
+    columns = int(offsets[-1]) + 2 * len(matches)
+    if len(words):
+        runs = words[(words & np.uint16(0xC000)) == 0]
+        columns += int(runs.sum(dtype=np.uint64))
+    cap = 192 * (len(matches) + 1) + 3 * columns + \
+        (3 * (width + 40) + 2) * (columns // width + len(matches) + 1)
+    buf = np.empty(cap, np.uint8)
+    n = lib.vsa_align_format(sink._h, _ptr(matches), len(matches),
+                             _ptr(offsets), _ptr(words), _ptr(text),
+                             _ptr(origtext), _ptr(qsym), _ptr(qorig),
+                             int(linewidth), _ptr(buf), cap)
+    if n < 0:
+        raise VsaError(int(n), messagespace())
+    return buf[:n].tobytes()

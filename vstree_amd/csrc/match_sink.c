@@ -34,6 +34,7 @@
 #include "sixframe_rules.h"
 
 #include "host_common.h"
+#include "sink_internal.h"
 
 #define SMALLESTEVALUE 1.0e-300 /* include/evaluedef.h:26 */
 #define MAXEXPONENTOF2 100      /* kurtz/evalues.c:51 */
@@ -77,7 +78,7 @@ typedef struct
   Cstr *identity;    /* [CACHE_MAXD+1][CACHE_MAXLEN+1] */
 } Fcache;
 
-#define LINEMAX 192 /* upper bound of one output line */
+#define LINEMAX VSA_SINK_LINEMAX /* upper bound of one output line */
 
 struct vsa_sink
 {
@@ -718,6 +719,54 @@ static int prepare(vsa_sink *s, const vsa_match *matches, uint64_t n)
     return vsa_fail(-101, "out of memory");
   }
   return 0;
+}
+
+/* ---- what align_host.c needs of the sink (sink_internal.h) ---------------- */
+
+const vsa_sinkparams *vsa_sink_params_(const vsa_sink *s)
+{
+  return &s->p;
+}
+
+int vsa_sink_prepare_(vsa_sink *s, const vsa_match *matches, uint64_t n)
+{
+  return prepare(s, matches, n);
+}
+
+void *vsa_sink_cache_new_(void)
+{
+  Fcache *c = (Fcache *) calloc(1, sizeof *c);
+
+  if (c != NULL && cache_init(c) != 0)
+  {
+    cache_free(c);
+    free(c);
+    c = NULL;
+  }
+  return c;
+}
+
+void vsa_sink_cache_free_(void *cache)
+{
+  if (cache != NULL)
+  {
+    cache_free((Fcache *) cache);
+    free(cache);
+  }
+}
+
+char *vsa_sink_line_(const vsa_sink *s, void *cache, const vsa_match *m,
+                     char *o)
+{
+  return formatmatch(s, (Fcache *) cache, m, o);
+}
+
+uint64_t vsa_sink_relpos_(const vsa_sink *s, uint64_t pos)
+{
+  uint64_t seqnum, start, length;
+
+  seqinfo(s, pos, &seqnum, &start, &length);
+  return pos - start;
 }
 
 typedef struct
