@@ -1929,4 +1929,5 @@ uint64_t vsa_extend_seedlength(uint64_t leastlength, uint64_t maxdist,
 #include "vstree_amd_edist.h"
 #include "vstree_amd_xdrop.h"
 #include "vstree_amd_align.h"
+#include "vstree_amd_online.h"
 #endif

@@ -480,15 +480,28 @@ def _load():
                                          U64]),
         "vsa_align_write": (I, [V, V, U64, V, V, V, V, V, V, U32, V]),
     }
+    # the entries of include/vstree_amd_online.h
+    online = {
+        "vsa_text_from_host": (I, [V, U64, U32, I, PP]),
+        "vsa_text_from_device": (I, [V, U64, U32, I, PP]),
+        "vsa_text_open": (I, [C.c_char_p, I, PP]),
+        "vsa_text_close": (None, [V]),
+        "vsa_findcompletematches_online": (I, [V, V, I, U64, I, I, PP]),
+        "vsa_text_findcompletematches_online": (I, [V, V, I, U64, I, I, PP]),
+        "vsa_findcompletematches_online_host": (
+            I, [V, U64, V, V, V, U64, U64, I, U64, I, I, I, V, U64,
+                C.POINTER(U64)]),
+    }
     for name, (res, args) in list(sig.items()) + list(edist.items()) + \
-            list(xdrop.items()) + list(align.items()):
+            list(xdrop.items()) + list(align.items()) + list(online.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    return lib, sorted(sig), sorted(edist), sorted(xdrop), sorted(align)
+    return (lib, sorted(sig), sorted(edist), sorted(xdrop), sorted(align),
+            sorted(online))
 
 
 (lib, ABI_SYMBOLS, EDIST_ABI_SYMBOLS, XDROP_ABI_SYMBOLS,
- ALIGN_ABI_SYMBOLS) = _load()
+ ALIGN_ABI_SYMBOLS, ONLINE_ABI_SYMBOLS) = _load()
 
 
 def messagespace():
@@ -2361,3 +2374,91 @@ def align_format(sink, matches, offsets, words, text, origtext, queries=None,
     if n < 0:
         raise VsaError(int(n), messagespace())
     return buf[:n].tobytes()
+
+
+# ---- the scan without an index: vmatch -online -complete --------------------
+# (include/vstree_amd_online.h)
+
+ONLINE_EXACT, ONLINE_EDIST, ONLINE_HAMMING = 0, 1, 2
+ONLINE_TILE_DEFAULT = 296
+
+
+class Text:
+    """The mapped text alone in one GPU's HBM (vsa_text): what vmatch -online
+    maps, TISTAB."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_host(cls, tis, numofchars=4, device=0):
+        tis = np.ascontiguousarray(tis, np.uint8)
+        h = C.c_void_p()
+        _check(lib.vsa_text_from_host(_ptr(tis), tis.shape[0], numofchars,
+                                      device, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device(cls, device_tis, totallength, numofchars=4, device=0):
+        h = C.c_void_p()
+        _check(lib.vsa_text_from_device(device_tis, int(totallength),
+                                        numofchars, device, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def open(cls, indexname, device=0):
+        """NAME.prj, NAME.al1 and NAME.tis (vsa_text_open)"""
+        h = C.c_void_p()
+        _check(lib.vsa_text_open(os.fsencode(indexname), device, C.byref(h)))
+        return cls(h)
+
+    def close(self):
+        if self._h and lib is not None:
+            lib.vsa_text_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def findcompletematches_online(where, queries, mode=ONLINE_EXACT, distvalue=0,
+                               percent=False, removeredundant=False):
+    """vmatch -online -complete [remred] [-e K | -h K] -q: the scan of the
+    text of an Index or of a Text.  mode: ONLINE_EXACT, ONLINE_EDIST (-e),
+    ONLINE_HAMMING (-h); the distance of a match travels in its querystart
+    field.  VsaError.code == NOT_COVERED: left to the CPU reference."""
+    fn = (lib.vsa_text_findcompletematches_online if isinstance(where, Text)
+          else lib.vsa_findcompletematches_online)
+    h = C.c_void_p()
+    rc = fn(where._h, queries._h, int(mode), int(distvalue), int(percent),
+            int(bool(removeredundant)), C.byref(h))
+    assert rc == 0 or not h, "a refusal delivers nothing"
+    _check(rc)
+    return Result(h)
+
+
+def findcompletematches_online_host(tis, symbols, start, length,
+                                    mode=ONLINE_EXACT, distvalue=0,
+                                    percent=False, removeredundant=False,
+                                    offset=0, threads=0, capacity=None):
+    """the same on the host (vsa_findcompletematches_online_host): query i is
+    symbols[start[i] : start[i] + length[i]] -> MATCH_DTYPE array.  The
+    capacity doubles until the list fits unless one is given."""
+    tis = np.ascontiguousarray(tis, np.uint8)
+    symbols = np.ascontiguousarray(symbols, np.uint8)
+    start = np.ascontiguousarray(start, np.uint64)
+    length = np.ascontiguousarray(length, np.uint64)
+    cap = 1 << 16 if capacity is None else int(capacity)
+    while True:
+        out = np.zeros(cap, MATCH_DTYPE)
+        n = C.c_uint64(0)
+        rc = lib.vsa_findcompletematches_online_host(
+            _ptr(tis), tis.shape[0], _ptr(symbols), _ptr(start), _ptr(length),
+            start.shape[0], int(offset), int(mode), int(distvalue),
+            int(percent), int(bool(removeredundant)), int(threads),
+            _ptr(out), cap, C.byref(n))
+        if rc == -3 and capacity is None:
+            cap *= 4
+            continue
+        _check(rc)
+        return out[:n.value].copy()

@@ -117,4 +117,42 @@ struct ApmColumn
   }
 };
 
+// long/medium/shortpatternlongestmatch (Vmengine/longestmatch.c): the
+// best-distance, then longest prefix of the vlen symbols at v, which ends at
+// a separator; a wildcard equals nothing.  Shared by the indexed search
+// (k_apm_longest) and the scan without an index (online.hip), which differ
+// in vlen alone.
+template <int W>
+__device__ __forceinline__ void
+apm_longest_prefix(const uint8_t *pattern, uint32_t m, const uint8_t *v,
+                   uint32_t vlen, uint32_t &bestlen, uint32_t &bestdist)
+{
+  ApmColumn<W> col;
+  col.init(pattern, m, false, false);
+  bestlen = 0;
+  bestdist = m;
+  bool stop = false;
+  for (uint32_t j = 0; j < vlen && !stop; j += 8)
+  {
+    // behind the text there are 64 bytes that read as separators
+    const uint64_t w8 = vsa_load8(v + j);
+    const uint32_t cnt = (vlen - j < 8) ? vlen - j : 8;
+    for (uint32_t i = 0; i < cnt; i++)
+    {
+      const uint8_t c = (uint8_t) (w8 >> (8 * i));
+      if (c == VSA_SEPARATOR)
+      {
+        stop = true;
+        break;
+      }
+      col.template step<1>(c);
+      if (bestdist >= col.score) // UPDATELENGTHANDSCORE, longestmatch.c:6-11
+      {
+        bestlen = j + i + 1;
+        bestdist = col.score;
+      }
+    }
+  }
+}
+
 #endif

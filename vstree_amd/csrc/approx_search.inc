@@ -411,32 +411,8 @@ k_apm_longest(const uint8_t *__restrict__ tis, const DevQueries qs,
   {
     vlen = (uint32_t) width;
   }
-  ApmColumn<W> col;
-  col.init(pattern, m, false, false);
-  const uint8_t *v = tis + hitpos[h];
-  uint32_t bestlen = 0, bestdist = m;
-  bool stop = false;
-  for (uint32_t j = 0; j < vlen && !stop; j += 8)
-  {
-    // behind the text there are 64 bytes that read as separators
-    const uint64_t w8 = vsa_load8(v + j);
-    const uint32_t cnt = (vlen - j < 8) ? vlen - j : 8;
-    for (uint32_t i = 0; i < cnt; i++)
-    {
-      const uint8_t c = (uint8_t) (w8 >> (8 * i));
-      if (c == VSA_SEPARATOR)
-      {
-        stop = true;
-        break;
-      }
-      col.template step<1>(c);
-      if (bestdist >= col.score) // UPDATELENGTHANDSCORE, longestmatch.c:6-11
-      {
-        bestlen = j + i + 1;
-        bestdist = col.score;
-      }
-    }
-  }
+  uint32_t bestlen, bestdist;
+  apm_longest_prefix<W>(pattern, m, tis + hitpos[h], vlen, bestlen, bestdist);
   vsa_match mt;
   mt.length = bestlen;
   mt.dbstart = hitpos[h];

@@ -339,3 +339,37 @@ done:
   unmap(&ssp);
   return rc;
 }
+
+/* The demand of vmatch -online, TISTAB alone (Vmatch/mapdemand.c:168-171):
+   IDX.prj for the length, IDX.al1 for the number of symbols, IDX.tis. */
+int vsa_text_open(const char *indexname, int device, vsa_text **text)
+{
+  Prj prj;
+  Mapped tis;
+  uint32_t numofchars = 0;
+  int rc;
+
+  if (indexname == NULL || text == NULL)
+  {
+    return vsa_fail(-1, "vsa_text_open: NULL argument");
+  }
+  *text = NULL;
+  if (readprj(indexname, &prj) != 0 ||
+      readnumofchars(indexname, &numofchars) != 0)
+  {
+    return -1;
+  }
+  if (prj.totallength >= (1ull << 40))
+  {
+    return vsa_fail(-1, "%s.prj: totallength=%lu: not the size of an index",
+                    indexname, (unsigned long) prj.totallength);
+  }
+  if (mapfile(indexname, "tis", prj.totallength, 1, &tis) != 0)
+  {
+    return -1;
+  }
+  rc = vsa_text_from_host((const uint8_t *) tis.ptr, prj.totallength,
+                          numofchars, device, text);
+  unmap(&tis);
+  return rc;
+}
