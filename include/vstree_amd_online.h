@@ -76,7 +76,12 @@ void vsa_text_close(vsa_text *text);
   visits only the pairs that have any.  VSA_ONLINE_TILE in the environment,
   read by every call, sets the symbols per tile of the edit scan (a multiple
   of 8 from 64 to the default, VSA_ONLINE_TILE_DEFAULT; a test hook, the
-  lists are the same).
+  lists are the same).  The queries are taken in chunks whose (query, tile)
+  counters fit a buffer of VSA_ONLINE_COUNTERS_DEFAULT words, and in no more
+  than 65535 groups of 32 queries; VSA_ONLINE_COUNTERS in the environment,
+  read by every call, sets that number of counters (1 to the default, other
+  values are ignored; a test hook as well).  vsa_online_plan() below tells
+  how a call is cut.
   Stats of the result: count = matches, sumlength = sum of length1,
   candidates = start positions before remred, searches = (query, tile) pairs
   the second pass visited, search_kernel_ms = HIP-event time of the two
@@ -94,6 +99,7 @@ void vsa_text_close(vsa_text *text);
   -1: NULL arguments, queries on another device.
 */
 #define VSA_ONLINE_TILE_DEFAULT 296u
+#define VSA_ONLINE_COUNTERS_DEFAULT (1ull << 26)
 int vsa_findcompletematches_online(const vsa_index *index,
                                    const vsa_queries *queries, int mode,
                                    uint64_t distvalue, int percent,
@@ -103,6 +109,22 @@ int vsa_text_findcompletematches_online(const vsa_text *text,
                                         uint64_t distvalue, int percent,
                                         int removeredundant,
                                         vsa_result **result);
+
+/*
+  A test hook, no GPU needed: how the two entries above cut a text of
+  totallength symbols and numofqueries queries, by the function the driver
+  itself calls, with VSA_ONLINE_TILE and VSA_ONLINE_COUNTERS as they stand in
+  the environment.  *tile: symbols per tile of the edit scan (mode 1), start
+  positions per tile of the window scans (modes 0 and 2, 2048); *ntiles:
+  tiles of the text, 0 for an empty one (an edit scan launches
+  ceil(ntiles / 128) workgroups per group of 32 queries, a window scan
+  ntiles); *queries_per_chunk: counters / ntiles, at least 1 and at most
+  65535 * 32; *numofchunks: 0 for an empty text or an empty batch.
+  -2: a mode outside 0 .. 2.  -1: NULL arguments.
+*/
+int vsa_online_plan(uint64_t totallength, uint64_t numofqueries, int mode,
+                    uint32_t *tile, uint64_t *ntiles,
+                    uint64_t *queries_per_chunk, uint64_t *numofchunks);
 
 /*
   The same on the host by the same rules (online_rules.h): query i is

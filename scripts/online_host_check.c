@@ -7,7 +7,10 @@
   read beyond them is seen.  The batch is scanned twice, cut into slices over
   `threads` threads and unsliced on one thread, and the two lists must be
   equal; before that the word comparison of online_rules.h is compared with a
-  loop over the bytes.
+  loop over the bytes.  The batches the test writes out include a text of low
+  complexity (every position a start position), texts of 7 and 9 symbols
+  with reads longer than the text under a percent threshold, and the empty
+  text: n = 0 and reads of any length are taken.
 
   input:  n nsymbols nq mode K percent remred threads
           n symbols of the text

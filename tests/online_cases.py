@@ -51,6 +51,24 @@ RUNS = [
     R("grumbach_exact_short", "grumbach", "short", EXACT),
 ]
 
+# low-complexity texts: every position a hit, runs of start positions as long
+# as a sequence; the period-3 text has four sequences
+for _name, _runs in (("homopolymer", "h1 e1 e1r e3 e3r"),
+                     ("period2", "h1 e1 e1r e3 e3r"),
+                     ("period3", "e1r e3r")):
+    for _w in _runs.split():
+        RUNS.append(R("%s_%s%s" % (_name, _w[:2], "_remred" * (len(_w) > 2)),
+                      "online_%s.fna" % _name, _name,
+                      EDIST if _w[0] == "e" else HAMMING, int(_w[1]),
+                      remred=len(_w) > 2))
+# texts of 7, 8 and 9 symbols with reads of n to n + 3 symbols: a staged word
+# that ends in the padding, reads longer than the text
+for _n in (7, 8, 9):
+    for _w, _mode, _k in (("exact", EXACT, 0), ("h1", HAMMING, 1),
+                          ("e1", EDIST, 1), ("e2", EDIST, 2)):
+        RUNS.append(R("tiny%d_%s" % (_n, _w), "online_tiny%d.fna" % _n,
+                      "tiny", _mode, _k))
+
 
 EMPTY = ("wildcards_e2",)   # runs without a line
 
@@ -191,6 +209,17 @@ def _short(t):
             t.tis[50000:50005].copy(), t.tis[70000:70003].copy()]
 
 
+def _periodic(unit, lengths):
+    sym = np.array(["acgt".index(c) for c in unit], np.uint8)
+    return [np.tile(sym, m // len(sym) + 1)[:m] for m in lengths]
+
+
+def _tiny(t):
+    """the text and 0 to 3 more symbols"""
+    more = np.array([0, 1, 2], np.uint8)
+    return [np.concatenate((t.tis, more[:i])) for i in range(4)]
+
+
 def reads_of(r):
     """-> H.Queries of a run (direct strand)"""
     key = (r["text"], r["reads"])
@@ -203,7 +232,15 @@ def reads_of(r):
                     "mixedshort": lambda: _mixed(t, True),
                     "wild4070": lambda: _wild4070(t),
                     "tandem": lambda: _tandem(t),
-                    "short": lambda: _short(t)}[r["reads"]]
+                    "short": lambda: _short(t),
+                    "homopolymer": lambda: _periodic("a", (4, 9, 33, 70)),
+                    "period2": lambda: [_periodic("at", (4,))[0],
+                                        _periodic("ta", (9,))[0]] +
+                    _periodic("at", (34, 80)),
+                    "period3": lambda: [_periodic("acg", (6,))[0],
+                                        _periodic("cga", (10,))[0],
+                                        _periodic("acg", (66,))[0]],
+                    "tiny": lambda: _tiny(t)}[r["reads"]]
             q = H.Queries.from_list(make())
         _reads[key] = q
     return _reads[key]
@@ -433,3 +470,277 @@ def model(edge, mode, K, percent=False, remred=False, offset=0):
     out = _model[key].copy()
     out["queryseq"] += np.uint64(offset)
     return out
+
+
+# --------------------------------------------------------------------------
+# the edges of the driver: workgroups of the edit scan, groups and chunks of
+# queries, dense hits, tiny texts.  An Edge here carries the thresholds it is
+# made for (Ks: (K, percent) pairs) and what it planted.
+# --------------------------------------------------------------------------
+
+WG_TILES = 128    # tiles a workgroup of the edit scan stages (ON_BLOCK)
+GROUP = 32        # queries a workgroup loops over (ON_GROUP)
+WTILE = 2048      # start positions of a tile of the window scans (ON_WTILE)
+MODES = ((EXACT, False), (HAMMING, False), (EDIST, False), (EDIST, True))
+
+WG_SIZES = {64: (8191, 8192, 8193, 8192 + 67, 2 * 8192 + 5),
+            None: (H_TILE * WG_TILES + 600,)}
+WG_LENGTHS = (8, 33, 65)
+WG_K = 2
+
+
+def wg_edge(tile, n, sep=0):
+    """a random text of n symbols around the border of the first workgroup of
+    the edit scan with tiles of `tile` symbols (border = 128 tiles); reads of
+    8, 33 and 65 symbols.  Each read is a window of the text that straddles
+    the border -- its start at border - m / 2, border - 1, border - m + 1 or
+    on the border, which of them turns with n -- or, where the text ends at
+    the border, the window that ends with the text or one symbol behind the
+    border.  Copies with 0 to 2 substitutions: at a second border where the
+    text has one, at n - m for one read and in front of that for the others
+    (the last tiles), and a copy of the 33-symbol read without one symbol
+    (-e alone finds it).  sep == 1: a separator at border - 1, a copy of one
+    read that starts on the border and a separator m + k behind the border;
+    sep == 2: the same one symbol further to the right (the separator on the
+    border)."""
+    T = tile or H_TILE
+    b = T * WG_TILES
+    rng = np.random.default_rng([77, T, n, sep])
+    t = rng.integers(0, 4, n).astype(np.uint8)
+    rot = (n + sep) % 4
+    reads, starts = [], []
+    for i, m in enumerate(WG_LENGTHS):
+        off = (m // 2, 1, m - 1, 0)[(i + rot) % 4]
+        if b - off + m > n:
+            off = m - 1 if b + 1 <= n else b - (n - m)
+        starts.append(b - off)
+        reads.append(t[b - off:b - off + m].copy())
+        assert len(reads[-1]) == m
+    if 2 * b + 66 <= n:
+        # the second border: the same windows, one symbol of each changed
+        t[2 * b - 65:2 * b + 66] = t[b - 65:b + 66]
+        for x in (2 * b - 3, 2 * b + 2):
+            t[x] = (int(t[x]) + 1) % 4
+    # the end of the text and the last tiles, where that is not the border
+    a, first = n, rot % 3
+    if n >= b + 66 + sum(WG_LENGTHS) + 9:
+        for j, i in enumerate([first] + [i for i in range(3) if i != first]):
+            m = WG_LENGTHS[i]
+            a -= m
+            t[a:a + m] = _mutate(rng, reads[i], j % (WG_K + 1))
+            a -= 3
+    # a deletion, in the middle of the first workgroup
+    x = b // 2 - 11
+    t[x:x + 32] = np.delete(reads[1], 16)
+    planted = dict(border=b, starts=starts, indel=x)
+    if sep:
+        s = b - 2 + sep
+        for i in ((rot + 1) % 3, 1, 0):
+            m = WG_LENGTHS[i]
+            if s + 1 + m + WG_K + 1 < min(n, a):
+                t[s + 1:s + 1 + m] = reads[i]
+                t[s + 1 + m + WG_K] = SEP
+                planted["onborder"] = (i, s + 1)
+                break
+        t[s] = SEP
+    e = Edge("wg_t%d_n%d_s%d" % (T, n, sep), t, reads)
+    e.Ks, e.planted = [(WG_K, False)], planted
+    return e
+
+
+def wg_edges(tile):
+    out = [wg_edge(tile, n) for n in WG_SIZES[tile]]
+    big = WG_SIZES[tile][-2] if tile else WG_SIZES[tile][0]
+    return out + [wg_edge(tile, big, 1), wg_edge(tile, big, 2)]
+
+
+GROUP_LENGTHS = (1, 2, 7, 8, 9, 12, 31, 32, 33, 63, 64, 65, 100, 129, 257,
+                 300)
+GROUP_NQ = (31, 32, 33, 65, 97)
+GROUP_EMPTY, GROUP_WILD40, GROUP_WILD70 = 17, 5, 13   # reads with a role
+GROUP_K0 = (1, True)    # threshold 0 for every read but the longest
+
+
+def _absent(m):
+    """a read that occurs nowhere in a text without the symbol 3"""
+    return np.full(m, 3, np.uint8)
+
+
+def groups_edge(nq, longest=300, hitters=None):
+    """a text of 3000 symbols over three of the four symbols, with the
+    fourth in what is planted only, and nq reads whose lengths cycle through
+    GROUP_LENGTHS (the last of them `longest`: 300, or 512).  Reads 0, 31, 32
+    and nq - 1 are windows of the text with a substitution each beyond 12
+    symbols; the others are random, so the short ones hit often and the long
+    ones never; with 97 reads the third group of 32 (reads 64 to 95) holds
+    reads of the absent symbol only and hits nowhere.  Read GROUP_EMPTY has
+    no symbol.  Reads GROUP_WILD40 and GROUP_WILD70 (40 and 70 symbols) carry
+    a wildcard that faces a wildcard of the text, as in wildcard_edge.
+    hitters: the reads that may hit at all (windows of the text); every other
+    read is of the absent symbol."""
+    n = 3000
+    rng = np.random.default_rng([31, nq, longest, len(hitters or ())])
+    t = rng.integers(0, 3, n).astype(np.uint8)
+    lengths = [longest if m == 300 else m
+               for m in (GROUP_LENGTHS * 7)[:nq]]
+    planted = tuple(sorted({0, 31, 32, nq - 1} & set(range(nq)))) \
+        if hitters is None else tuple(hitters)
+    silent = range(64, 96) if hitters is None and nq >= 96 else ()
+    facing, wild = {}, {}
+    if hitters is None:
+        for i, m, a in ((GROUP_WILD40, 40, 700), (GROUP_WILD70, 70, 1900)):
+            t[a + m // 3] = WILD
+            wild[i] = t[a:a + m].copy()
+            facing[i] = a
+    reads = []
+    for i, m in enumerate(lengths):
+        if i in planted:
+            q = np.array([WILD], np.uint8)
+            while (q == WILD).any():
+                a = int(rng.integers(0, n - m))
+                q = t[a:a + m].copy()
+            if m > 12:
+                q[m // 2] = 3
+        elif i in silent or hitters is not None:
+            q = _absent(m)
+        else:
+            q = rng.integers(0, 4 if m > 2 else 3, m).astype(np.uint8)
+        reads.append(q)
+    if hitters is None:
+        reads[GROUP_EMPTY] = np.zeros(0, np.uint8)
+        for i, q in wild.items():
+            reads[i] = q
+    e = Edge("groups_%d_%d_%s" % (nq, longest, "all" if hitters is None else
+                                  "-".join(map(str, planted))), t, reads)
+    e.Ks = [(5, True), (10, True), (20, True)]
+    e.planted = dict(planted=planted, silent=tuple(silent), facing=facing)
+    return e
+
+
+def uniform_edge(nq, m=41, hitters=None):
+    """nq reads of one length that is no multiple of 4, for the batch forms
+    whose symbol addressing multiplies by the absolute query number: a text
+    of 3000 symbols; every third read (or `hitters`) is a window of the text
+    with one substitution, the others are random; read 1 carries a wildcard
+    facing one of the text (a packed batch keeps it in its side list)."""
+    n = 3000
+    rng = np.random.default_rng([41, nq, m, len(hitters or ())])
+    t = rng.integers(0, 4, n).astype(np.uint8)
+    hit = set(range(0, nq, 3)) | {nq - 1} if hitters is None else set(hitters)
+    reads = []
+    for i in range(nq):
+        q = rng.integers(0, 4, m).astype(np.uint8)
+        if i in hit:
+            a = int(rng.integers(0, n - m))
+            q = t[a:a + m].copy()
+            q[m // 2] = (int(q[m // 2]) + 1) % 4
+        reads.append(q)
+    a = 1234
+    t[a:a + m] = reads[1]
+    t[a + m // 3] = reads[1][m // 3] = WILD
+    e = Edge("uniform_%d_%d_%s" % (nq, m, "third" if hitters is None else
+                                   "-".join(map(str, sorted(hit)))), t, reads)
+    e.Ks = [(2, False)]
+    e.planted = dict(planted=tuple(sorted(hit)))
+    return e
+
+
+DENSE_KINDS = ("homopolymer", "period2", "period3sep")
+DENSE_SIZES = (2047, 2048, 2049, 4200)
+DENSE_KS = ((1, True), (1, False), (3, False))   # 1 percent: threshold 0
+
+
+def dense_edge(kind, n):
+    """low-complexity text: a homopolymer, a text of period 2, one of period
+    3 with a separator every 701 symbols; reads of 4, 9, 33 and 66 symbols of
+    the same period and one out of phase (a foreign symbol for the
+    homopolymer)."""
+    unit = {"homopolymer": [0], "period2": [0, 3],
+            "period3sep": [0, 1, 2]}[kind]
+    p = len(unit)
+    t = np.tile(np.array(unit, np.uint8), n // p + 1)[:n]
+    if kind == "period3sep":
+        t[700::701] = SEP
+    reads = [np.tile(np.array(unit, np.uint8), m // p + 1)[:m]
+             for m in (4, 9, 33, 66)]
+    if p == 1:
+        reads.append(np.full(4, 1, np.uint8))
+    else:
+        reads.append(np.tile(np.array(unit[1:] + unit[:1], np.uint8), 5))
+    e = Edge("dense_%s_%d" % (kind, n), t, reads)
+    e.Ks, e.planted = list(DENSE_KS), {}
+    return e
+
+
+TINY_SIZES = (1, 2, 3, 7, 8, 9, 63, 64, 65)
+# a read of one symbol is in the batch: -e on the device takes thresholds
+# below 1 for it, i.e. K = 0 or a percentage.  50 percent of 2, 4 and 8
+# symbols is 1, 2 and 4.
+TINY_KS = ((0, False), (20, True), (50, True))
+
+
+def tiny_edge(n, sep=False):
+    """a text of n symbols; reads: the text, the text and 1 and 3 more
+    symbols, the text without its last symbol (not for n = 1), one foreign
+    symbol.  sep: a separator in the middle of the text (the reads keep the
+    symbol it replaces)."""
+    rng = np.random.default_rng([11, n])
+    t = rng.integers(0, 3, n).astype(np.uint8)
+    more = rng.integers(0, 3, 3).astype(np.uint8)
+    reads = [t.copy(), np.concatenate((t, more[:1])), np.concatenate((t, more))]
+    if n > 1:
+        reads.append(t[:-1].copy())
+    reads.append(_absent(1))
+    if sep:
+        t[n // 2] = SEP
+    e = Edge("tiny_%d_%d" % (n, int(sep)), t, reads)
+    e.Ks, e.planted = list(TINY_KS), {}
+    return e
+
+
+def empty_edges():
+    """the empty text with reads, and a text with an empty batch"""
+    a = Edge("tiny_0", np.zeros(0, np.uint8), tiny_edge(3).reads)
+    b = Edge("tiny_noreads", tiny_edge(9).text, [])
+    a.Ks = b.Ks = [(0, False), (50, True)]
+    return [a, b]
+
+
+def modes_of(edge, K, percent, device=True):
+    """the (mode, remred) pairs a threshold goes with: a fixed K above 0
+    says nothing new for exact; -e on the device refuses a threshold that is
+    not below every read"""
+    out = []
+    for mode, remred in MODES:
+        if mode == EXACT and (percent or K != edge.Ks[0][0]) and \
+                (K, percent) != edge.Ks[0]:
+            continue
+        if mode == EDIST and device and edge.reads and \
+                (K >= 100 if percent else
+                 K >= min(len(q) for q in edge.reads)):
+            continue
+        out.append((mode, remred))
+    return out
+
+
+def edge_model(edge, mode, K, percent=False, remred=False, offset=0):
+    """model() with the list left unchanged for the next test"""
+    return model(edge, mode, K, percent, remred, offset)
+
+
+def expected_stats(edge, mode, K, percent, tile):
+    """(candidates, searches) the device must report: the start positions
+    before remred, and the distinct (query, tile) pairs they lie in -- tiles
+    of `tile` symbols for -e, of WTILE start positions otherwise"""
+    plain = model(edge, mode, K, percent, False)
+    T = (tile or H_TILE) if mode == EDIST else WTILE
+    pairs = set(zip(plain["queryseq"].tolist(),
+                    (plain["dbstart"] // np.uint64(T)).tolist()))
+    return len(plain), len(pairs)
+
+
+def setcounters(monkeypatch, counters):
+    if counters is None:
+        monkeypatch.delenv("VSA_ONLINE_COUNTERS", raising=False)
+    else:
+        monkeypatch.setenv("VSA_ONLINE_COUNTERS", str(counters))

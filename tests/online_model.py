@@ -17,6 +17,8 @@ which changes no bit below m.
     findedistcompletematchesonline    edistcompl.c:458-513
     findcompletematches               fcomplete.c:209-261 over all queries
 """
+import functools
+
 import numpy as np
 
 SEPARATOR = 255
@@ -129,9 +131,20 @@ def longpatternlongestmatch(u, v):
     return longest
 
 
+@functools.lru_cache(maxsize=1 << 14)
+def _longestmatch(pattern, v):
+    """(what the two functions return depends on their arguments alone: in a
+    text of low complexity the same stretch comes up thousands of times)"""
+    if len(pattern) > 64:
+        return longpatternlongestmatch(pattern, v)
+    return shortpatternlongestmatch(getEqs(pattern), len(pattern), v)
+
+
 def edistprocessstartpos(seq, pattern, startpos, maxlength, process):
     v = seq[startpos:startpos + maxlength]
-    if len(pattern) > 64:
+    if isinstance(seq, bytes) and isinstance(pattern, bytes):
+        longest = _longestmatch(pattern, v)
+    elif len(pattern) > 64:
         longest = longpatternlongestmatch(pattern, v)
     else:
         longest = shortpatternlongestmatch(getEqs(pattern), len(pattern), v)
@@ -299,7 +312,4 @@ def findcompletematches(seq, queries, mode, distvalue=0, percent=False,
         for length, pos, dist in query_matches(seq, q, mode, distvalue,
                                                percent, removeredundant, info):
             rows.append((length, pos, i + offset, abs(dist)))
-    out = np.zeros(len(rows), MATCH_DTYPE)
-    for i, r in enumerate(rows):
-        out[i] = r
-    return out
+    return np.array(rows, MATCH_DTYPE).reshape(-1)

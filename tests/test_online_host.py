@@ -48,7 +48,7 @@ def test_host_code_equals_every_recorded_list(V, key):
 
 def test_the_recorded_runs_are_the_ones_the_issue_names():
     m = OC.manifest()
-    assert set(m) == set(OC.golden_keys()) and len(m) == 16
+    assert set(m) == set(OC.golden_keys()) and len(m) == 40
     for key, e in m.items():
         assert e["lines"] <= 6000 and "-online" in e["args"] and \
             "-complete" in e["args"]
@@ -73,6 +73,18 @@ def test_the_recorded_runs_are_the_ones_the_issue_names():
     assert any(e["wildvswild"] > 0 for e in m.values())
     assert any(e["rawhits"] > 0 for e in m.values())
     assert any(e["abovethreshold"] > 0 for e in m.values())
+    # a read longer than its text; low complexity: remred drops more than
+    # 1000 hits of a run of start positions as long as the text
+    assert any(max(e["lengths"], default=0) > OC.text_of(OC.run_of(k)).n or
+               max(OC.reads_of(OC.run_of(k)).length) >
+               OC.text_of(OC.run_of(k)).n for k, e in m.items())
+    assert any(e["remred"] and e["dropped"] > 1000 and
+               m[k.replace("_remred", "")]["lines"] - e["lines"] > 1000
+               for k, e in m.items())
+    for name in ("homopolymer", "period2", "period3", "tiny7", "tiny8",
+                 "tiny9"):
+        assert os.path.getsize(os.path.join(
+            H.GOLDEN, "online_%s.fna" % name)) < 1024
     r = OC.run_of("grumbach_exact_short")
     assert max(OC.reads_of(r).length) < OC.text_of(r).prefixlength
     for name in ("online_manifest.json", "online_expected.npz"):
@@ -168,7 +180,7 @@ def test_every_entry_of_the_header_has_its_mirror(V):
     text = open(os.path.join(H.ROOT, "include", "vstree_amd_online.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     syms = sorted(set(re.findall(r"\b(vsa_[a-z0-9_]+)\s*\(", text)))
-    assert len(syms) == 7 and syms == V.ONLINE_ABI_SYMBOLS
+    assert len(syms) == 8 and syms == V.ONLINE_ABI_SYMBOLS
     out = subprocess.check_output(["nm", "-D", "--defined-only",
                                    V.LIBPATH_NORT]).decode()
     have = {l.split()[-1] for l in out.splitlines() if l}
@@ -176,6 +188,8 @@ def test_every_entry_of_the_header_has_its_mirror(V):
     assert re.search(r"#define VSA_ONLINE_TILE_DEFAULT\s+%du\b"
                      % V.ONLINE_TILE_DEFAULT, text)
     assert OC.H_TILE == V.ONLINE_TILE_DEFAULT
+    assert re.search(r"#define VSA_ONLINE_COUNTERS_DEFAULT\s+\(1ull << 26\)",
+                     text) and V.ONLINE_COUNTERS_DEFAULT == 1 << 26
     main = open(os.path.join(H.ROOT, "include", "vstree_amd.h")).read()
     assert '#include "vstree_amd_online.h"' in main
 
@@ -208,18 +222,26 @@ def test_host_code_under_the_sanitizers_as_a_program_of_its_own(tmp_path):
         return subprocess.run([exe, path], stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE)
 
-    cases = [(OC.borders_edge(33, 3), 3), (OC.borders_edge(65, 6), 6),
-             (OC.borders_edge(1, 0), 0), (OC.remred_edge(), 2),
-             (OC.wildcard_edge(70, 2), 2)]
-    for edge, k in cases:
+    # (a dense text: every position a start position, runs of them as long
+    # as a sequence; a tiny one: reads longer than the text, 50 percent of
+    # them as the threshold)
+    cases = [(OC.borders_edge(33, 3), 3, 0), (OC.borders_edge(65, 6), 6, 0),
+             (OC.borders_edge(1, 0), 0, 0), (OC.remred_edge(), 2, 0),
+             (OC.wildcard_edge(70, 2), 2, 0),
+             (OC.dense_edge("period3sep", 2049), 3, 0),
+             (OC.tiny_edge(7), 50, 1), (OC.tiny_edge(9, True), 50, 1),
+             (OC.empty_edges()[0], 0, 0)]
+    for edge, k, percent in cases:
         for mode, remred in ((OC.EXACT, False), (OC.HAMMING, False),
                              (OC.EDIST, False), (OC.EDIST, True)):
-            p = run(edge, mode, k, remred, 5)
+            p = run(edge, mode, k, remred, 5, percent)
             assert p.returncode == 0, p.stderr.decode()
             assert b"Sanitizer" not in p.stderr and b"runtime error" not in \
                 p.stderr
-            want = OM.findcompletematches(edge.text, edge.reads, mode, k,
-                                          False, remred)
+            want = OC.model(edge, mode, k, bool(percent), remred) \
+                if hasattr(edge, "Ks") else \
+                OM.findcompletematches(edge.text, edge.reads, mode, k,
+                                       False, remred)
             got = np.array([[int(v) for v in l.split()]
                             for l in p.stdout.decode().splitlines()],
                            np.int64).reshape(-1, 4)

@@ -491,6 +491,8 @@ def _load():
         "vsa_findcompletematches_online_host": (
             I, [V, U64, V, V, V, U64, U64, I, U64, I, I, I, V, U64,
                 C.POINTER(U64)]),
+        "vsa_online_plan": (I, [U64, U64, I, C.POINTER(U32), C.POINTER(U64),
+                                C.POINTER(U64), C.POINTER(U64)]),
     }
     for name, (res, args) in list(sig.items()) + list(edist.items()) + \
             list(xdrop.items()) + list(align.items()) + list(online.items()):
@@ -2435,6 +2437,29 @@ def findcompletematches_online(where, queries, mode=ONLINE_EXACT, distvalue=0,
     assert rc == 0 or not h, "a refusal delivers nothing"
     _check(rc)
     return Result(h)
+
+
+ONLINE_COUNTERS_DEFAULT = 1 << 26
+
+
+class OnlinePlan(tuple):
+    """(tile, ntiles, queries_per_chunk, numofchunks) of vsa_online_plan"""
+    tile = property(lambda s: s[0])
+    ntiles = property(lambda s: s[1])
+    queries_per_chunk = property(lambda s: s[2])
+    numofchunks = property(lambda s: s[3])
+
+
+def online_plan(totallength, numofqueries, mode=ONLINE_EXACT):
+    """how findcompletematches_online cuts a text and a batch
+    (vsa_online_plan; a test hook, no GPU needed): symbols or start positions
+    per tile, tiles of the text, queries per chunk, chunks -- with
+    VSA_ONLINE_TILE and VSA_ONLINE_COUNTERS as the environment has them."""
+    tile = C.c_uint32(0)
+    out = [C.c_uint64(0) for _ in range(3)]
+    _check(lib.vsa_online_plan(int(totallength), int(numofqueries), int(mode),
+                               C.byref(tile), *[C.byref(x) for x in out]))
+    return OnlinePlan([int(tile.value)] + [int(x.value) for x in out])
 
 
 def findcompletematches_online_host(tis, symbols, start, length,

@@ -4,7 +4,8 @@
 //
 // Both device entries go through one driver over a "text view" (the padded
 // text of a vsa_index or of a vsa_text).  The queries are taken in chunks
-// whose (query, tile) counters fit ON_COUNTERS words; per chunk:
+// whose (query, tile) counters fit ON_COUNTERS words (VSA_ONLINE_COUNTERS in
+// the environment: fewer; plan() is the arithmetic); per chunk:
 //
 //   edit distance
 //     count    k_online_edist_count: a work-item is (query, tile of T
@@ -45,7 +46,8 @@
 #define ON_WBLOCK 256
 #define ON_WROUNDS 8
 #define ON_WTILE (ON_WBLOCK * ON_WROUNDS) // start positions of a window tile
-#define ON_COUNTERS (1ull << 26) // (query, tile) counters of one chunk
+// (query, tile) counters of one chunk
+#define ON_COUNTERS VSA_ONLINE_COUNTERS_DEFAULT
 #define ON_MAXGROUPS 65535ull    // the y dimension of a grid
 
 struct vsa_text
@@ -471,6 +473,45 @@ uint32_t tilesize()
   return t;
 }
 
+// (query, tile) counters of a chunk: VSA_ONLINE_COUNTERS, from 1 to the
+// default
+uint64_t countersize()
+{
+  const char *s = getenv("VSA_ONLINE_COUNTERS");
+  uint64_t n = ON_COUNTERS;
+  if (s != nullptr && *s != '\0')
+  {
+    const unsigned long long v = strtoull(s, nullptr, 10);
+    if (v >= 1 && v <= ON_COUNTERS)
+    {
+      n = v;
+    }
+  }
+  return n;
+}
+
+// how a call cuts its work: the arithmetic of the driver, which
+// vsa_online_plan shows to the tests
+struct Plan
+{
+  uint32_t tile;   // symbols (edit scan) or start positions of a tile
+  uint64_t ntiles; // 0 for an empty text
+  uint64_t step;   // queries of a chunk
+  uint64_t chunks; // 0 where nothing is scanned
+};
+
+Plan plan(uint64_t n, uint64_t nq, int mode)
+{
+  Plan p;
+  p.tile = mode == VSA_ONLINE_EDIST ? tilesize() : (uint32_t) ON_WTILE;
+  p.ntiles = n / p.tile + (n % p.tile != 0 ? 1 : 0);
+  p.step = countersize() / std::max<uint64_t>(1, p.ntiles);
+  p.step = std::max<uint64_t>(1, p.step);
+  p.step = std::min<uint64_t>(p.step, ON_MAXGROUPS * ON_GROUP);
+  p.chunks = n > 0 ? nq / p.step + (nq % p.step != 0 ? 1 : 0) : 0;
+  return p;
+}
+
 struct Chunk
 {
   void *matches;
@@ -772,16 +813,15 @@ int online_run(const TextView &tv, const vsa_queries *queries, int mode,
     c.distvalue = distvalue;
     c.percent = percent;
     c.mode = mode;
-    const uint32_t T = tilesize();
-    c.ntiles = mode == VSA_ONLINE_EDIST ? (tv.n + T - 1) / T
-                                        : (tv.n + ON_WTILE - 1) / ON_WTILE;
+    const Plan pl = plan(tv.n, nq, mode);
+    const uint32_t T = pl.tile; // (of the edit scan only)
+    c.ntiles = pl.ntiles;
     const uint64_t maxm = queries->maxlength,
                    maxk = vsa_online_threshold(maxm, distvalue, percent);
     const uint32_t warmmax =
         ((uint32_t) vsa_online_warmup(maxm, maxk < maxm ? maxk : maxm) + 7u) &
         ~7u;
-    uint64_t step = std::max<uint64_t>(1, ON_COUNTERS / c.ntiles);
-    step = std::min<uint64_t>(step, ON_MAXGROUPS * ON_GROUP);
+    const uint64_t step = pl.step;
     for (uint64_t q0 = 0; q0 < nq && rc == 0; q0 += step)
     {
       Chunk ch = {nullptr, 0};
@@ -930,6 +970,31 @@ int text_fill(const void *src, uint64_t n, uint32_t numofchars, int device,
 }
 
 } // namespace
+
+extern "C" int vsa_online_plan(uint64_t totallength, uint64_t numofqueries,
+                               int mode, uint32_t *tile, uint64_t *ntiles,
+                               uint64_t *queries_per_chunk,
+                               uint64_t *numofchunks)
+{
+  if (tile == nullptr || ntiles == nullptr || queries_per_chunk == nullptr ||
+      numofchunks == nullptr)
+  {
+    VSA_ERROR("vsa_online_plan: NULL argument");
+    return -1;
+  }
+  if (mode < VSA_ONLINE_EXACT || mode > VSA_ONLINE_HAMMING)
+  {
+    VSA_ERROR("vsa_online_plan: mode %d: expected mode 0 (exact), 1 (-e) or 2 "
+              "(-h)", mode);
+    return -2;
+  }
+  const Plan p = plan(totallength, numofqueries, mode);
+  *tile = p.tile;
+  *ntiles = p.ntiles;
+  *queries_per_chunk = p.step;
+  *numofchunks = p.chunks;
+  return 0;
+}
 
 extern "C" int vsa_text_from_host(const uint8_t *tis, uint64_t totallength,
                                   uint32_t numofchars, int device,
